@@ -1,7 +1,7 @@
 """Headline benchmark: diffusion mel-frames/s of one full GaussianDiffusion.forward(infer=True)
 (conditioner once + 100 x (DiffNet + posterior step)) at B=32 per GPU, T=800, fp32.
 
-  python bench.py --gpus N --steps K --warmup W [--mode infer|train] [--dtype f32|bf16]
+  python bench.py --gpus N --steps K --warmup W [--mode infer|train] [--dtype f32|bf16] [--dump-outputs DIR]
 
 With N > 1 and no WORLD_SIZE in the environment the script re-launches itself as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -380,6 +380,50 @@ def device_identity(dev):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20  # --dump-outputs: all files of one run together (payload + .npy headers)
+
+
+def host_outputs(named):
+    """The tensors among `named` (what a caller of the timed path receives; timings and other plain values are left out), on the host:
+    float64 stays float64, other floating types become float32, integer and bool outputs float64 (exact below 2**53)."""
+    out = {}
+    for name, v in named.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            v = v.double() if v.dtype == torch.float64 or not v.is_floating_point() else v.float()
+            out[name] = v.cpu().numpy()
+    return out
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write every array as out_dir/<name>.npy, within `budget` bytes in all.  When the arrays are larger than that, each keeps the same
+    fraction of its elements: a seeded choice of flat indices in ascending order, written as a 1-D array -- the same elements for the
+    same shapes in every run, so that two builds compare output for output.  Returns {name: {"shape", "dtype"[, "sampled_elements"]}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    payload = sum(a.nbytes for a in arrays.values())
+    room = budget - 256 * len(arrays)  # an .npy header is 128 bytes for these shapes
+    frac = min(1.0, room / payload) if payload else 1.0
+    info = {}
+    for name, a in sorted(arrays.items()):
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        keep = max(1, int(a.size * frac))
+        if keep < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, keep, replace=False))]
+            entry["sampled_elements"] = keep
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        info[name] = entry
+    return info
+
+
+def dump_rank_outputs(args, rank, world, arrays):
+    """--dump-outputs DIR: rank 0 writes DIR/<name>.npy, rank r > 0 its own shard's outputs to DIR/rank<r>/; the budget is shared."""
+    if not args.dump_outputs:
+        return None
+    out_dir = args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, "rank%d" % rank)
+    return {"dir": args.dump_outputs, "arrays": dump_outputs(out_dir, arrays, DUMP_BUDGET_BYTES // world)}
+
+
 def run_infer(args, rank, world, dev):
     from set_amd import _lib, parallel
     from set_amd.synthetic import synthetic_inputs
@@ -409,6 +453,8 @@ def run_infer(args, rank, world, dev):
     elapsed = time.perf_counter() - t0
     parallel.barrier()
     t_max = parallel.max_over_ranks(elapsed, device=dev if world > 1 else "cpu")
+    # the last timed step's outputs, copied before anything else runs on the device
+    dumped = dump_rank_outputs(args, rank, world, host_outputs(ret))
     assert torch.isfinite(ret["mel_out"]).all()
     assert ret["mel_out"].shape[0] == B_PER_GPU, "this rank did not get %d utterances of the global batch" % B_PER_GPU
     facts = dist_facts(dev, world, elapsed)
@@ -548,6 +594,8 @@ def run_infer(args, rank, world, dev):
                               "loop on the exact 24-bit splitting")
                      if split_operands else None},
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     if extras and not args.no_quality:
         out.update(quality_vs_oracle(model))
     if extras and split_operands and not args.no_native_fp32:
@@ -977,6 +1025,9 @@ def run_train(args, rank, world, dev):
     elapsed = time.perf_counter() - t0
     parallel.barrier()
     t_max = parallel.max_over_ranks(elapsed, device=dev if world > 1 else "cpu")
+    # the last timed step: its loss, the loss terms and the parameters it left (flat), before the extra steps below
+    dumped = dump_rank_outputs(args, rank, world, host_outputs(
+        {"loss": total, **{"loss_" + k: v for k, v in parts.items()}, "params": opt.flat_p}))
     facts = dist_facts(dev, world, elapsed)
     assert torch.isfinite(total).all()
     same_after = True
@@ -1029,6 +1080,7 @@ def run_train(args, rank, world, dev):
         "whole_step": None if stub_device() else {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s", "frac": ach / peak,
                                                   "flop_per_step": flop / args.steps},
         "launches_per_step": None if stub_device() else _profiled("launches_per_step", "campnet" if campnet else "spec_denoiser", args.dtype),
+        **({"dump_outputs": dumped} if dumped else {}),
     }
 
 
@@ -1048,7 +1100,12 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the sub-benchmarks of BASELINE configs[1], [3], [4] (sub-processes)")
     ap.add_argument("--model", choices=("spec_denoiser", "campnet"), default="spec_denoiser",
                     help="train mode only: campnet = BASELINE configs[4] (B=16/GPU, T=800)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: a fixed seeded sample of larger outputs); the inputs are the same in every run")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     stub = stub_device()
     if not stub and not torch.cuda.is_available():
@@ -1058,7 +1115,7 @@ def main():
     import set_amd  # noqa: F401
     from set_amd import _lib, parallel
     _lib.build()
-    rank, world, local_rank = parallel.init_from_env()
+    rank, world, local_rank = parallel.init_from_env(backend="gloo" if stub else None)  # the stub runs on CPU even where GPUs are visible
     if world != args.gpus:
         raise SystemExit("bench.py --gpus %d but the launcher started %d rank(s)" % (args.gpus, world))
     if stub:

@@ -250,10 +250,14 @@ def denorm_f0(f0, uv, pitch_padding=None, fmin=50, fmax=900):
 
 
 def f0_to_coarse(f0, f0_bin=256, f0_max=900.0, f0_min=50.0):
-    """utils/audio/pitch/utils.py:17-28 -> int64 bins 1..255."""
+    """utils/audio/pitch/utils.py:17-28 -> int64 bins 1..255.
+
+    The fp32 log is taken in fp64 and rounded: torch-CPU's fp32 log differs in the last ulp between host CPUs (MKL picks its code path
+    by instruction set), which moves 2-3 of the 8.9 M fp32 inputs of the committed reference run (tests/golden/pitch_edges.npz,
+    csrc/pitch_edges.h) into the neighbouring bin; the rounded fp64 log reproduces that run at every one of them on each of MKL's paths."""
     mel_min = 1127 * np.log(1 + f0_min / 700)
     mel_max = 1127 * np.log(1 + f0_max / 700)
-    m = 1127 * (1 + f0 / 700).log()
+    m = 1127 * (1 + f0 / 700).double().log().float()
     m = torch.where(m > 0, (m - mel_min) * (f0_bin - 2) / (mel_max - mel_min) + 1, m)
     m = torch.where(m <= 1, torch.ones_like(m), m)
     m = torch.where(m > f0_bin - 1, torch.full_like(m, f0_bin - 1), m)

@@ -3,8 +3,9 @@
 * section A (registry swap) -- build container only: the reference is imported through oracle/ref_import.py, the block is executed
   verbatim (with the checkout path filled in), the model is built through the REFERENCE's own SpeechDenoiserTask.build_tts_model
   (tasks/speech_editing/spec_denoiser.py:29-36) and a state dict produced by the reference's own classes is loaded with strict=True;
-  the vocoder registry (tasks/tts/vocoder_infer/base_vocoder.py:6-18) hands out this package's wrapper.  Skipped where /root/reference is absent
-  (the GPU box).
+  the vocoder registry (tasks/tts/vocoder_infer/base_vocoder.py:6-18) hands out this package's wrapper.  Skipped where the reference
+  checkout is absent (oracle/ref_import.py); the same block also runs against stand-ins of the two registry modules it patches, with the
+  reference's state_dict layout from tests/golden/.
 * section B (raw ctypes binding of one ResidualBlock.forward, diffnet.py:60-81) -- `-m gpu`: the block is executed verbatim in a namespace that
   has never imported this package (only ctypes + torch + the path of the built library) and its output is compared with the reference's own
   layer trace in tests/golden/infer_tiny.npz.
@@ -35,7 +36,55 @@ def test_integration_md_has_the_three_blocks():
     assert "set_attention" in blocks[2]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tasks/speech_editing"), reason="the reference checkout is not on this box")
+def _reference_available():
+    sys.path.insert(0, ROOT)
+    from oracle import ref_import
+    return ref_import.available()
+
+
+def test_section_a_registry_swap_on_stand_in_registries(monkeypatch):
+    """Section A without the reference checkout: the block runs verbatim against stand-ins of the two reference modules it patches
+    (nothing but the registry names it assigns to), the patched `GaussianDiffusion` / `DIFF_DECODERS["wavenet"]` build this package's
+    model with the reference's constructor keywords, and that model has the reference's state_dict layout (tests/golden/
+    manifest_spec_denoiser.json, written from the reference's own model) and loads it with strict=True."""
+    import types
+    from conftest import base_hparams
+    from oracle import weights as Wt
+    hp = base_hparams(timesteps=4)  # the schedule length the manifest was written with
+    ref_task = types.ModuleType("tasks.speech_editing.spec_denoiser")
+    ref_task.DIFF_DECODERS, ref_task.GaussianDiffusion, ref_task.hparams = {}, None, hp
+    ref_voc = types.ModuleType("tasks.tts.vocoder_infer.base_vocoder")
+    ref_voc.REGISTERED_VOCODERS = {}
+    mods = {"tasks": types.ModuleType("tasks"), "tasks.speech_editing": types.ModuleType("tasks.speech_editing"),
+            "tasks.speech_editing.spec_denoiser": ref_task, "tasks.tts": types.ModuleType("tasks.tts"),
+            "tasks.tts.vocoder_infer": types.ModuleType("tasks.tts.vocoder_infer"), "tasks.tts.vocoder_infer.base_vocoder": ref_voc}
+    for name, mod in mods.items():
+        monkeypatch.setitem(sys.modules, name, mod)
+        parent, _, child = name.rpartition(".")
+        if parent:
+            setattr(mods[parent], child, mod)
+    monkeypatch.setattr(sys, "path", list(sys.path))
+    ns = {}
+    exec(compile(_python_blocks()[0].replace("/path/to/this/repo", ROOT), "INTEGRATION.md#A", "exec"), ns)
+    from set_amd import vocoder_infer as amd_voc
+    from set_amd.diffnet import DiffNet as AmdDiffNet
+    from set_amd.spec_denoiser import GaussianDiffusion as AmdGD
+    assert ref_voc.REGISTERED_VOCODERS == {"HifiGAN": amd_voc.HifiGAN}
+    dn = ref_task.DIFF_DECODERS["wavenet"](hp)
+    model = ref_task.GaussianDiffusion(phone_encoder=list(range(80)), out_dims=80, denoise_fn=dn, timesteps=4, time_scale=1,
+                                       loss_type="l1", spec_min=[], spec_max=[])
+    assert isinstance(model, AmdGD) and isinstance(model.denoise_fn, AmdDiffNet) and model.num_timesteps == 4
+    manifest = Wt.load_manifest("spec_denoiser")
+    assert [(k, tuple(v.shape)) for k, v in model.state_dict().items()] == manifest and len(manifest) == 339
+    sd = dict(model.state_dict())
+    sd.update(Wt.seeded_weights(manifest, 3))
+    missing, unexpected = model.load_state_dict(sd, strict=True)
+    assert not missing and not unexpected
+    for k, v in model.state_dict().items():
+        assert torch.equal(v, sd[k]), k
+
+
+@pytest.mark.skipif(not _reference_available(), reason="the reference checkout is not available")
 def test_section_a_registry_swap_inside_the_reference(tmp_path):
     """In a process of its own (the reference's top-level packages `utils`, `modules`, `tasks` stay out of this one)."""
     block = _python_blocks()[0].replace("/path/to/this/repo", ROOT)
