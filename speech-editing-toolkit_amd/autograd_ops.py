@@ -956,18 +956,6 @@ def sum_losses(vals):
     return _SumLossesFn.apply(*vals)
 
 
-def _bf16_layer_pointers(dn, layers, imgs):
-    """[(image, b_dil, b_cond, b_out, dilation)] of the residual layers as integers, cached on the DiffNet while the tensors stay where they are
-    (parameters are views of the optimizer's flat buffer; the images are rebuilt in place)."""
-    key = (imgs[0].data_ptr(), imgs[-1].data_ptr(), layers[0].dilated_conv.bias.data_ptr(), layers[-1].output_projection.bias.data_ptr(), len(layers))
-    ent = getattr(dn, "_bf16_ptrs", None)
-    if ent is None or ent[0] != key:
-        ent = (key, [(imgs[l].data_ptr(), ly.dilated_conv.bias.data_ptr(), ly.conditioner_projection.bias.data_ptr(),
-                      ly.output_projection.bias.data_ptr(), int(ly.dilation)) for l, ly in enumerate(layers)])
-        dn._bf16_ptrs = ent
-    return ent[1]
-
-
 SWEEP_EVENTS = None  # bench.py sets a list: (start, end, launches) hipEvent pairs around the layer-backward sweep of every step
 
 
@@ -983,8 +971,7 @@ class _DiffNetStackBf16Fn(torch.autograd.Function):
         hx, cond, dmat = hx.contiguous(), cond.contiguous(), dmat.contiguous()
         B, _, T = hx.shape
         dev = hx.device
-        layers = list(dn.residual_layers)
-        imgs = dn.bf16_layer_images()
+        imgs, per = dn.bf16_layer_images(params)
         x_all = torch.empty(L_ + 1, B, C_, T, dtype=torch.float32, device=dev)
         x_all[0].copy_(hx)
         y16 = torch.empty(L_, B, 2 * C_, T, dtype=torch.bfloat16, device=dev)
@@ -998,7 +985,6 @@ class _DiffNetStackBf16Fn(torch.autograd.Function):
         # in this loop and the backward sweep: the step is bound by the host's enqueue time)
         x0, sx = x_all.data_ptr(), 4 * B * C_ * T
         y0, z0, d0 = y16.data_ptr(), z16.data_ptr(), dmat.data_ptr()
-        per = _bf16_layer_pointers(dn, layers, imgs)
         fn, st, ref = L().set_diffnet_layer_fwd_bf16, _stream(), C.byref(a)
         for l in range(L_):
             a.x_in, a.x_out = x0 + l * sx, x0 + (l + 1) * sx
@@ -1007,13 +993,13 @@ class _DiffNetStackBf16Fn(torch.autograd.Function):
             a.y16, a.z16 = y0 + l * sx, z0 + l * (sx // 2)  # bf16 [B][2C][T] and [B][C][T]
             a.first = int(l == 0)
             check(fn(ref, st), "set_diffnet_layer_fwd_bf16")
-        ctx.dn, ctx.imgs = dn, imgs
+        ctx.dn, ctx.imgs, ctx.per = dn, imgs, per
         ctx.save_for_backward(cond, dmat, x_all, y16, z16)
         return skip
 
     @staticmethod
     def backward(ctx, dskip):
-        dn, imgs = ctx.dn, ctx.imgs
+        dn, imgs, per = ctx.dn, ctx.imgs, ctx.per
         cond, dmat, x_all, y16, z16 = ctx.saved_tensors
         L_, C_ = dn.n_layers, dn.C
         B, H, T = cond.shape
@@ -1050,7 +1036,6 @@ class _DiffNetStackBf16Fn(torch.autograd.Function):
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
         if grouped:  # the sweep as 20 launches on integer addresses (see forward); everything else of this form happens after the loop
-            per = _bf16_layer_pointers(dn, layers, imgs)
             dy0, do0, y0, s16 = dy16_all.data_ptr(), do16_all.data_ptr(), y16.data_ptr(), 2 * B * 2 * C_ * T
             pb0, py0, pd0, sp = pdbo_all.data_ptr(), pdby_all.data_ptr(), pdd_all.data_ptr(), 4 * B * tiles_g * C_
             dxp = (dx[0].data_ptr(), dx[1].data_ptr())
@@ -1208,19 +1193,11 @@ def step_projections(dn, h):
 
 
 def diffnet_stack_train_bf16(dn, hx, cond, dmat):
-    params = []
-    for layer in dn.residual_layers:
-        params += [layer.conditioner_projection.weight, layer.conditioner_projection.bias, layer.dilated_conv.weight,
-                   layer.dilated_conv.bias, layer.output_projection.weight, layer.output_projection.bias]
-    return _DiffNetStackBf16Fn.apply(dn, hx, cond, dmat, *params)
+    return _DiffNetStackBf16Fn.apply(dn, hx, cond, dmat, *dn.stack_params())
 
 
 def diffnet_stack_train(dn, hx, cond, dmat):
-    params = []
-    for layer in dn.residual_layers:
-        params += [layer.conditioner_projection.weight, layer.conditioner_projection.bias, layer.dilated_conv.weight,
-                   layer.dilated_conv.bias, layer.output_projection.weight, layer.output_projection.bias]
-    return _DiffNetStackFn.apply(dn, hx, cond, dmat, *params)
+    return _DiffNetStackFn.apply(dn, hx, cond, dmat, *dn.stack_params())
 
 
 # --------------------------------------------------------------------------------------------------

@@ -36,16 +36,11 @@ class ResidualBlock(nn.Module):
         self._w_dproj = ops.ConvWeight((self, "diffusion_projection.weight"), C, C, 1)
         self._w_cond = ops.ConvWeight((self, "conditioner_projection.weight"), 2 * C, H, 1)
         self._w_out = ops.ConvWeight((self, "output_projection.weight"), 2 * C, C, 1)
-        self._fused = None
-        self._fused_key = None
+        self._fused = ops.CacheSlot()
 
     def fused_weights(self):
         wd, wo = self.dilated_conv.weight, self.output_projection.weight
-        key = (wd.data_ptr(), wd._version, wo.data_ptr(), wo._version, ops.weights_epoch())
-        if self._fused is None or key != self._fused_key:
-            self._fused = ops.pack_diffnet_layer(wd, wo)
-            self._fused_key = key
-        return self._fused
+        return self._fused.get(ops.weights_key((wd, wo)), lambda _: ops.pack_diffnet_layer(wd, wo))
 
 
 class DiffNet(nn.Module):
@@ -74,7 +69,9 @@ class DiffNet(nn.Module):
         self._w_skip = ops.ConvWeight((self, "skip_projection.weight"), C, C, 1)
         self._w_outp = ops.ConvWeight((self, "output_projection.weight"), in_dims, C, 1)
         self.impl = "auto"  # auto | fused | unfused  (unfused = generic kernels; device-side cross-check)
-        self._packs, self._packs_key = None, None
+        # weight-derived device data, rebuilt when a tensor it is computed from changes (ops.weights_key)
+        self._packs, self._packs_extra, self._img16, self._dtab, self._cond_all = (ops.CacheSlot() for _ in range(5))
+        self._img16_strides = ops.CacheSlot()  # the layers' strides, a property of where the tensors live: keyed by their addresses
 
     # ---- helpers -------------------------------------------------------------------------------------
     def can_fuse(self):
@@ -93,12 +90,12 @@ class DiffNet(nn.Module):
         inference=False (the training forward, whose weights change every step): only what the Winograd training kernel
         reads -- the last three are None (no extra 40 MB permutation and no per-layer scale read-backs per step)."""
         layers = list(self.residual_layers)
-        key = tuple((p.data_ptr(), p._version) for l in layers for p in
-                    (l.dilated_conv.weight, l.output_projection.weight, l.dilated_conv.bias, l.output_projection.bias))
-        key = key + (ops.weights_epoch(),)
+        key = ops.weights_key([p for l in layers for p in
+                               (l.dilated_conv.weight, l.output_projection.weight, l.dilated_conv.bias, l.output_projection.bias)])
         dev = layers[0].dilated_conv.weight.device
         L = len(layers)
-        if self._packs is None or key != self._packs_key:
+
+        def build(_):
             w1 = torch.empty(L, 512 * 768, dtype=torch.float32, device=dev)
             w2 = torch.empty(L, 512 * 256, dtype=torch.float32, device=dev)
             wino = self.dilation_cycle_length <= 4  # Winograd F(2,3) images for the persistent stack kernel (d <= 8)
@@ -118,56 +115,53 @@ class DiffNet(nn.Module):
                         ops.pack_diffnet_layer_wino(wds[i], wos[i], w1w[i], w2w[i])
             bd = torch.stack([l.dilated_conv.bias for l in layers]).contiguous()
             bo = torch.stack([l.output_projection.bias for l in layers]).contiguous()
-            self._packs, self._packs_key = (w1, w2, bd, bo, w1w, w2w), key
-            self._packs_extra_key = None
+            return w1, w2, bd, bo, w1w, w2w
+        packs = self._packs.get(key, build)
         if not inference:
-            return self._packs + (None, None, None)
-        ekey = key + (ops.split_operand_mode(),)
-        if getattr(self, "_packs_extra_key", None) != ekey:
-            w1s, w2s = ops.split_images(self._packs[0], self._packs[1])  # small-batch (row-split) stack kernel
+            return packs + (None, None, None)
+
+        def build_extra(_):
+            w1s, w2s = ops.split_images(packs[0], packs[1])  # small-batch (row-split) stack kernel
             wx3 = None
             if self.dilation_cycle_length <= 4:  # split-operand images of the throughput kernel (csrc/diffnet_x3.hip)
                 wx3 = ops.SplitOperandImages(L, ops.split_operand_mode(), dev)
                 for i, l in enumerate(layers):
                     wx3.pack(i, l.dilated_conv.weight.detach(), l.output_projection.weight.detach())
-            self._packs_extra, self._packs_extra_key = (w1s, w2s, wx3), ekey
-        return self._packs + self._packs_extra
+            return w1s, w2s, wx3
+        return packs + self._packs_extra.get((key, ops.split_operand_mode()), build_extra)
 
-    def bf16_layer_images(self):
-        """Per-layer packed bf16 weight images of the fused training kernels (forward GEMM 1 / 2 and the three transposed
-        images of the backward), re-rounded from the fp32 master weights whenever they change."""
-        layers = list(self.residual_layers)
-        # the 60 weight tensors as a flat list, looked up once (module attribute chains cost ~1 us each: this key is computed every step)
-        ps = getattr(self, "_img16_params", None)
-        if ps is None or len(ps) != 3 * len(layers) or ps[0] is not layers[0].dilated_conv.weight or ps[-1] is not layers[-1].output_projection.weight:
-            ps = self._img16_params = [p for l in layers for p in (l.dilated_conv.weight, l.conditioner_projection.weight, l.output_projection.weight)]
-            self._img16_strides = None
-        key = tuple((p.data_ptr(), p._version) for p in ps)
-        key = key + (ops.weights_epoch(),)
-        if getattr(self, "_img16", None) is None or self._img16_key != key:
+    def stack_params(self):
+        """Every residual layer's conditioner projection, dilated conv and output projection, weight then bias: the parameters of the
+        training stacks (autograd_ops.diffnet_stack_train / _bf16)."""
+        return [p for l in self.residual_layers for p in (l.conditioner_projection.weight, l.conditioner_projection.bias, l.dilated_conv.weight,
+                                                          l.dilated_conv.bias, l.output_projection.weight, l.output_projection.bias)]
+
+    def bf16_layer_images(self, params=None):
+        """Per-layer packed bf16 weight images of the fused training kernels (forward GEMM 1 / 2 and the three transposed images of the
+        backward) and every layer's (image, b_dil, b_cond, b_out, dilation) as integers for the launch loops.  Rebuilt from the fp32 master
+        weights whenever any of `params` changes: stack_params(), which the training step has resolved already."""
+        ps = self.stack_params() if params is None else params
+        key = ops.weights_key(ps)
+
+        def build(_):
             from . import _lib
-            n = _lib.lib().set_diffnet_layer_bf16_image_size()
-            dev = layers[0].dilated_conv.weight.device
-            img = torch.empty(len(layers), n, dtype=torch.bfloat16, device=dev)
             from .autograd_ops import _uniform_stride
-            # the layers' strides are a property of where the tensors live: recomputed when any address changes
-            addr = tuple(k[0] for k in key[:-1])
-            if self._img16_strides is None or self._img16_strides[0] != addr:
-                self._img16_strides = (addr, [_uniform_stride([p.detach() for p in ps[j::3]]) for j in range(3)])
-            strides = self._img16_strides[1]
+            layers = list(self.residual_layers)
+            L = len(layers)
+            img = torch.empty(L, _lib.lib().set_diffnet_layer_bf16_image_size(), dtype=torch.bfloat16, device=ps[0].device)
+            wd, wc, wo = ps[2::6], ps[0::6], ps[4::6]
+            strides = self._img16_strides.get(tuple(a for a, _ in key[-1]), lambda _: [_uniform_stride(ws) for ws in (wd, wc, wo)])
             if all(st is not None for st in strides):  # (the flat optimizer's layout: every layer's tensors at one stride) one launch
-                l0 = layers[0]
-                _lib.check(_lib.lib().set_pack_diffnet_layers_bf16(
-                    ops._p(l0.dilated_conv.weight.detach()), ops._p(l0.conditioner_projection.weight.detach()),
-                    ops._p(l0.output_projection.weight.detach()), strides[0], strides[1], strides[2], ops._p(img), len(layers),
-                    ops._stream()), "set_pack_diffnet_layers_bf16")
+                _lib.check(_lib.lib().set_pack_diffnet_layers_bf16(ops._p(wd[0]), ops._p(wc[0]), ops._p(wo[0]), strides[0], strides[1],
+                                                                   strides[2], ops._p(img), L, ops._stream()), "set_pack_diffnet_layers_bf16")
             else:
-                for i, l in enumerate(layers):
-                    _lib.check(_lib.lib().set_pack_diffnet_layer_bf16(
-                        ops._p(l.dilated_conv.weight.detach()), ops._p(l.conditioner_projection.weight.detach()),
-                        ops._p(l.output_projection.weight.detach()), ops._p(img[i]), ops._stream()), "set_pack_diffnet_layer_bf16")
-            self._img16, self._img16_key = img, key
-        return self._img16
+                for i in range(L):
+                    _lib.check(_lib.lib().set_pack_diffnet_layer_bf16(ops._p(wd[i]), ops._p(wc[i]), ops._p(wo[i]), ops._p(img[i]),
+                                                                      ops._stream()), "set_pack_diffnet_layer_bf16")
+            row = img.stride(0) * img.element_size()
+            return img, [(img.data_ptr() + i * row, ps[6 * i + 3].data_ptr(), ps[6 * i + 1].data_ptr(), ps[6 * i + 5].data_ptr(),
+                          int(ly.dilation)) for i, ly in enumerate(layers)]
+        return self._img16.get(key, build)
 
     def step_table(self, t_values):
         """d[l][c][n] = diffusion_projection_l(mlp(sinusoid(t_n)))[c]  ->  tensor [L*C, n]
@@ -186,15 +180,22 @@ class DiffNet(nn.Module):
     def step_table_all(self, steps, dev):
         """step_table(arange(steps)) for the reverse loop, kept across loops for as long as the tensors it is computed from are unchanged: it
         depends on the step MLP and the layers' diffusion projections only (22 launches of work on 100 columns -- 0.8 ms of a 150 ms loop at
-        B = 32, T = 800).  Keyed by storage, version counter and the optimizer's weights epoch of every one of those tensors."""
+        B = 32, T = 800).  Computed with fp32 operands whatever the compute dtype, so the fp32 and the bf16 loop share it and it depends on
+        those 44 tensors and the forced conv impl alone; recomputed on every call while grad is enabled."""
         ps = [self.mlp[0].weight, self.mlp[0].bias, self.mlp[2].weight, self.mlp[2].bias]
         for layer in self.residual_layers:
             ps += [layer.diffusion_projection.weight, layer.diffusion_projection.bias]
-        key = (int(steps), str(dev), ops.weights_epoch(), torch.is_grad_enabled()) + tuple((p.data_ptr(), p._version) for p in ps)
-        if getattr(self, "_dtab_key", None) != key or torch.is_grad_enabled():
-            self._dtab = self.step_table(torch.arange(int(steps), device=dev).to(torch.float32))
-            self._dtab_key = key
-        return self._dtab
+
+        def build(_):
+            prev = ops.compute_dtype()
+            ops.set_compute_dtype("f32")
+            try:
+                return self.step_table(torch.arange(int(steps), device=dev).to(torch.float32))
+            finally:
+                ops.set_compute_dtype(prev)
+        if torch.is_grad_enabled():
+            return build(None)
+        return self._dtab.get(ops.weights_key(ps, int(steps), str(dev), ops._DEFAULT_IMPL), build)
 
     def cond_projections(self, cond):
         """conditioner_projection_l(cond) for every layer -> [B, L*2C, T].  It does not depend on the
@@ -205,15 +206,14 @@ class DiffNet(nn.Module):
         if not torch.is_grad_enabled():
             # one launch on the layers' weights stacked along the output channels (bit-identical to the per-layer launches: same kernel, same
             # k order per output; 1.17 against 1.4 - 1.55 ms at B = 32, T = 800, profiles/r06_condproj_probe.log); the stacked copy follows the
-            # layers' tensors by storage, version counter and the optimizer's weights epoch
+            # layers' tensors (ops.weights_key)
             ps = [t for layer in self.residual_layers for t in (layer.conditioner_projection.weight, layer.conditioner_projection.bias)]
-            key = (str(cond.device), ops.weights_epoch()) + tuple((p.data_ptr(), p._version) for p in ps)
-            if getattr(self, "_wc_all_key", None) != key:
-                self._wc_all = torch.cat([p.detach() for p in ps[0::2]], 0).contiguous()
-                self._bc_all = torch.cat([p.detach() for p in ps[1::2]], 0).contiguous()
-                self._wc_all_cw = ops.ConvWeight((self, "_wc_all"), L * 2 * C, H, 1)
-                self._wc_all_key = key
-            ops.conv1d(cond, self._wc_all_cw, self._bc_all, out=out)
+
+            def build(_):
+                w_all = torch.cat([p.detach() for p in ps[0::2]], 0).contiguous()
+                return ops.ConvWeight(w_all, L * 2 * C, H, 1), torch.cat([p.detach() for p in ps[1::2]], 0).contiguous()
+            cw, b_all = self._cond_all.get(ops.weights_key(ps, str(cond.device)), build)
+            ops.conv1d(cond, cw, b_all, out=out)
             return out
         for l, layer in enumerate(self.residual_layers):
             ops.conv1d(cond, layer._w_cond, layer.conditioner_projection.bias,

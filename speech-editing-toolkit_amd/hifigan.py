@@ -34,23 +34,23 @@ class _WNConv:
 
     def __init__(self, mod, transposed=False, stride=1):
         self.mod, self.transposed, self.stride = mod, transposed, stride
-        self._w, self._key = None, None
+        self._fold = ops.CacheSlot()
         self._cw = None
         self._phases = {}
 
     def folded(self):
-        g, v = self.mod.weight_g.data, self.mod.weight_v.data
-        key = (g.data_ptr(), g._version, v.data_ptr(), v._version)
-        if self._w is None or key != self._key:
-            self._w, self._key = ops.weight_norm_fold(g.contiguous(), v.contiguous()), key
-            self._cw, self._phases = None, {}
-        return self._w
+        g, v = self.mod.weight_g, self.mod.weight_v
+        return self._fold.get(ops.weights_key((g, v)), lambda _: self._refold(g, v))
+
+    def _refold(self, g, v):
+        self._cw, self._phases = None, {}  # images of the previous fold: a new tensor may reuse its address
+        return ops.weight_norm_fold(g.contiguous(), v.contiguous())
 
     def conv_weight(self):
         w = self.folded()
         if self._cw is None:
             cout, cin, k = w.shape
-            self._cw = ops.ConvWeight((self, "_w"), cout, cin, k)
+            self._cw = ops.ConvWeight((self._fold, "value"), cout, cin, k)
         return self._cw
 
 
@@ -157,7 +157,7 @@ class HifiGanGenerator(nn.Module):
             cin, cout, k, u, P = self._up_cfg[i]
             up = self._ups[i]
             up.folded()
-            x = ops.conv_transpose1d(x, (up, "_w"), self.ups[i].bias.data, cin, cout, k, u, P,
+            x = ops.conv_transpose1d(x, (up._fold, "value"), self.ups[i].bias.data, cin, cout, k, u, P,
                                      pro="lrelu", pro_param=LRELU_SLOPE, cache=up._phases)
             # MRF (hifigan.py:131-137): xs = rb_0(x); xs += rb_j(x) ...; x = xs / num_kernels.  The running sum lives in
             # the epilogue of each ResBlock's final conv (first block stores, the others accumulate, the last one also

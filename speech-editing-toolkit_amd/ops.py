@@ -42,8 +42,31 @@ def bump_weights_epoch():
     _WEIGHTS_EPOCH += 1
 
 
-def weights_epoch():
-    return _WEIGHTS_EPOCH
+def weights_key(tensors, *extra):
+    """The key of everything cached from `tensors`: storage address and version counter of each tensor object (an in-place op, a
+    load_state_dict copy or a new parameter object changes it; a `.data` view would carry a fresh counter), their device, the optimizer's
+    weights epoch (its in-place kernels move no version counter) and the caller's `extra` settings.  A hit costs this one tuple and one
+    compare: the bf16 training step looks up 100 - 170 weight images with it."""
+    return (_WEIGHTS_EPOCH, tensors[0].device, extra, tuple([(t.data_ptr(), t._version) for t in tensors]))
+
+
+class CacheSlot:
+    """One cached value and the key it was built for.  `get(key, build)` returns the value while the key is unchanged, else stores
+    `build(old_value)` (None at first; an image re-packed into the old storage reuses it).  `mark(key)`: the value was brought up to
+    date for `key` elsewhere (the optimizer's one-launch re-packs)."""
+    __slots__ = ("key", "value")
+
+    def __init__(self):
+        self.key = self.value = None
+
+    def get(self, key, build):
+        if key != self.key:
+            self.value = build(self.value)
+            self.key = key
+        return self.value
+
+    def mark(self, key):
+        self.key = key
 
 
 import weakref  # noqa: E402
@@ -57,19 +80,19 @@ def repack_bf16_images():
     present weights epoch.  Called by the optimizer right after its step: the lazy per-weight check in `packed_bf16()` then
     finds nothing to do, instead of launching 100 - 170 tiny pack kernels (and allocating as many tensors) per training step.
     The descriptor table lives on the device and is rebuilt only when the set of images or their storage changes."""
-    cws = [cw for cw in _BF16_IMAGES if cw._packed16 is not None]
+    cws = [cw for cw in _BF16_IMAGES if cw._img16.value is not None]
     if not cws:
         return 0
     ws = [cw.raw() for cw in cws]
     dev = ws[0].device
-    keep = [i for i, w in enumerate(ws) if w.device == dev and cws[i]._packed16[1].device == dev]
+    keep = [i for i, w in enumerate(ws) if w.device == dev and cws[i]._img16.value.device == dev]
     cws, ws = [cws[i] for i in keep], [ws[i] for i in keep]
-    sig = tuple((id(cw), w.data_ptr(), cw._packed16[1].data_ptr()) for cw, w in zip(cws, ws))
+    sig = tuple((id(cw), w.data_ptr(), cw._img16.value.data_ptr()) for cw, w in zip(cws, ws))
     if _BF16_BATCH[0] != sig:
         arr = (_lib.SetPackBf16Desc * len(cws))()
         start = 0
         for d, cw, w in zip(arr, cws, ws):
-            wp = cw._packed16[1]
+            wp = cw._img16.value
             d.w, d.wp = w.data_ptr(), wp.data_ptr()
             d.w_base, d.w_sco, d.w_sci, d.w_stap, d.start = cw.base, cw.sco, cw.sci, cw.stap, start
             d.Cout, d.Cin, d.K = cw.Cout, cw.Cin, cw.K
@@ -81,7 +104,7 @@ def repack_bf16_images():
     check(_lib.lib().set_pack_conv_weights_bf16_batch(C.c_void_p(_BF16_BATCH[1].data_ptr()), len(cws), _BF16_BATCH[2], _stream()),
           "set_pack_conv_weights_bf16_batch")
     for cw, w in zip(cws, ws):
-        cw._packed16 = ((w.data_ptr(), w._version, w.device, _WEIGHTS_EPOCH), cw._packed16[1])
+        cw._img16.mark(weights_key((w,)))
     return len(cws)
 
 
@@ -95,14 +118,14 @@ def repack_f32_images():
     `packed_v2()` then finds nothing to do instead of launching ~150 pack kernels of ~5 us per fp32 training step (1.1 ms of the
     compute stream's 32 ms at B = 32, T = 800).  An image that was not used stays stale and is re-packed when it is next asked for.
     Same kernel arithmetic (a copy into the image layout): same bits."""
-    items = []
+    items = []  # (ConvWeight, kind: 0 = plain / 1 = big-tile, slot, image, dil, CacheSlot)
     for cw in _F32_IMAGES:
-        if cw._used32 and cw._packed is not None:
-            items.append((cw, 0, None, cw._packed, 0))
+        if cw._used32 and cw._img32.value is not None:
+            items.append((cw, 0, None, cw._img32.value, 0, cw._img32))
         for slot in cw._used2:
-            ent = cw._packed2.get(slot)
+            ent = cw._img2.get(slot)
             if ent is not None:
-                items.append((cw, 1, slot, ent[1], ent[2]))
+                items.append((cw, 1, slot, *ent.value, ent))
         cw._used32 = False
         cw._used2 = set()
     if not items:
@@ -122,7 +145,7 @@ def repack_f32_images():
     else:
         arr = (_lib.SetPackF32Desc * len(items))()
         start = 0
-        for d, (cw, kind, slot, wp, dil), w in zip(arr, items, ws):
+        for d, (cw, kind, slot, wp, dil, _), w in zip(arr, items, ws):
             d.w, d.wp = w.data_ptr(), wp.data_ptr()
             d.w_base, d.w_sco, d.w_sci, d.w_stap, d.start = cw.base, cw.sco, cw.sci, cw.stap, start
             d.Cout, d.Cin, d.K = cw.Cout, cw.Cin, cw.K
@@ -137,12 +160,8 @@ def repack_f32_images():
             _F32_TABLES.popitem(last=False)
     check(_lib.lib().set_pack_conv_weights_f32_batch(C.c_void_p(ent[0].data_ptr()), len(items), ent[1], _stream()),
           "set_pack_conv_weights_f32_batch")
-    for (cw, kind, slot, wp, dil), w in zip(items, ws):
-        key = (w.data_ptr(), w._version, w.device, _WEIGHTS_EPOCH)
-        if kind == 0:
-            cw._key = key
-        else:
-            cw._packed2[slot] = (key, wp, dil)
+    for it, w in zip(items, ws):
+        it[5].mark(weights_key((w,)))
     return len(items)
 
 
@@ -223,10 +242,8 @@ class ConvWeight:
         self.sco = int(sco if sco is not None else Cin * K)
         self.sci = int(sci if sci is not None else K)
         self.stap = int(stap)
-        self._packed = None
-        self._key = None
-        self._packed2 = {}
-        self._packed16 = None
+        self._img32, self._img16, self._img_x2 = CacheSlot(), CacheSlot(), CacheSlot()
+        self._img2 = {}  # big-tile images by LDS slot width: CacheSlot of (image, dil)
         self._used32, self._used2 = False, set()  # fp32 images asked for since the last repack_f32_images()
 
     def _resolve(self):
@@ -263,75 +280,48 @@ class ConvWeight:
                                   stap=1)
         return self._tr
 
+    def _pack(self, w, wp, name, dtype, registry=None, mid=(), tail=()):
+        """`set_pack_<name>` of the weight `w` into `wp` (None, or on another device: a new image).  An image re-packed in place is safe
+        for the launches that read it before: they are earlier in stream order."""
+        L = _lib.lib()
+        if wp is None or wp.device != w.device:
+            wp = torch.empty(getattr(L, "set_packed_%s_size" % name)(self.Cout, self.Cin, self.K), dtype=dtype, device=w.device)
+        check(getattr(L, "set_pack_" + name)(_p(w), _p(wp), self.Cout, self.Cin, self.K, *mid, self.base, self.sco, self.sci, self.stap,
+                                             *tail, _stream()), "set_pack_" + name)
+        if registry is not None:
+            registry.add(self)  # from now on the optimizer re-packs it in one launch with the others (repack_f32 / bf16_images)
+        return wp
+
     def packed(self):
         w = self.raw()
-        key = (w.data_ptr(), w._version, w.device, _WEIGHTS_EPOCH)
-        if self._packed is None or self._key != key:
-            if self._packed is not None and self._packed.device == w.device:
-                wp = self._packed
-            else:
-                n = _lib.lib().set_packed_conv_weight_size(self.Cout, self.Cin, self.K)
-                wp = torch.empty(n, dtype=torch.float32, device=w.device)
-            check(_lib.lib().set_pack_conv_weight(_p(w), _p(wp), self.Cout, self.Cin, self.K, self.base, self.sco,
-                                                  self.sci, self.stap, _stream()), "set_pack_conv_weight")
-            self._packed, self._key = wp, key
-            _F32_IMAGES.add(self)  # from now on the optimizer re-packs it with the others it used (repack_f32_images)
         self._used32 = True
-        return self._packed
-
+        return self._img32.get(weights_key((w,)), lambda wp: self._pack(w, wp, "conv_weight", torch.float32, _F32_IMAGES))
 
     def packed_bf16(self):
         """bf16 image for SET_IMPL_BF16 (re-rounded from the fp32 master weights whenever they change)."""
         w = self.raw()
-        key = (w.data_ptr(), w._version, w.device, _WEIGHTS_EPOCH)
-        if self._packed16 is None or self._packed16[0] != key:
-            if self._packed16 is not None and self._packed16[1].device == w.device:
-                wp = self._packed16[1]  # re-rounded in place once per optimizer step (stream order keeps earlier readers safe)
-            else:
-                n = _lib.lib().set_packed_conv_weight_bf16_size(self.Cout, self.Cin, self.K)
-                wp = torch.empty(n, dtype=torch.bfloat16, device=w.device)
-            check(_lib.lib().set_pack_conv_weight_bf16(_p(w), _p(wp), self.Cout, self.Cin, self.K, self.base, self.sco,
-                                                       self.sci, self.stap, _stream()), "set_pack_conv_weight_bf16")
-            self._packed16 = (key, wp)
-            _BF16_IMAGES.add(self)  # from now on the optimizer re-rounds it with all the others (repack_bf16_images)
-        return self._packed16[1]
+        return self._img16.get(weights_key((w,)), lambda wp: self._pack(w, wp, "conv_weight_bf16", torch.bfloat16, _BF16_IMAGES))
 
     def packed_x2(self):
-        """Two-piece fp16 image for SET_IMPL_F16X2 (re-split from the fp32 master weights whenever they change); the weights
-        are scaled by a power of two so that max |w| lands in [8, 16): one host read-back per weight version."""
+        """Two-piece fp16 image for SET_IMPL_F16X2 (re-split from the fp32 master weights whenever they change, into a new image)."""
         w = self.raw()
-        key = (w.data_ptr(), w._version, w.device, _WEIGHTS_EPOCH)
-        if getattr(self, "_packed_x2", None) is None or self._packed_x2[0] != key:
-            import math
-            n = _lib.lib().set_packed_conv_weight_x2_size(self.Cout, self.Cin, self.K)
-            wp = torch.empty(n, dtype=torch.float16, device=w.device)
-            m = float(w.abs().max())
-            k = max(-60, min(60, 4 - math.frexp(m)[1])) if m > 0 and math.isfinite(m) else 0
-            check(_lib.lib().set_pack_conv_weight_x2(_p(w), _p(wp), self.Cout, self.Cin, self.K, self.base, self.sco, self.sci,
-                                                     self.stap, k, _stream()), "set_pack_conv_weight_x2")
-            self._packed_x2 = (key, wp)
-        return self._packed_x2[1]
+        return self._img_x2.get(weights_key((w,)), lambda _: self._pack(w, None, "conv_weight_x2", torch.float16, tail=(_x2_exponent(w),)))
 
     def packed_v2(self, dil):
         """Image for the big-tile kernel (depends on |dil| through the LDS chunking)."""
         w = self.raw()
-        key = (w.data_ptr(), w._version, w.device, _WEIGHTS_EPOCH)
         halo = (self.K - 1) * abs(dil)
         slot = 128 if (64 + halo) * 256 * 4 > 96 * 1024 else 256
-        ent = self._packed2.get(slot)
-        if ent is None or ent[0] != key:
-            if ent is not None and ent[1].device == w.device:
-                wp = ent[1]  # re-packed in place (stream order keeps earlier readers safe)
-            else:
-                n = _lib.lib().set_packed_conv_weight_v2_size(self.Cout, self.Cin, self.K)
-                wp = torch.empty(n, dtype=torch.float32, device=w.device)
-            check(_lib.lib().set_pack_conv_weight_v2(_p(w), _p(wp), self.Cout, self.Cin, self.K, int(dil), self.base,
-                                                     self.sco, self.sci, self.stap, _stream()), "set_pack_conv_weight_v2")
-            ent = (key, wp, int(dil))
-            self._packed2[slot] = ent
-            _F32_IMAGES.add(self)
+        wp, _ = self._img2.setdefault(slot, CacheSlot()).get(weights_key((w,)), lambda old: (
+            self._pack(w, old and old[0], "conv_weight_v2", torch.float32, _F32_IMAGES, mid=(int(dil),)), int(dil)))
         self._used2.add(slot)
-        return ent[1]
+        return wp
+
+
+def _x2_exponent(w):
+    """Power-of-two scale of a two-piece fp16 image: max |w| lands in [8, 16) (one host read-back per weight version)."""
+    m = float(w.abs().max())
+    return max(-60, min(60, 4 - math.frexp(m)[1])) if m > 0 and math.isfinite(m) else 0
 
 
 def f16x2_eligible(T_iter, Cout, Cin, K, dil):
@@ -496,17 +486,15 @@ def conv_transpose1d(x, w_getter, bias, Cin, Cout, k, stride, padding, *, pro="n
     if impl is None and _AUTO_SPLIT[0] and Cin >= 32 and u * Cout >= 32 and T_in >= 64 and k >= u:
         # split-operand scope: every phase in one launch on the two-piece fp16 kernel (contiguous 16-byte stores)
         w = _f(ConvWeight(w_getter, Cout, Cin, k)._resolve(), "weight")
-        key = (w.data_ptr(), w._version, w.device, _WEIGHTS_EPOCH)
-        ent = phases.get("x2")
-        if ent is None or ent[0] != key:
-            import math
+
+        def pack(_):
             wp = torch.empty(_lib.lib().set_packed_conv_transpose_x2_size(Cout, Cin, k, u), dtype=torch.float16, device=w.device)
-            m = float(w.abs().max())
-            ke = max(-60, min(60, 4 - math.frexp(m)[1])) if m > 0 and math.isfinite(m) else 0
-            check(_lib.lib().set_pack_conv_transpose_x2(_p(w), _p(wp), Cout, Cin, k, u, ke, _stream()), "set_pack_conv_transpose_x2")
-            ent = phases["x2"] = (key, wp)
+            check(_lib.lib().set_pack_conv_transpose_x2(_p(w), _p(wp), Cout, Cin, k, u, _x2_exponent(w), _stream()),
+                  "set_pack_conv_transpose_x2")
+            return wp
+        wp = phases.setdefault("x2", CacheSlot()).get(weights_key((w,)), pack)
         _f(x, "x")
-        check(_lib.lib().set_conv_transpose1d_x2(_p(x), _p(ent[1]), _p(bias) if bias is not None else None, _p(out), B, Cin, Cout, k,
+        check(_lib.lib().set_conv_transpose1d_x2(_p(x), _p(wp), _p(bias) if bias is not None else None, _p(out), B, Cin, Cout, k,
                                                  u, P, T_in, PRO[pro], float(pro_param), _stream()), "set_conv_transpose1d_x2")
         return out
     for p in range(u):

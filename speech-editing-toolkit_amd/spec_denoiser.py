@@ -175,7 +175,7 @@ class GaussianDiffusion(nn.Module):
         # opt-in bf16-operand loop (ops.set_compute_dtype("bf16")): NOT the parity path -- see DESIGN.md section 3.5
         bf16 = None
         if ops.compute_dtype() == "bf16" and dn.use_fused() and dn.encoder_hidden == 192 and T >= 32:
-            bf16 = dict(cond=cond.contiguous(), imgs=dn.bf16_layer_images(),
+            bf16 = dict(cond=cond.contiguous(), imgs=dn.bf16_layer_images()[0],
                         b_cond=torch.stack([l.conditioner_projection.bias for l in dn.residual_layers]).contiguous())
         condproj = dn.cond_projections(cond) if bf16 is None else None  # hoisted: independent of the step
         if dn.use_fused():

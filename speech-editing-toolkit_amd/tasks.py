@@ -49,6 +49,7 @@ class SpeechEditingBaseTask:
         else:
             self.token_encoder = list(range(int(hparams.get("dict_size", 80))))
             self.sil_ids = [int(i) for i in hparams.get("sil_token_ids", [1, 2, 3])]
+        self._sil_lut = ops.CacheSlot()  # is_sil by token id (word_ids)
         self.vocoder = None
         if build_vocoder and os.path.exists(os.path.join(hparams.get("vocoder_ckpt", "") or "", "config.yaml")):
             self.vocoder = get_vocoder_cls(hparams["vocoder"])()
@@ -233,14 +234,13 @@ class SpeechDenoiserTask(SpeechEditingBaseTask):
         non-alphabetic tokens incl. the reserved ones (`self.sil_ids`, see __init__)."""
         # is_sil through a lookup table over the token ids (one gather instead of a compare + or per silence id: 11 -> 4 launches per step;
         # token ids are < len(token_encoder), the size of the embedding table they index)
-        lut, key = getattr(self, "_sil_lut", None), (txt_tokens.device, tuple(int(i) for i in self.sil_ids))
-        if lut is None or self._sil_lut_key != key:
-            self._sil_lut_key = key
-            n_tok = max(len(self.token_encoder), max([int(i) for i in self.sil_ids], default=0) + 1)
-            lut = torch.zeros(n_tok, dtype=torch.int64)
-            lut[[int(i) for i in self.sil_ids]] = 1
-            lut = self._sil_lut = lut.to(txt_tokens.device)
-        sil = lut[txt_tokens]
+        sil_ids = [int(i) for i in self.sil_ids]
+
+        def build(_):
+            lut = torch.zeros(max(len(self.token_encoder), max(sil_ids, default=0) + 1), dtype=torch.int64)
+            lut[sil_ids] = 1
+            return lut.to(txt_tokens.device)
+        sil = self._sil_lut.get((txt_tokens.device, tuple(sil_ids), len(self.token_encoder)), build)[txt_tokens]
         word_id = (sil.cumsum(-1) * (1 - sil)).contiguous()
         # number of word slots: the reference sizes its scatter target with word_id.max() + 1, a device->host read in the
         # middle of every step; T_txt is an upper bound (a word has at least one token) and the empty slots have zero

@@ -282,6 +282,61 @@ def test_phone_set_json_follows_the_reference_token_encoder(tmp_path):
         H.hparams.update(saved)
 
 
+def test_weights_key_follows_every_weight_change():
+    """ops.weights_key + ops.CacheSlot, the one key of every weight-derived cache: while nothing changed a lookup hits and returns the same
+    object; an in-place op, a load_state_dict, a `.data =` assignment, a new parameter object, an optimizer epoch bump and a changed extra
+    value each miss, and the build is handed the old value.  mark() makes a value current without a build."""
+    from set_amd import ops
+    conv = torch.nn.Conv1d(4, 4, 3)
+    slot, seen = ops.CacheSlot(), []
+
+    def get(extra=0):
+        return slot.get(ops.weights_key((conv.weight, conv.bias), extra), lambda old: seen.append(old) or object())
+    v = get()
+    assert get() is v and seen == [None]
+
+    def misses(change, extra=0):
+        nonlocal v
+        change()
+        old, v = v, get(extra)
+        assert v is not old and seen[-1] is old
+        assert get(extra) is v
+    def in_place():
+        with torch.no_grad():
+            conv.weight.add_(1.0)
+    misses(in_place)
+    misses(lambda: conv.load_state_dict(torch.nn.Conv1d(4, 4, 3).state_dict()))
+    misses(lambda: setattr(conv.weight, "data", torch.randn(4, 4, 3)))
+    misses(lambda: setattr(conv, "bias", torch.nn.Parameter(torch.randn(4))))
+    misses(ops.bump_weights_epoch)
+    misses(lambda: None, extra=1)
+    n = len(seen)
+    ops.bump_weights_epoch()
+    slot.mark(ops.weights_key((conv.weight, conv.bias), 1))
+    assert get(1) is v and len(seen) == n
+    # weight norm: the key reads the parameters' own version counters (`.data` carries a fresh one, unchanged by a load)
+    wn = torch.nn.utils.weight_norm(torch.nn.Conv1d(4, 4, 3))
+    k0 = ops.weights_key((wn.weight_g, wn.weight_v))
+    wn.load_state_dict(torch.nn.utils.weight_norm(torch.nn.Conv1d(4, 4, 3)).state_dict())
+    assert ops.weights_key((wn.weight_g, wn.weight_v)) != k0
+
+
+def test_word_ids_table_follows_the_token_set():
+    """The silence lookup table of SpeechEditingTask.word_ids is rebuilt when the token set grows (the same silence ids)."""
+    from set_amd import hparams as H, tasks
+    saved = dict(H.hparams)
+    try:
+        H.hparams.clear()
+        H.hparams.update(base_hparams(timesteps=4, dict_size=8, sil_token_ids=[1, 2]))
+        task = tasks.SpeechDenoiserTask(build_vocoder=False)
+        assert task.word_ids(torch.tensor([[3, 1, 4, 5, 2, 6]]))[0].tolist() == [[0, 0, 1, 1, 0, 2]]
+        task.token_encoder.extend(range(8, 12))
+        assert task.word_ids(torch.tensor([[9, 1, 10, 2, 11]]))[0].tolist() == [[0, 0, 1, 0, 2]]
+    finally:
+        H.hparams.clear()
+        H.hparams.update(saved)
+
+
 def test_conv_weights_follow_a_deepcopy_of_the_model():
     """a ConvWeight looks its tensor up on the owning module at every use, so copy.deepcopy(model) (EMA /
     teacher copies) computes with the COPY's parameters, and the model pickles."""

@@ -530,6 +530,40 @@ def test_fused_bf16_layers_match_emulation(dev, bf16, T, cycle):
         assert _rel(layer.output_projection.bias.grad, dbo) < 4e-3, l
 
 
+def test_bf16_stack_follows_a_replaced_middle_parameter(dev, bf16):
+    """The bf16 layer images and the per-layer addresses of _DiffNetStackBf16Fn follow every layer's parameters: after a step, replacing
+    a middle layer's output_projection.weight by a new nn.Parameter gives the forward and backward of a model built with it from the start."""
+    from set_amd import autograd_ops as A
+    from set_amd.diffnet import DiffNet
+    L, B, C, H, T = 4, 2, 256, 192, 96
+    hp = base_hparams(residual_layers=L, dilation_cycle_length=1)
+    torch.manual_seed(4)
+    dn = DiffNet(80, hp).to(dev)
+    g = torch.Generator().manual_seed(5)
+    hx, cond, gsk = torch.randn(B, C, T, generator=g), torch.randn(B, H, T, generator=g), torch.randn(B, C, T, generator=g)
+    dmat = torch.randn(B, L * C, generator=g) * 0.5
+
+    def step(net):
+        net.zero_grad(set_to_none=True)
+        ins = [t.clone().to(dev).requires_grad_(True) for t in (hx, cond, dmat)]
+        with torch.enable_grad():
+            skip = A.diffnet_stack_train_bf16(net, *ins)
+            skip.backward(gsk.to(dev))
+        torch.cuda.synchronize()
+        return [skip.detach()] + [t.grad for t in ins] + [p.grad for n, p in sorted(net.named_parameters())
+                                                          if n.startswith("residual_layers") and "diffusion_projection" not in n]
+    step(dn)
+    w = torch.randn(2 * C, C, 1, generator=g) * 0.05
+    dn.residual_layers[2].output_projection.weight = torch.nn.Parameter(w.to(dev))
+    got = step(dn)
+    fresh = DiffNet(80, hp).to(dev)
+    fresh.load_state_dict(dn.state_dict())
+    want = step(fresh)
+    assert len(got) == len(want) == 4 + 6 * L
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert torch.equal(a, b), i
+
+
 def test_bf16_inference_loop_tolerance(dev):
     """The opt-in bf16-operand reverse loop (fused bf16 layer kernel per residual layer, conditioner projection inside the
     layer GEMM) on the reference goldens: NOT the parity path (that one is fp32, |dmel| < 1e-4) -- its bar is the quality
@@ -624,7 +658,7 @@ def test_bf16_loop_utterance_groups_do_not_share_scratch(dev, monkeypatch):
         assert torch.equal(o, outs[0])
 
 
-def test_batch_repack_equals_per_weight_packs(dev):
+def test_batch_repack_equals_per_weight_packs_and_marks_the_images_current(dev):
     """ops.repack_bf16_images (what FlatAdamW.step calls in bf16 mode): every registered bf16 weight image re-rounded from its
     fp32 master weight in ONE launch -- bit-equal to the per-weight pack kernel, for plain, transposed (input-gradient) and
     offset / strided (a slice of a packed projection) weights; afterwards the lazy per-weight check finds the images current."""
@@ -647,7 +681,7 @@ def test_batch_repack_equals_per_weight_packs(dev):
     assert n >= len(cws)
     torch.cuda.synchronize()
     for cw, im, ptr in zip(cws, imgs, ptrs):
-        assert cw._packed16[0][3] == ops.weights_epoch() and cw._packed16[1].data_ptr() == ptr
+        assert cw._img16.key == ops.weights_key((cw.raw(),)) and cw._img16.value.data_ptr() == ptr
         fresh = torch.empty_like(im)
         _lib.check(_lib.lib().set_pack_conv_weight_bf16(C.c_void_p(cw.raw().data_ptr()), C.c_void_p(fresh.data_ptr()), cw.Cout, cw.Cin,
                                                         cw.K, cw.base, cw.sco, cw.sci, cw.stap, None), "pack")

@@ -1297,7 +1297,7 @@ def test_full800_single_utterance_matches_reference(dev, row):
     assert d < 1e-4
 
 
-def test_step_table_is_kept_across_loops_and_follows_the_weights(dev):
+def test_cached_step_table_and_conditioner_weights_follow_the_weights(dev):
     """Round 6: the reverse loop keeps its table of step offsets (DiffNet.step_table_all: a function of the step MLP and the layers' diffusion
     projections only) across calls.  A second loop reuses it (same object, same mel); an in-place change of ONE of the 44 tensors (version
     counter), a load_state_dict and an optimizer-style epoch bump each rebuild it, and the loop then equals a freshly built model's."""
@@ -1309,26 +1309,26 @@ def test_step_table_is_kept_across_loops_and_follows_the_weights(dev):
     args = (inp["txt_tokens"], inp["time_mel_masks"], inp["mel2ph"], inp["spk_embed"], inp["ref_mels"], inp["f0"], inp["uv"])
     a = model(*args, infer=True, noises=noises, **m["flags"])["mel_out"].clone()
     dn = model.denoise_fn
-    t0 = dn._dtab
+    t0 = dn._dtab.value
     b = model(*args, infer=True, noises=noises, **m["flags"])["mel_out"].clone()
-    assert dn._dtab is t0 and torch.equal(a, b)
+    assert dn._dtab.value is t0 and torch.equal(a, b)
     assert _maxdiff(a, g["mel_out"]) < 1e-4
     with torch.no_grad():
         dn.residual_layers[3].diffusion_projection.bias.add_(0.25)   # in place: version counter
     c = model(*args, infer=True, noises=noises, **m["flags"])["mel_out"].clone()
-    assert dn._dtab is not t0 and not torch.equal(a, c)
+    assert dn._dtab.value is not t0 and not torch.equal(a, c)
     fresh, _ = _build_model(dev, "spec_denoiser", m["wseed"], m["steps"], **m["overrides"])
     with torch.no_grad():
         fresh.denoise_fn.residual_layers[3].diffusion_projection.bias.add_(0.25)
     assert torch.equal(c, fresh(*args, infer=True, noises=noises, **m["flags"])["mel_out"])
-    t1 = dn._dtab
+    t1 = dn._dtab.value
     model.load_state_dict({k: v.to(dev) for k, v in W.items()}, strict=False)   # back to the golden's weights (copy_: version counters)
     d = model(*args, infer=True, noises=noises, **m["flags"])["mel_out"].clone()
-    assert dn._dtab is not t1 and torch.equal(d, a)
-    t2 = dn._dtab
+    assert dn._dtab.value is not t1 and torch.equal(d, a)
+    t2 = dn._dtab.value
     ops.bump_weights_epoch()                                                     # what FlatAdamW.step does after its in-place kernel
     e = model(*args, infer=True, noises=noises, **m["flags"])["mel_out"]
-    assert dn._dtab is not t2 and torch.equal(e, a)
+    assert dn._dtab.value is not t2 and torch.equal(e, a)
     # the stacked conditioner projection of the loop (DiffNet.cond_projections: one launch for all layers) follows its layers the same way and
     # equals the per-layer launches bit for bit
     cond = torch.randn(2, dn.encoder_hidden, 64, device=dev)
@@ -1336,13 +1336,50 @@ def test_step_table_is_kept_across_loops_and_follows_the_weights(dev):
     with torch.enable_grad():
         per_layer = dn.cond_projections(cond)
     assert torch.equal(one, per_layer)
-    w_all = dn._wc_all
+    w_all = dn._cond_all.value
     with torch.no_grad():
         dn.residual_layers[7].conditioner_projection.weight.mul_(1.5)
     two = dn.cond_projections(cond)
     with torch.enable_grad():
         per_layer = dn.cond_projections(cond)
-    assert dn._wc_all is not w_all and torch.equal(two, per_layer) and not torch.equal(one, two)
+    assert dn._cond_all.value is not w_all and torch.equal(two, per_layer) and not torch.equal(one, two)
+
+
+def test_fp32_loop_after_a_bf16_loop_equals_a_fresh_models(dev):
+    """The table of step offsets is computed with fp32 operands whichever loop asks for it first: a bf16-operand loop on a model leaves
+    no bf16-rounded table behind for a later fp32 (parity) loop on the same model.  40 steps: wide enough for the bf16 conv kernel."""
+    from set_amd import ops
+    over = dict(residual_layers=20, residual_channels=256, dilation_cycle_length=1)
+    model, _ = _build_model(dev, "spec_denoiser", 11, 40, **over)
+    inp = {k: v.to(dev) for k, v in Wt.synthetic_inputs(2, 64, 16, seed=101).items()}
+    args = (inp["txt_tokens"], inp["time_mel_masks"], inp["mel2ph"], inp["spk_embed"], inp["ref_mels"], inp["f0"], inp["uv"])
+    ops.set_compute_dtype("bf16")
+    try:
+        model(*args, infer=True, seed=5)
+    finally:
+        ops.set_compute_dtype("f32")
+    got = model(*args, infer=True, seed=5)["mel_out"]
+    fresh, _ = _build_model(dev, "spec_denoiser", 11, 40, **over)
+    assert torch.equal(got, fresh(*args, infer=True, seed=5)["mel_out"])
+
+
+def test_hifigan_fold_follows_a_weight_load(dev):
+    """The folded weight-norm weights follow load_state_dict (it copies into the same storage): after a forward on one set of weights and
+    a load of another, the generator equals a fresh one built with the second set, bit for bit."""
+    from set_amd.hifigan import HifiGanGenerator
+    man = Wt.load_manifest("hifigan_tiny")
+    mel = torch.randn(1, 80, 40, generator=torch.Generator().manual_seed(3)).to(dev)
+
+    def gen(seed):
+        g = HifiGanGenerator(Wt.HIFIGAN_TINY)
+        g.load_state_dict(Wt.seeded_weights(man, seed))
+        return g.to(dev).eval()
+    g = gen(21)
+    first = g(mel).clone()
+    g.load_state_dict(Wt.seeded_weights(man, 22))
+    second = g(mel)
+    assert not torch.equal(first, second)
+    assert torch.equal(second, gen(22)(mel))
 
 
 @pytest.mark.parametrize("form", ["2", "3"])

@@ -861,7 +861,7 @@ def test_gate_and_res_skip_backward_vector_and_scalar_forms(dev):
 
 
 @pytest.mark.parametrize("stack", ["per_op", "fused_stack"])
-def test_batched_fp32_image_repack_equals_the_per_image_packs(dev, monkeypatch, stack):
+def test_batched_fp32_image_repack_equals_the_per_image_packs_and_marks_them_current(dev, monkeypatch, stack):
     """ops.repack_f32_images / set_pack_conv_weights_f32_batch and set_pack_diffnet_layers (round 5): after an fp32 optimizer step every weight
     image the step used has been re-packed by ONE launch (two for the DiffNet stack).  Each must equal, bit for bit, the image the
     one-launch-per-weight entry points (set_pack_conv_weight, set_pack_conv_weight_v2, set_pack_diffnet_layer(_wino)) make of the
@@ -888,18 +888,19 @@ def test_batched_fp32_image_repack_equals_the_per_image_packs(dev, monkeypatch, 
         w = cw.raw()
         if w.device != dev:
             continue
-        key = (w.data_ptr(), w._version, w.device, ops.weights_epoch())
-        if cw._packed is not None and cw._key == key:  # current for this epoch without having been asked for: the batch launch did it
-            ref = torch.empty_like(cw._packed)
+        key = ops.weights_key((w,))
+        if cw._img32.value is not None and cw._img32.key == key:  # current for this epoch without having been asked for: the batch launch did it
+            ref = torch.empty_like(cw._img32.value)
             _lib.check(L.set_pack_conv_weight(_p(w), _p(ref), cw.Cout, cw.Cin, cw.K, cw.base, cw.sco, cw.sci, cw.stap, _stream()), "pack")
-            assert torch.equal(ref, cw._packed), (cw.Cout, cw.Cin, cw.K)
+            assert torch.equal(ref, cw._img32.value), (cw.Cout, cw.Cin, cw.K)
             n0 += 1
-        for slot, ent in cw._packed2.items():
-            if ent[0] == key:
-                ref = torch.empty_like(ent[1])
-                _lib.check(L.set_pack_conv_weight_v2(_p(w), _p(ref), cw.Cout, cw.Cin, cw.K, ent[2], cw.base, cw.sco, cw.sci, cw.stap,
+        for slot, ent in cw._img2.items():
+            if ent.key == key:
+                wp, dil = ent.value
+                ref = torch.empty_like(wp)
+                _lib.check(L.set_pack_conv_weight_v2(_p(w), _p(ref), cw.Cout, cw.Cin, cw.K, dil, cw.base, cw.sco, cw.sci, cw.stap,
                                                      _stream()), "pack v2")
-                assert torch.equal(ref, ent[1]), (cw.Cout, cw.Cin, cw.K, slot)
+                assert torch.equal(ref, wp), (cw.Cout, cw.Cin, cw.K, slot)
                 n2 += 1
     print("images current after the step: %d plain, %d big-tile" % (n0, n2))
     assert n0 >= 20

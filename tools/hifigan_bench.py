@@ -50,7 +50,7 @@ if os.environ.get("HSTAGES"):
         cin, cout, k, u, P = g._up_cfg[i]
         up = g._ups[i]
         up.folded()
-        ms, x = timed(lambda: ops.conv_transpose1d(x, lambda up=up: up._w, g.ups[i].bias.data, cin, cout, k, u, P,
+        ms, x = timed(lambda: ops.conv_transpose1d(x, lambda up=up: up._fold.value, g.ups[i].bias.data, cin, cout, k, u, P,
                                                     pro="lrelu", pro_param=0.1, cache=up._phases))
         Tn = x.shape[2]
         print("stage %d  up %4d->%4d k%-2d s%d  T=%6d : %7.2f ms  %6.1f TF/s" % (
