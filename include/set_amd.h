@@ -704,6 +704,25 @@ int set_expand_states_bwd(const int64_t *mel2ph, const float *dout, float *denc,
 /* inverted dropout with a Philox keep-mask keyed by (seed, offset + i/4): y = keep ? x/(1-p) : 0.  Calling it on the
  * output gradient with the same (seed, offset) is the backward (nar_tts_modules.py:20,86 predictor dropout). */
 int set_dropout(const float *x, float *y, int64_t n, float p, uint64_t seed, uint64_t offset, void *stream);
+/* dropout on the branch of a residual sub-block (modules/commons/conv.py:57-65): y = (x + keep z/(1-p)) * mask[b][t] on [B][C][T],
+ * keep = set_dropout's decision for the same (seed, offset, element index); mask may be NULL */
+int set_residual_dropout(const float *x, const float *z, const float *mask, float *y, int32_t B, int32_t C, int32_t T, float p,
+                         uint64_t seed, uint64_t offset, void *stream);
+/* its backward: g2 = dy * mask (the residual's gradient), gz = keep g2/(1-p) (the branch's) */
+int set_conv_epilogue_bwd_dropout(const float *dy, const float *mask, float *g2, float *gz, int32_t B, int32_t C, int32_t T, float p,
+                                  uint64_t seed, uint64_t offset, void *stream);
+/* StutterSpeech head + losses (csrc/stutter.hip): h [B][C][T] (post_net1 output), w [3][C], bias [3], labels int64 [B][T] in {0,1,2}
+ * (2 = pad).  Writes logits [B][T][3]; with labels, stats[3] = {ce (mean over label != 2), focal (mean over all B*T rows), n_valid}
+ * from per-block partials in scratch (set_stutter_head_scratch_floats), combined in block order.  labels NULL: logits only. */
+int64_t set_stutter_head_scratch_floats(int32_t B, int32_t C, int32_t T);
+int set_stutter_head_loss(const float *h, const float *w, const float *bias, const int64_t *labels, float *logits, float *stats,
+                          float *scratch, int32_t B, int32_t C, int32_t T, void *stream);
+/* backward from the saved logits and stats: g_ce / g_focal are device scalars (either may be NULL = 0); writes dh [B][C][T] and the
+ * per-(utterance, 256-frame chunk) weight / bias partials into scratch; dw / db non-NULL: also dw[3][C] += , db[3] += (set_stutter_head_bwd_reduce) */
+int set_stutter_head_loss_bwd(const float *h, const float *w, const float *logits, const int64_t *labels, const float *stats,
+                              const float *g_ce, const float *g_focal, float *dh, float *dw, float *db, float *scratch, int32_t B,
+                              int32_t C, int32_t T, void *stream);
+int set_stutter_head_bwd_reduce(const float *scratch, float *dw, float *db, int32_t B, int32_t C, int32_t T, void *stream);
 /* w[f] = (sum_m |target[f][m]|) != 0    (weights_nonzero_speech, utils/nn/seq_utils.py:33-37) */
 int set_frame_weight(const float *target, float *w, int64_t frames, int32_t M, void *stream);
 /* out[0] += sum_i x[i] * (w ? w[i/inner] : 1) */

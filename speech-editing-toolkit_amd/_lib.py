@@ -17,7 +17,7 @@ INCLUDE = os.path.join(_ROOT, "include")
 LIB_PATH = os.path.join(_PKG, "libset_amd.so")
 # measurement only (tools/build_exp.sh): load an experimental build of the library instead; never built or rebuilt from here
 _LIB_OVERRIDE = os.environ.get("SET_AMD_LIB")
-SOURCES = ["conv1d.hip", "conv_x2.hip", "resblock_x2.hip", "glue.hip", "diffnet.hip", "diffnet_x3.hip", "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip"]
+SOURCES = ["conv1d.hip", "conv_x2.hip", "resblock_x2.hip", "glue.hip", "diffnet.hip", "diffnet_x3.hip", "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 # constants mirrored from set_amd.h
@@ -321,6 +321,12 @@ SIGNATURES = {
     "set_embedding_bwd": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _I32, _F, _I32, _V]),
     "set_expand_states_bwd": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _I32, _V]),
     "set_dropout": (C.c_int, [_V, _V, _I64, _F, _U64, _U64, _V]),
+    "set_residual_dropout": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _F, _U64, _U64, _V]),
+    "set_conv_epilogue_bwd_dropout": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _F, _U64, _U64, _V]),
+    "set_stutter_head_scratch_floats": (_I64, [_I32, _I32, _I32]),
+    "set_stutter_head_loss": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _V]),
+    "set_stutter_head_loss_bwd": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _V]),
+    "set_stutter_head_bwd_reduce": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _V]),
     "set_frame_weight": (C.c_int, [_V, _V, _I64, _I32, _V]),
     "set_weighted_sum": (C.c_int, [_V, _V, _V, _I64, _I64, _V]),
     "set_l1_elem": (C.c_int, [_V, _V, _V, _V, _I64, _V]),

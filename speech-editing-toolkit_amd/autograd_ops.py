@@ -553,15 +553,18 @@ class _PreLnFfnFn(torch.autograd.Function):
     fan-out bookkeeping between them.  Gradients are bit-identical to the per-op tape's (tests: all-gradients goldens)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, w1, b1, w2, b2, cw1, cw2, dil, pad, alpha, act, act_param, eps, mask, t_out):
+    def forward(ctx, x, gamma, beta, w1, b1, w2, b2, cw1, cw2, dil, pad, alpha, act, act_param, eps, mask, t_out, drop=None):
         x = x.contiguous()
         h = ops.layernorm_ch(x, gamma, beta, None, eps)
         z = ops.conv1d(h, cw1, b1, dil=dil, pad=pad, alpha=alpha, T_out=t_out)
         f = torch.empty_like(z)
         check(L().set_act_fwd(_p(z), _p(f), z.numel(), ACT[act], float(act_param), _stream()), "set_act_fwd")
-        y = ops.conv1d(f, cw2, b2, res=x, mask=mask)
+        if drop is None:
+            y = ops.conv1d(f, cw2, b2, res=x, mask=mask)
+        else:  # the branch through inverted dropout, then + x, * mask (conv.py:57-65)
+            y = ops.residual_dropout(x, ops.conv1d(f, cw2, b2), mask, *drop)
         ctx.save_for_backward(x, gamma, mask, h, z, f)
-        ctx.cws, ctx.cfg = (cw1, cw2), (dil, pad, alpha, act, act_param, eps)
+        ctx.cws, ctx.cfg, ctx.drop = (cw1, cw2), (dil, pad, alpha, act, act_param, eps), drop
         ctx.params = (gamma, beta, w1, b1, w2, b2)
         return y
 
@@ -585,16 +588,22 @@ class _PreLnFfnFn(torch.autograd.Function):
             return tmp, tmp
 
         # ---- second conv (1x1, + residual, * mask): G2 = dy * mask is also the residual's gradient
-        if mask is None:
-            g2 = dy
+        if ctx.drop is not None:  # the branch's gradient is keep * G2 / (1 - p) (same Philox keys as the forward)
+            g2, gb = torch.empty_like(dy), torch.empty_like(dy)
+            p_, seed_, off_ = ctx.drop
+            check(L().set_conv_epilogue_bwd_dropout(_p(dy), _p(mask), _p(g2), _p(gb), B, Cc, T, float(p_), int(seed_), int(off_),
+                                                    _stream()), "set_conv_epilogue_bwd_dropout")
+        elif mask is None:
+            g2 = gb = dy
         else:
             g2 = torch.empty_like(dy)
             check(L().set_conv_epilogue_bwd(_p(dy), None, _p(mask), _p(g2), B, Cc, T, 0, 1.0, _stream()), "set_conv_epilogue_bwd")
-        df = ops.conv1d(g2, cw2.transposed(), None, dil=-1, pad=0, T_iter=T1, T_out=T1)
+            gb = g2
+        df = ops.conv1d(gb, cw2.transposed(), None, dil=-1, pad=0, T_iter=T1, T_out=T1)
         (t_w2, r_w2), (t_b2, r_b2) = tgt(p_w2, cw2), tgt(p_b2)
-        with leaf_work(dev, r_w2 is None and r_b2 is None, g2, f):  # (g2 may be dy itself: kept referenced, see _Conv1dFn.backward)
-            conv_wgrad(g2, f, None, t_w2, B, Cmid, Cc, 1, 1, 0, T, T1, dw_ptr=t_w2.data_ptr() + 4 * cw2.base)
-            channel_sum_(g2, t_b2, B, Cc, T)
+        with leaf_work(dev, r_w2 is None and r_b2 is None, gb, f):  # (gb may be dy itself: kept referenced, see _Conv1dFn.backward)
+            conv_wgrad(gb, f, None, t_w2, B, Cmid, Cc, 1, 1, 0, T, T1, dw_ptr=t_w2.data_ptr() + 4 * cw2.base)
+            channel_sum_(gb, t_b2, B, Cc, T)
         # ---- activation backward with the first conv's alpha folded in: G1 = gradient of the raw conv + bias
         g1 = torch.empty_like(z)
         check(L().set_act_bwd_scaled(_p(z), _p(df), _p(g1), z.numel(), ACT[act], float(act_param), float(alpha), _stream()), "set_act_bwd_scaled")
@@ -609,18 +618,86 @@ class _PreLnFfnFn(torch.autograd.Function):
         part = _det_scratch(dev, L().set_layernorm_ch_bwd_scratch(B, Cc, T_in))
         check(L().set_layernorm_ch_bwd_add(_p(x), _p(gamma), None, _p(dh), _p(g2), _p(dxl), _p(t_g), _p(t_bt), _p(part), B, Cc, T_in, float(eps),
                                            _stream()), "set_layernorm_ch_bwd_add")  # dx = LN gradient + residual gradient, one launch
-        return (dxl, r_g, r_bt, r_w1, r_b1, r_w2, r_b2) + (None,) * 10
+        return (dxl, r_g, r_bt, r_w1, r_b1, r_w2, r_b2) + (None,) * 11
 
 
-def preln_ffn(x, ln, cw1, b1, cw2, b2, *, dil=1, pad=0, alpha=1.0, act="gelu", act_param=0.0, mask=None, eps=1e-5, T_out=None):
+def preln_ffn(x, ln, cw1, b1, cw2, b2, *, dil=1, pad=0, alpha=1.0, act="gelu", act_param=0.0, mask=None, eps=1e-5, T_out=None,
+              drop=None):
     """(x + conv1x1(act(alpha conv_k(LN(x))))) (* mask) as one tape node; ln = (gamma, beta).  SET_AMD_FUSED_NODES=0: the per-op tape
-    (fan-out, LayerNorm, conv, activation, conv: five nodes) -- the cross-check of tests/test_gpu_training.py and the A/B of the bench."""
+    (fan-out, LayerNorm, conv, activation, conv: five nodes) -- the cross-check of tests/test_gpu_training.py and the A/B of the bench.
+    drop=(p, seed, offset): inverted dropout on the branch before the residual add, keep-mask of set_dropout keyed by (seed, offset,
+    element index); the per-op form is then fan-out, LayerNorm, conv, activation, conv, dropout, add, mask."""
     if not _fused_nodes():
         x_ln, x_res = fanout(x, 2)
         h = layernorm_ch(x_ln, ln[0], ln[1], eps=eps)
         h = conv1d(h, cw1, b1, dil=dil, pad=pad, alpha=alpha, act=act, act_param=act_param, T_out=T_out)
-        return conv1d(h, cw2, b2, res=x_res, mask=mask)
-    return _PreLnFfnFn.apply(x, ln[0], ln[1], cw1.raw(), b1, cw2.raw(), b2, cw1, cw2, dil, pad, alpha, act, act_param, eps, mask, T_out)
+        if drop is None:
+            return conv1d(h, cw2, b2, res=x_res, mask=mask)
+        y = add(x_res, dropout(conv1d(h, cw2, b2), *drop))
+        return add_chan_mask(y, None, mask) if mask is not None else y
+    return _PreLnFfnFn.apply(x, ln[0], ln[1], cw1.raw(), b1, cw2.raw(), b2, cw1, cw2, dil, pad, alpha, act, act_param, eps, mask, T_out,
+                             None if drop is None else (float(drop[0]), int(drop[1]), int(drop[2])))
+
+
+class _AddFn(torch.autograd.Function):
+    """a + b on equal shapes (set_sum_scale); the gradient goes to both unchanged."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        return ops.sum_div(a.contiguous(), b.contiguous())
+
+    @staticmethod
+    def backward(ctx, d):
+        return d, d
+
+
+def add(a, b):
+    return _AddFn.apply(a, b)
+
+
+class _StutterLossFn(torch.autograd.Function):
+    """StutterSpeech's head and losses as one tape node (csrc/stutter.hip): h [B,C,T] (post_net1 output) -> logits [B,T,3] = Linear(C, 3),
+    ce = CrossEntropyLoss(ignore_index=2), focal = MultiFocalLoss (stutter_predictor.py:15-44, stutter_speech.py:97-99).  labels: int64
+    [B,T] already remapped to {0: fluent, 1: stutter, 2: pad}.  The logits carry no gradient (they only feed the accuracy)."""
+
+    @staticmethod
+    def forward(ctx, h, w, b, labels):
+        h = h.contiguous()
+        B, Cc, T = h.shape
+        dev = h.device
+        ops._i(labels, "labels")
+        assert labels.shape == (B, T), (tuple(labels.shape), (B, T))
+        logits = torch.empty(B, T, 3, dtype=torch.float32, device=dev)
+        stats = torch.empty(3, dtype=torch.float32, device=dev)
+        scratch = _det_scratch(dev, L().set_stutter_head_scratch_floats(B, Cc, T))
+        check(L().set_stutter_head_loss(_p(h), _p(w), _p(b), _p(labels), _p(logits), _p(stats), _p(scratch), B, Cc, T, _stream()),
+              "set_stutter_head_loss")
+        ctx.save_for_backward(h, w, logits, labels, stats)
+        ctx.params = (w, b)
+        ctx.mark_non_differentiable(logits)
+        return logits, stats[0], stats[1]
+
+    @staticmethod
+    def backward(ctx, _dlogits, g_ce, g_focal):
+        h, w, logits, labels, stats = ctx.saved_tensors
+        p_w, p_b = ctx.params
+        B, Cc, T = h.shape
+        dev = h.device
+        g_ce = None if g_ce is None else g_ce.contiguous()
+        g_focal = None if g_focal is None else g_focal.contiguous()
+        dh = torch.empty_like(h)
+        part = torch.empty(L().set_stutter_head_scratch_floats(B, Cc, T), dtype=torch.float32, device=dev)  # own buffer: read on the leaf stream
+        check(L().set_stutter_head_loss_bwd(_p(h), _p(w), _p(logits), _p(labels), _p(stats), _p(g_ce), _p(g_focal), _p(dh), None, None,
+                                            _p(part), B, Cc, T, _stream()), "set_stutter_head_loss_bwd")
+        (t_w, r_w), (t_b, r_b) = _tape_tgt(p_w, dev), _tape_tgt(p_b, dev)
+        with leaf_work(dev, r_w is None and r_b is None, part):
+            check(L().set_stutter_head_bwd_reduce(_p(part), _p(t_w), _p(t_b), B, Cc, T, _stream()), "set_stutter_head_bwd_reduce")
+        return dh, r_w, r_b, None
+
+
+def stutter_losses(h, w, b, labels):
+    """(logits [B,T,3], ce, focal) of StutterSpeech's predictor head; see _StutterLossFn."""
+    return _StutterLossFn.apply(h, w, b, labels)
 
 
 class _EmbeddingFn(torch.autograd.Function):

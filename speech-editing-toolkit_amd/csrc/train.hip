@@ -582,6 +582,39 @@ __global__ void __launch_bounds__(256) dropout_kernel(const float *x, float *y, 
     }
 }
 
+// ---- dropout on the branch of a residual sub-block (modules/commons/conv.py:57-65, training):
+//   forward  y = (x + keep(i) z/(1-p)) * mask[b][t]
+//   backward g2 = dy * mask (the residual's gradient), gz = keep(i) g2/(1-p) (the branch's)
+// keep(i) is dropout_kernel's decision for element i of the [B][C][T] tensor (same Philox counter, same threshold), and every
+// product / sum is the one the per-op tape (dropout, add, mask) rounds: the fused node and the tape agree bit for bit.
+__global__ void __launch_bounds__(256) residual_dropout_kernel(const float *x, const float *z, const float *mask, float *y, float *gz,
+                                                               int64_t n, int64_t CT, int T, float p, uint64_t seed, uint64_t offset,
+                                                               const uint64_t *seed_delta) {
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (q * 4 >= n) return;
+    if (seed_delta) seed += *seed_delta;
+    const uint64_t ctr = offset + (uint64_t)q;
+    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x5eedu, 0u};
+    philox_round(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float inv = 1.0f / (1.0f - p);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t i = q * 4 + k;
+        if (i >= n) break;
+        const bool keep = (float)(c[k] >> 8) * (1.0f / 16777216.0f) >= p;
+        const float m = mask ? mask[(i / CT) * T + i % T] : 1.0f;
+        if (gz == nullptr) {  // forward: x = residual, z = branch
+            float v = x[i] + (keep ? z[i] * inv : 0.0f);
+            if (mask) v *= m;
+            y[i] = v;
+        } else {  // backward: x = dy; y = g2, gz = branch gradient
+            const float g = mask ? x[i] * m * 1.0f : x[i];
+            y[i] = g;
+            gz[i] = keep ? g * inv : 0.0f;
+        }
+    }
+}
+
 // ---- losses ------------------------------------------------------------------------------------------------------
 // weights_nonzero_speech (utils/nn/seq_utils.py:33-37): w[b][t] = (sum_m |target[b][t][m]|) != 0
 __global__ void __launch_bounds__(256) frame_weight_kernel(const float *target, float *w, int64_t frames, int M) {
@@ -1378,6 +1411,22 @@ extern "C" int set_dropout(const float *x, float *y, int64_t n, float p, uint64_
     hipLaunchKernelGGL(dropout_kernel, dim3(set_blocks((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, x, y, n, p,
                        seed, offset, set_seed_delta_ptr(), set_aligned16(x, y, y) ? 1 : 0);
     return set_check_launch("set_dropout");
+}
+extern "C" int set_residual_dropout(const float *x, const float *z, const float *mask, float *y, int32_t B, int32_t C, int32_t T, float p,
+                                    uint64_t seed, uint64_t offset, void *stream) {
+    SET_REQUIRE(x && z && y && B > 0 && C > 0 && T > 0 && p >= 0.0f && p < 1.0f, "set_residual_dropout");
+    const int64_t n = (int64_t)B * C * T;
+    hipLaunchKernelGGL(residual_dropout_kernel, dim3(set_blocks((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, x, z, mask, y,
+                       (float *)nullptr, n, (int64_t)C * T, T, p, seed, offset, set_seed_delta_ptr());
+    return set_check_launch("set_residual_dropout");
+}
+extern "C" int set_conv_epilogue_bwd_dropout(const float *dy, const float *mask, float *g2, float *gz, int32_t B, int32_t C, int32_t T,
+                                             float p, uint64_t seed, uint64_t offset, void *stream) {
+    SET_REQUIRE(dy && g2 && gz && B > 0 && C > 0 && T > 0 && p >= 0.0f && p < 1.0f, "set_conv_epilogue_bwd_dropout");
+    const int64_t n = (int64_t)B * C * T;
+    hipLaunchKernelGGL(residual_dropout_kernel, dim3(set_blocks((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, dy,
+                       (const float *)nullptr, mask, g2, gz, n, (int64_t)C * T, T, p, seed, offset, set_seed_delta_ptr());
+    return set_check_launch("set_conv_epilogue_bwd_dropout");
 }
 extern "C" int set_frame_weight(const float *target, float *w, int64_t frames, int32_t M, void *stream) {
     SET_REQUIRE(target && w && frames > 0 && M > 0, "set_frame_weight");

@@ -242,6 +242,8 @@ class StutterSpeechDataset:
         else:
             m = generate_inference_mask(mel2ph, 0.5)  # dataset_utils.py:143-145
         sample["time_mel_mask"] = m
+        if "stutter_mel_mask" in item:  # dataset_utils.py:130-131 (StutterSpeech labels: > 0 stutter, 0 fluent)
+            sample["stutter_mel_mask"] = torch.LongTensor(np.asarray(item["stutter_mel_mask"]))[:T]
         return sample
 
     def collater(self, samples):
@@ -265,4 +267,7 @@ class StutterSpeechDataset:
             batch["pitch"] = collate_1d_or_2d([s["pitch"] for s in samples], 0)
         if self.hparams["use_spk_embed"]:
             batch["spk_embed"] = torch.stack([s["spk_embed"] for s in samples])
+        if "stutter_mel_mask" in samples[0]:  # dataset_utils.py:167-168; padding becomes class 2 in the task's remap
+            batch["stutter_mel_masks"] = collate_1d_or_2d([s["stutter_mel_mask"] for s in samples],
+                                                          self.hparams.get("stutter_pad_idx", -1))
         return batch

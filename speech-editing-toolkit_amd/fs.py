@@ -43,9 +43,10 @@ class ResidualBlock(nn.Module):
     """n x [LN(ch) -> conv k (C->2C) -> *k^-0.5 -> GELU -> conv 1x1 (2C->C)] + residual, x nonpadding
     (modules/commons/conv.py:24-65)."""
 
-    def __init__(self, channels, kernel_size, dilation, n=2, c_multiple=2, ln_eps=1e-5):
+    def __init__(self, channels, kernel_size, dilation, n=2, c_multiple=2, ln_eps=1e-5, dropout=0.0):
         super().__init__()
         self.kernel_size, self.dilation, self.ln_eps = kernel_size, dilation, ln_eps
+        self.dropout = dropout  # on each unit's branch before the residual add (conv.py:59-61), train() mode with a tape only
         self.blocks = nn.ModuleList([
             nn.Sequential(
                 nn.LayerNorm(channels, eps=ln_eps),
@@ -56,14 +57,18 @@ class ResidualBlock(nn.Module):
             ) for _ in range(n)])
         self._cw = [(_cw(b[1]), _cw(b[4])) for b in self.blocks]
 
-    def run(self, x):
+    def run(self, x, drop_seed=None, drop_site=0):
+        """drop_seed: Philox seed of the branch dropout (active when `dropout` > 0 in train() mode with a tape); unit i of the block draws
+        its keep-mask at counter offset (drop_site + i) * 2^28, so every mask is a function of (seed, site) only."""
         F = _backend()
         k, d = self.kernel_size, self.dilation
+        p = self.dropout if (drop_seed is not None and self.training and torch.is_grad_enabled()) else 0.0
         nonpad = F.abs_sum_mask(x.detach())  # conv.py:58
-        for b, (w1, w2) in zip(self.blocks, self._cw):
+        for i, (b, (w1, w2)) in enumerate(zip(self.blocks, self._cw)):
             # LN -> conv k * k^-0.5 -> GELU -> conv 1x1, + x, * nonpadding: one tape node in training (autograd_ops._PreLnFfnFn)
+            drop = (p, int(drop_seed), (drop_site + i) * (1 << 28)) if p > 0 else None
             x = F.preln_ffn(x, (b[0].weight, b[0].bias), w1, b[1].bias, w2, b[4].bias, dil=d, pad=(d * (k - 1)) // 2, alpha=k ** -0.5,
-                            act="gelu", mask=nonpad, eps=self.ln_eps)
+                            act="gelu", mask=nonpad, eps=self.ln_eps, drop=drop)
         return x
 
 
@@ -71,12 +76,12 @@ class ConvBlocks(nn.Module):
     """modules/commons/conv.py:68-116 (norm 'ln', is_BTC handled by the caller: this works on [B,C,T])."""
 
     def __init__(self, hidden_size, out_dims, dilations, kernel_size, layers_in_block=2, c_multiple=2,
-                 ln_eps=1e-5, post_net_kernel=3, norm_type="ln"):
+                 ln_eps=1e-5, post_net_kernel=3, norm_type="ln", dropout=0.0):
         super().__init__()
         if norm_type != "ln":
             raise NotImplementedError("enc_dec_norm=%r (spec_denoiser.yaml uses 'ln')" % norm_type)
         self.res_blocks = nn.Sequential(*[
-            ResidualBlock(hidden_size, kernel_size, d, n=layers_in_block, c_multiple=c_multiple, ln_eps=ln_eps)
+            ResidualBlock(hidden_size, kernel_size, d, n=layers_in_block, c_multiple=c_multiple, ln_eps=ln_eps, dropout=dropout)
             for d in dilations])
         self.last_norm = nn.LayerNorm(hidden_size, eps=ln_eps)
         self.post_net1 = nn.Conv1d(hidden_size, out_dims, kernel_size=post_net_kernel, padding=post_net_kernel // 2)
@@ -87,11 +92,11 @@ class ConvBlocks(nn.Module):
                 nn.init.xavier_uniform_(m.weight)
         self._w_post = _cw(self.post_net1)
 
-    def run(self, x):
+    def run(self, x, drop_seed=None, drop_site=0):
         F = _backend()
         nonpad = F.abs_sum_mask(x.detach())  # conv.py:108
-        for rb in self.res_blocks:
-            x = rb.run(x)
+        for i, rb in enumerate(self.res_blocks):
+            x = rb.run(x, drop_seed, drop_site + i * len(rb.blocks))
         x = F.add_chan_mask(x, None, nonpad)
         x = F.layernorm_ch(x, self.last_norm.weight, self.last_norm.bias, mask=nonpad, eps=self.ln_eps)
         return F.conv1d(x, self._w_post, self.post_net1.bias, pad=self.post_net_kernel // 2, mask=nonpad)

@@ -530,11 +530,36 @@ def layernorm_ch(x, gamma, beta, mask=None, eps=1e-5, out=None):
     return out
 
 
-def preln_ffn(x, ln, cw1, b1, cw2, b2, *, dil=1, pad=0, alpha=1.0, act="gelu", act_param=0.0, mask=None, eps=1e-5, T_out=None):
-    """Inference form of autograd_ops.preln_ffn: (x + conv1x1(act(alpha conv_k(LN(x))))) (* mask), the activation in the first conv's epilogue."""
+def preln_ffn(x, ln, cw1, b1, cw2, b2, *, dil=1, pad=0, alpha=1.0, act="gelu", act_param=0.0, mask=None, eps=1e-5, T_out=None,
+              drop=None):
+    """Inference form of autograd_ops.preln_ffn: (x + conv1x1(act(alpha conv_k(LN(x))))) (* mask), the activation in the first conv's epilogue.
+    drop=(p, seed, offset): the branch goes through inverted dropout before the residual add (set_residual_dropout)."""
     h = layernorm_ch(x, ln[0], ln[1], eps=eps)
     h = conv1d(h, cw1, b1, dil=dil, pad=pad, alpha=alpha, act=act, act_param=act_param, T_out=T_out)
-    return conv1d(h, cw2, b2, res=x, mask=mask)
+    if drop is None:
+        return conv1d(h, cw2, b2, res=x, mask=mask)
+    return residual_dropout(x, conv1d(h, cw2, b2), mask, *drop)
+
+
+def residual_dropout(x, z, mask, p, seed, offset=0):
+    """(x + keep z/(1-p)) (* mask) on [B,C,T]; keep = set_dropout's decision for (seed, offset, element index)."""
+    _f(x), _f(z), _f(mask)
+    B, Cc, T = x.shape
+    y = torch.empty_like(x)
+    check(_lib.lib().set_residual_dropout(_p(x), _p(z), _p(mask), _p(y), B, Cc, T, float(p), int(seed), int(offset), _stream()),
+          "set_residual_dropout")
+    return y
+
+
+def stutter_head(h, w, b):
+    """Inference form of autograd_ops.stutter_losses: logits [B,T,3] = Linear(C, 3) over the frames of h [B,C,T] (no losses)."""
+    _f(h), _f(w), _f(b)
+    B, Cc, T = h.shape
+    assert w.shape == (3, Cc) and b.shape == (3,), (tuple(w.shape), tuple(b.shape))
+    logits = torch.empty(B, T, 3, dtype=torch.float32, device=h.device)
+    check(_lib.lib().set_stutter_head_loss(_p(h), _p(w), _p(b), None, _p(logits), None, None, B, Cc, T, _stream()),
+          "set_stutter_head_loss")
+    return logits
 
 
 def preln_self_attn(x, ln, attn, key_padding=None, mask=None, eps=1e-5):

@@ -16,6 +16,7 @@ from . import autograd_ops, ops
 from .diffnet import DiffNet
 from .hparams import hparams, set_hparams
 from .spec_denoiser import GaussianDiffusion, GaussianDiffusionNormal
+from .stutter_speech import GaussianDiffusionStutter
 from .text_encoder import build_token_encoder
 from .vocoder_infer import get_vocoder_cls
 
@@ -28,6 +29,7 @@ TASK_ALIASES = {
     "tasks.speech_editing.spec_denoiser.SpeechDenoiserTask": "set_amd.tasks.SpeechDenoiserTask",
     "tasks.speech_editing.campnet.CampNetTask": "set_amd.tasks.CampNetTask",
     "tasks.speech_editing.spec_denoiser_normal.SpeechDenoiserNormalTask": "set_amd.tasks.SpeechDenoiserNormalTask",
+    "tasks.speech_editing.stutter_speech.StutterSpeechTask": "set_amd.tasks.StutterSpeechTask",
 }
 
 
@@ -72,6 +74,10 @@ class SpeechEditingBaseTask:
     def training_step(self, sample, optimizer, **kwargs):
         """One optimisation step: forward + losses, backward, gradient all-reduce (if distributed), clip + AdamW."""
         return _optimisation_step(self, sample, optimizer, **kwargs)
+
+    def loss_terms(self, losses):
+        """The terms training_step sums into the optimised total (every loss, unweighted)."""
+        return list(losses.values())
 
     # ---- Trainer hooks (tasks/tts/speech_base.py:59-137,140-205; utils/commons/base_task.py:60-65) -----------------
     def configure_optimizers(self):
@@ -315,6 +321,108 @@ class SpeechDenoiserNormalTask(SpeechDenoiserTask):
     model_cls = GaussianDiffusionNormal
 
 
+class StutterSpeechTask(SpeechDenoiserTask):
+    """tasks/speech_editing/stutter_speech.py:20-156 (egs/stutter_speech.yaml): the spec_denoiser task over GaussianDiffusionStutter,
+    plus the stutter predictor's cross-entropy and focal losses, weighted by the global step in the optimised total (the logged losses
+    stay unweighted), and the frame accuracies in validation."""
+    model_cls = GaussianDiffusionStutter
+
+    @staticmethod
+    def remap_stutter_labels(m):
+        """stutter_speech.py:75-76 without mutating the batch: > 0 -> 1 (stutter), < 0 -> 2 (pad: the collate fills with
+        stutter_pad_idx = -1), 0 stays 0 (fluent).  int64 [B,T]."""
+        return ((m > 0).long() + 2 * (m < 0).long()).contiguous()
+
+    def loss_weights(self):
+        """stutter_speech.py:101-104 at self.global_step; every other loss has weight 1."""
+        g = self.global_step + 1
+        return {"ce": 8e-3 + 5e-3 * g / 100000, "focal": 1 + 2 * g / 100000}
+
+    def loss_terms(self, losses):
+        w = self.loss_weights()
+        with torch.enable_grad():
+            return [v * w[k] if k in w else v for k, v in losses.items()]
+
+    def run_model(self, sample, infer=False, tape=True, **kwargs):
+        """stutter_speech.py:59-95.  infer=False: (losses, output), the loss dict in the reference's order (l1 / ssim, pdur, wdur, ce,
+        focal, uv, f0); infer=True: the pasted output, `stutter_mel_masks` optional."""
+        target = sample["mels"]
+        labels = sample.get("stutter_mel_masks")
+        if labels is not None:
+            labels = self.remap_stutter_labels(labels)
+            T = target.shape[1]
+            if labels.shape[1] != T:  # masks collated narrower than the mels (an item's mask shorter than its mel): no label = pad
+                labels = torch.nn.functional.pad(labels[:, :T], (0, max(0, T - labels.shape[1])), value=2).contiguous()
+        tmask = sample["time_mel_masks"][:, :, None]
+        spk = sample.get("spk_embed") if not hparams["use_spk_id"] else sample.get("spk_ids")
+        if infer:
+            with torch.no_grad():
+                output = self.model(sample["txt_tokens"], tmask, labels, mel2ph=sample["mel2ph"], spk_embed=spk, ref_mels=target,
+                                    f0=sample["f0"], uv=sample["uv"], energy=None, infer=True, **kwargs)
+                B, T, M = target.shape
+                output["mel_out"] = ops.blend_mask(target.contiguous(), output["mel_out"], tmask.reshape(B, T).contiguous(), M)
+            return output
+        if labels is None:
+            raise KeyError("StutterSpeechTask: the batch has no 'stutter_mel_masks' (binarise with stutter masks)")
+        with (torch.enable_grad() if tape else torch.no_grad()):
+            output = self.model(sample["txt_tokens"], tmask, labels, mel2ph=sample["mel2ph"], spk_embed=spk, ref_mels=target,
+                                f0=sample["f0"], uv=sample["uv"], energy=None, infer=False, **kwargs)
+            base = self.compute_losses(output, sample)
+        losses = {}
+        for k in ("l1_coarse", "ssim_coarse", "pdur", "wdur"):
+            if k in base:
+                losses[k] = base.pop(k)
+        losses["ce"], losses["focal"] = output.pop("stutter_ce"), output.pop("stutter_focal")
+        losses.update(base)  # uv, f0
+        output["stutter_mel_masks"] = labels
+        with torch.no_grad():
+            B, T, M = target.shape
+            output["mel_out"] = ops.blend_mask(target.contiguous(), output["mel_out"].detach().contiguous(),
+                                               tmask.reshape(B, T).contiguous(), M)
+        return losses, output
+
+    def _training_step(self, sample, batch_idx, optimizer_idx=-1, **kwargs):
+        """stutter_speech.py:97-107: the step-weighted sum of the losses that carry a gradient."""
+        losses, _ = self.run_model(sample, infer=False, **kwargs)
+        w = self.loss_weights()
+        with torch.enable_grad():
+            total = sum(w.get(k, 1) * v for k, v in losses.items() if isinstance(v, torch.Tensor) and v.requires_grad)
+        log = {k: v.detach() for k, v in losses.items()}
+        log["batch_size"] = sample["txt_tokens"].shape[0]
+        return total, log
+
+    @staticmethod
+    def frame_accuracy(logits, labels):
+        """stutter_speech.py:131-140: acc = correctly predicted class-0 and class-1 frames / numel (pads in the denominator); acc_1 =
+        class-1 recall, None without class-1 frames."""
+        pred = logits.argmax(dim=-1)
+        hit = pred == labels
+        acc = ((hit & (pred == 0)).float().sum() + (hit & (pred == 1)).float().sum()) / labels.numel()
+        ones = labels == 1
+        acc_1 = (pred[ones] == 1).float().sum() / ones.sum().float() if bool(ones.any()) else None
+        return acc, acc_1
+
+    def validation_step(self, sample, batch_idx):
+        """stutter_speech.py:109-156 without plots: the unweighted loss dict, `acc` / `acc_1`, and total_loss = the sum of the dict
+        INCLUDING acc (the reference's quirk, kept)."""
+        losses, output = self.run_model(sample, infer=False, tape=False, seed=batch_idx)
+        acc, acc_1 = self.frame_accuracy(output["stutter_predictor_out"], output["stutter_mel_masks"])
+        losses["acc"] = acc
+        if acc_1 is not None:
+            losses["acc_1"] = acc_1
+        losses = {k: float(v) for k, v in losses.items()}
+        return {"losses": losses, "total_loss": sum(losses.values()), "nsamples": sample.get("nsamples", 1)}
+
+    @torch.no_grad()
+    def predict_stutter(self, sample):
+        """Detection: per-frame class ids int64 [B,T] (0 fluent, 1 stutter, 2 pad) from forward_stutter_predictor (all-zero time
+        mask, ground-truth mel2ph and pitch, no diffusion)."""
+        spk = sample.get("spk_embed") if not hparams["use_spk_id"] else sample.get("spk_ids")
+        logits = self.model.forward_stutter_predictor(sample["txt_tokens"], sample["mel2ph"], spk, sample["mels"], sample["f0"],
+                                                      sample["uv"])
+        return logits.argmax(dim=-1)
+
+
 class CampNetTask(SpeechEditingBaseTask):
     """tasks/speech_editing/campnet.py:19-138 (BASELINE configs[4]): `CampNetTask(SpeechEditingBaseTask)` -- the phone and
     word dictionaries of <binary_data_dir> size the model (`word_set.json`, campnet.py:22-23,28-31), `run_model` returns
@@ -395,7 +503,7 @@ def _optimisation_step(task, sample, optimizer, **kwargs):
     try:
         losses, _ = task.run_model(sample, infer=False, **kwargs)
         with torch.enable_grad():  # callers may run under a global no_grad
-            total = autograd_ops.sum_losses(list(losses.values()))
+            total = autograd_ops.sum_losses(task.loss_terms(losses))
         total.backward()
     except BaseException:
         optimizer.abort_step()
