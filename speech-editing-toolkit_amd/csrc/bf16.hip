@@ -521,12 +521,8 @@ template <int CINP>
 static int launch_conv1x1_oneshot(const SetConv1dArgs &a, hipStream_t s) {
     const int CoutP = round_up_i(a.Cout, 128);
     const size_t lds = (size_t)128 * (CINP * 2 + 16);
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_oneshot_bf16_kernel<CINP>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024), "conv 1x1 attr");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 96 * 1024, "conv 1x1 attr", conv1x1_oneshot_bf16_kernel<CINP>)) return rc;
     dim3 grid((a.T_iter + 127) / 128, (a.Cout + 127) / 128, a.B), block(256);
     hipLaunchKernelGGL((conv1x1_oneshot_bf16_kernel<CINP>), grid, block, lds, s, a, CoutP, round_up_i(a.Cin, 32) / 32);
     return set_check_launch("set_conv1d(bf16, 1x1)");
@@ -543,12 +539,8 @@ static int launch_conv_bf16(const SetConv1dArgs &a, int lo, int halo, hipStream_
     constexpr int MB = 64 * WM, NB = 64 * WN, ROWB = KCH * 2 + 16, BF_TG_MAX = TGM;
     const int CinP = round_up_i(a.Cin, 32), CoutP = round_up_i(a.Cout, 128);
     const size_t lds = (size_t)BF_TG_MAX * MB * ROWB + (size_t)(NB + halo + (VEC ? 1 : 0)) * ROWB;  // (VEC: one spare row for the masked-out writes)
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv1d_bf16_kernel<WM, WN, KCH, TGM, HALO, ADD, VEC>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024), "conv bf16 attr");  // (two blocks per CU)
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;  // (96 KiB: two blocks per CU)
+    if (int rc = set_lds_optin(lds_once, 96 * 1024, "conv bf16 attr", conv1d_bf16_kernel<WM, WN, KCH, TGM, HALO, ADD, VEC>)) return rc;
     if (lds > 96 * 1024) return set_fail(SET_E_UNSUPPORTED, "set_conv1d(bf16)", "tile does not fit LDS");
     dim3 grid((a.T_iter + NB - 1) / NB, (a.Cout + MB - 1) / MB, a.B), block(256);
     hipLaunchKernelGGL((conv1d_bf16_kernel<WM, WN, KCH, TGM, HALO, ADD, VEC>), grid, block, lds, s, a, lo, halo, CinP, CoutP);

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <atomic>
+
 #include "set_amd.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -30,6 +32,50 @@ static inline int set_check_launch(const char *what) {
         hipError_t e__ = (call);                                                   \
         if (e__ != hipSuccess) return set_fail(SET_E_LAUNCH, what, hipGetErrorString(e__)); \
     } while (0)
+
+// ---- launch-time state set up once per device -----------------------------------------------
+// Launches come from the main thread (forward) and torch's autograd device thread (backward), on any device.  A site keeps one
+// `static SetDeviceOnce`; run(f) calls f() -> SET_OK | error on the current device unless f already succeeded there.  Success is one
+// bit per device (release / acquire); a failure records nothing, so the next call retries.  Two threads racing on a first call may
+// both run f: every f is idempotent (the same attribute value, the same constant bytes).  A device index beyond the mask, or none
+// (hipGetDevice failed), runs f every time: correct, only slower.  Warm path: hipGetDevice and one atomic load.
+struct SetDeviceOnce {
+    std::atomic<uint64_t> done{0};
+    template <typename F> int run(F &&f) {
+        int dev = -1;
+        const uint64_t bit = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 64 ? uint64_t(1) << dev : 0;
+        if (done.load(std::memory_order_acquire) & bit) return SET_OK;
+        const int rc = f();
+        if (rc == SET_OK) done.fetch_or(bit, std::memory_order_release);
+        return rc;
+    }
+};
+// Opt `kernels` in to `bytes` of dynamic LDS on the current device, once per device.
+template <typename... K>
+static inline int set_lds_optin(SetDeviceOnce &once, int bytes, const char *what, K... kernels) {
+    return once.run([&] {
+        for (const void *k : {reinterpret_cast<const void *>(kernels)...})
+            SET_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), what);
+        return SET_OK;
+    });
+}
+// The current device's CU count, queried once per device; on failure the query's error (nothing cached, *n_cu untouched).  The
+// cached count, nonzero once known, is the per-device done flag; like SetDeviceOnce, a device beyond the table asks every time.
+static inline hipError_t set_cu_count(int *n_cu) {
+    static std::atomic<int> cached[64];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const bool slot = dev >= 0 && dev < 64;
+    int n = slot ? cached[dev].load(std::memory_order_relaxed) : 0;
+    if (n == 0) {
+        e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        if (e != hipSuccess) return e;
+        if (slot) cached[dev].store(n, std::memory_order_relaxed);
+    }
+    *n_cu = n;
+    return hipSuccess;
+}
 
 const uint64_t *set_seed_delta_ptr();  // the device word of set_rng_seed_delta (csrc/diffnet.hip), NULL when unset
 // Clear `words` 32-bit words with a KERNEL.  Not hipMemsetAsync: as a memset node of a captured graph (training.GraphedTrainStep) a clear

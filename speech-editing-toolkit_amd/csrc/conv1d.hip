@@ -527,16 +527,9 @@ static int launch_conv_v2(const SetConv1dArgs &a, hipStream_t s) {
     const int ch = CinP < ch_max ? CinP : ch_max;
     size_t lds = (size_t)ch * (64 + halo) * sizeof(float);
     if (lds < 128 * 64 * sizeof(float)) lds = 128 * 64 * sizeof(float);  // epilogue slice
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv1d_mfma_v2_kernel<1>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024), "conv v2 attr");
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv1d_mfma_v2_kernel<2>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024), "conv v2 attr");
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv1d_mfma_v2_kernel<4>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024), "conv v2 attr");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 128 * 1024, "conv v2 attr", conv1d_mfma_v2_kernel<1>, conv1d_mfma_v2_kernel<2>, conv1d_mfma_v2_kernel<4>))
+        return rc;
     dim3 grid((a.T_iter + 63) / 64, (a.Cout + 128 * RB - 1) / (128 * RB), a.B), block(256);
     if (RB == 4) hipLaunchKernelGGL(conv1d_mfma_v2_kernel<4>, grid, block, lds, s, a, lo, halo, CinP, ch_max);
     else if (RB == 2) hipLaunchKernelGGL(conv1d_mfma_v2_kernel<2>, grid, block, lds, s, a, lo, halo, CinP, ch_max);

@@ -374,12 +374,8 @@ int launch_conv_x2(const SetConv1dArgs &a, int lo, int halo, hipStream_t s, int 
     constexpr int MB = 32 * RBW * WM, NB = 32 * NCB * WN;
     const int CinP = cx_round_up(a.Cin, CX_KCH), CoutP = cx_round_up(a.Cout, 32);
     const size_t lds = (size_t)2 * (NB + halo) * CX_ROWB;
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(conv1d_x2_kernel<WM, WN, RBW, NCB, PHASES>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024), "conv x2 attr");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 96 * 1024, "conv x2 attr", conv1d_x2_kernel<WM, WN, RBW, NCB, PHASES>)) return rc;
     if (lds > 96 * 1024) return set_fail(SET_E_UNSUPPORTED, "set_conv1d(f16x2)", "tile does not fit LDS");
     dim3 grid((a.T_iter + NB - 1) / NB, (a.Cout + MB - 1) / MB, a.B), block(256);
     hipLaunchKernelGGL((conv1d_x2_kernel<WM, WN, RBW, NCB, PHASES>), grid, block, lds, s, a, lo, halo, CinP, CoutP, ph_u, ph_pad);

@@ -1089,13 +1089,8 @@ extern "C" int set_diffnet_layer(const SetDiffnetLayerArgs *args, void *stream) 
     SET_REQUIRE(a.x_in != a.x_out, "set_diffnet_layer(x_in must not alias x_out)");
     if (a.dil > 8) return set_fail(SET_E_UNSUPPORTED, "set_diffnet_layer", "dilation > 8 (LDS tile > 80 KiB)");
     const size_t lds = (size_t)DC * (NT + 2 * a.dil) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(diffnet_layer_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024),
-                "set_diffnet_layer(attr)");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 96 * 1024, "set_diffnet_layer(attr)", diffnet_layer_kernel)) return rc;
     dim3 grid((a.T + NT - 1) / NT, a.B);
     hipLaunchKernelGGL(diffnet_layer_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
     return set_check_launch("set_diffnet_layer");
@@ -1107,6 +1102,13 @@ extern "C" int set_debug_split_phase_buffer(uint64_t *buf) {
 }
 
 extern "C" int64_t set_sizeof_diffnet_stack_args(void) { return (int64_t)sizeof(SetDiffnetStackArgs); }
+
+// read at every call (tests set the environment between launches): SET_AMD_SPLIT_F32 != 0 pins the row-split kernel to the fp32 pipe
+static bool split_f32_pinned() {
+    const char *e = getenv("SET_AMD_SPLIT_F32");
+    return e && atoi(e) != 0;
+}
+static int x3_mode_of_images(int images) { return (images & 4) ? 3 : ((images & 8) ? 2 : 0); }  // split-operand mode of an `images` mask (set_amd.h)
 
 // 0 = direct kernel, 64-frame tiles; 1 = direct kernel, 32-frame tiles; 2 = Winograd F(2,3) kernel (64-frame tiles,
 // 8-wave blocks, needs its packed images, dilation_cycle_length <= 4 and at least ~0.68 tiles per CU to be worth it);
@@ -1122,7 +1124,7 @@ static int stack_variant(int B, int T, int dcl, bool have_wino, bool have_split,
     const int64_t split_blocks = 4 * (int64_t)B * ((T + 31) / 32);
     // co-residency: two blocks per CU for the fp32-pipe kernel, ONE for the two-piece fp16 one (its A ring takes the whole register
     // file of a SIMD lane group: launch bounds (256, 1)) unless SET_AMD_SPLIT_F32 pins the fp32-pipe kernel
-    const bool split_one_per_cu = have_x3 && !(getenv("SET_AMD_SPLIT_F32") && atoi(getenv("SET_AMD_SPLIT_F32")) != 0);
+    const bool split_one_per_cu = have_x3 && !split_f32_pinned();
     const bool split_fits = have_split && dcl <= 4 && split_blocks <= (split_one_per_cu ? 1 : 2) * (int64_t)n_cu;
     const bool split_pays = split_blocks <= (int64_t)(have_x3 ? 1 : 2) * n_cu;
     int split_env = 1;
@@ -1143,18 +1145,17 @@ static int stack_variant(int B, int T, int dcl, bool have_wino, bool have_split,
     return wino ? 2 : (ncb == 1 ? 1 : 0);
 }
 extern "C" int set_diffnet_stack_variant(int B, int T, int dilation_cycle_length, int images) {
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    return stack_variant(B, T, dilation_cycle_length, (images & 1) != 0, (images & 2) != 0,
-                         (images & 4) ? 3 : ((images & 8) ? 2 : 0), n_cu);
+    int n_cu = 256;
+    (void)set_cu_count(&n_cu);  // (stays 256 when the query fails)
+    return stack_variant(B, T, dilation_cycle_length, (images & 1) != 0, (images & 2) != 0, x3_mode_of_images(images), n_cu);
 }
 
 int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, int n_cu, int fault_tile, hipStream_t s);  // csrc/diffnet_x3.hip
 int set_x3_winograd_selected(int x3_mode, int B, int T, int dilation_cycle_length, int n_cu);                // csrc/diffnet_x3.hip (0 / 1 / 2)
 extern "C" int set_diffnet_stack_x3_winograd(int B, int T, int dilation_cycle_length, int images) {
-    int dev = 0, n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-    const int x3_mode = (images & 4) ? 3 : ((images & 8) ? 2 : 0);
+    int n_cu = 256;
+    (void)set_cu_count(&n_cu);  // (stays 256 when the query fails)
+    const int x3_mode = x3_mode_of_images(images);
     if (stack_variant(B, T, dilation_cycle_length, (images & 1) != 0, (images & 2) != 0, x3_mode, n_cu) != 5) return 0;
     return set_x3_winograd_selected(x3_mode, B, T, dilation_cycle_length, n_cu);
 }
@@ -1169,22 +1170,12 @@ extern "C" int set_diffnet_stack(const SetDiffnetStackArgs *args, void *stream) 
     SET_REQUIRE(a.B > 0 && a.T > 0 && a.L > 0 && a.dilation_cycle_length >= 1 && a.dilation_cycle_length <= 4,
                 "set_diffnet_stack");
     hipStream_t s = (hipStream_t)stream;
-    static int n_cu = 0;
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void *fns[5] = {reinterpret_cast<const void *>(diffnet_stack_kernel<1, 8, 2>),
-                              reinterpret_cast<const void *>(diffnet_stack_kernel<2, 4, 2>),
-                              reinterpret_cast<const void *>(diffnet_stack_wino_kernel<true>),
-                              reinterpret_cast<const void *>(diffnet_stack_wino_kernel<false>),
-                              reinterpret_cast<const void *>(diffnet_stack_split_kernel)};
-        for (const void *f : fns)
-            SET_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024),
-                    "set_diffnet_stack(attr)");
-        int dev = 0;
-        SET_HIP(hipGetDevice(&dev), "set_diffnet_stack");
-        SET_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev), "set_diffnet_stack");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 150 * 1024, "set_diffnet_stack(attr)", diffnet_stack_kernel<1, 8, 2>, diffnet_stack_kernel<2, 4, 2>,
+                               diffnet_stack_wino_kernel<true>, diffnet_stack_wino_kernel<false>, diffnet_stack_split_kernel))
+        return rc;
+    int n_cu = 0;
+    SET_HIP(set_cu_count(&n_cu), "set_diffnet_stack");
     // Tile width: a task (l, i) needs tiles i-1..i+1 of layer l-1, so at most `tiles per layer` tasks are ever
     // runnable.  Workers (2 per CU) must stay BELOW that or the youngest ones only wait (measured: 36 % wait time
     // with 512 workers on 416 64-frame tiles).  Use 64-frame tiles when a layer has >= 1.5x the workers, else
@@ -1195,7 +1186,7 @@ extern "C" int set_diffnet_stack(const SetDiffnetStackArgs *args, void *stream) 
     int fault_tile = -1;  // test hook: never publish this tile of layer 0 (exercises the time-out / error path)
     if (const char *e = getenv("SET_AMD_FAULT_TILE")) fault_tile = atoi(e);
     if (variant >= 4) return set_launch_diffnet_stack_x3(a, n_cu, fault_tile, s);
-    if (variant == 3 && a.wx3_all && a.x3_mode == 2 && !(getenv("SET_AMD_SPLIT_F32") && atoi(getenv("SET_AMD_SPLIT_F32")) != 0))
+    if (variant == 3 && a.wx3_all && a.x3_mode == 2 && !split_f32_pinned())
         return set_launch_diffnet_stack_split_x2(a, fault_tile, s);  // the same scheme on the two-piece fp16 operands
     if (variant == 3) {
         const int tiles = (a.T + 31) / 32, nt = a.B * tiles;
@@ -1797,14 +1788,8 @@ static bool boundary_fusable(const SetDiffLoopArgs &a) {
 
 static int launch_boundary(const SetDiffLoopArgs &a, int Bg, const float *skip, float *x, const float *eps, int sid,
                            uint64_t quad_offset, float *xin_next, bool x2, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(diffnet_boundary_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024), "boundary(attr)");
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(diffnet_boundary_x2_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024), "boundary(attr)");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 80 * 1024, "boundary(attr)", diffnet_boundary_kernel, diffnet_boundary_x2_kernel)) return rc;
     BoundaryArgs g = {};
     g.skip = skip; g.x = x; g.eps = eps; g.coef4 = a.coef4 + 4 * sid;
     g.w_skip_p = a.w_skip_p; g.b_skip = a.b_skip; g.w_outp_p = a.w_outp_p; g.b_outp = a.b_outp;
@@ -1860,19 +1845,15 @@ static int diffusion_chain(const SetDiffLoopArgs &a, int g, int b0, int Bg, hipS
     int rc = SET_OK;
     const bool fused_boundary = boundary_fusable(a);
     const bool bf16_loop = a.img16_all != nullptr;
+    int n_cu = 0;
+    SET_HIP(set_cu_count(&n_cu), "set_diffusion_loop");
     // the step boundary on two-piece fp16 operands whenever the layer stack runs on them (same splitting, same range guard)
-    static int n_cu_chain = 0;
-    if (!n_cu_chain) {
-        int dev = 0;
-        SET_HIP(hipGetDevice(&dev), "set_diffusion_loop");
-        SET_HIP(hipDeviceGetAttribute(&n_cu_chain, hipDeviceAttributeMultiprocessorCount, dev), "set_diffusion_loop");
-    }
     bool boundary_x2 = false;
     if (a.persistent && !bf16_loop && fused_boundary && a.w_skip_x2 && a.w_outp_x2 && a.w_in_x2 && a.wx3_all && a.x3_mode == 2 &&
         a.M <= 96) {
         const int v = stack_variant(Bg, T, a.dilation_cycle_length, a.w1w_all && a.w2w_all, a.w1s_all && a.w2s_all && a.z_ws,
-                                    a.x3_mode, n_cu_chain);
-        boundary_x2 = v == 5 || (v == 3 && !(getenv("SET_AMD_SPLIT_F32") && atoi(getenv("SET_AMD_SPLIT_F32")) != 0));
+                                    a.x3_mode, n_cu);
+        boundary_x2 = v == 5 || (v == 3 && !split_f32_pinned());
     }
     // the bf16-operand loop takes the split-operand boundary whenever its images are given (round 4: 85 -> 37 us per step at B = 32,
     // T = 800; it is the fp32-equivalent one, and it raises the same range word, which the caller must read)

@@ -1541,14 +1541,10 @@ extern "C" int set_diffnet_layer_fwd_bf16(const SetDiffnetLayerBf16Args *args, v
     // tile: 128 frames, 8 waves, one block per CU (round 3's 64-frame / two-blocks-per-CU experiment spilled registers, measured
     // slower, and is gone)
     constexpr int tile = 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(diffnet_layer_fwd_bf16_kernel<true, 128>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "layer fwd bf16 attr");
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(diffnet_layer_fwd_bf16_kernel<false, 128>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "layer fwd bf16 attr");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 160 * 1024, "layer fwd bf16 attr", diffnet_layer_fwd_bf16_kernel<true, 128>,
+                               diffnet_layer_fwd_bf16_kernel<false, 128>))
+        return rc;
     const size_t ldsz = (size_t)(tile + 2 * a.dil) * XR + (size_t)tile * CR + 5 * FC * sizeof(float);  // tiles, step offsets, the two bias vectors
     dim3 grid((a.T + tile - 1) / tile, a.B);
     hipStream_t st = (hipStream_t)stream;
@@ -1568,8 +1564,8 @@ static int layers_tile_env() { const char *e = getenv("SET_AMD_BF16_FUSE_TILE");
 extern "C" int64_t set_sizeof_diffnet_layers_bf16_args(void) { return (int64_t)sizeof(SetDiffnetLayersBf16Args); }
 
 static int layers_cu_count() {
-    static int n_cu = 0;
-    if (!n_cu) { int dev = 0; hipDeviceProp_t pr; n_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256; }
+    int n_cu = 256;
+    (void)set_cu_count(&n_cu);  // (stays 256 when the query fails)
     return n_cu;
 }
 // tile width for a group: 128 frames (half the weight bytes per MFMA, 4 barriers per layer) when that still fills 3/4 of the chip,
@@ -1632,13 +1628,10 @@ extern "C" int set_diffnet_layers_fwd_bf16(const SetDiffnetLayersBf16Args *args,
     const size_t ldsz = tile == 64 ? (size_t)(64 + 2 * dmax) * XR + (size_t)64 * CR + (size_t)64 * XR + (size_t)a.nl * (FC + 1024) * sizeof(float)
                                    : (size_t)(128 + 2 * dmax) * XR + (size_t)128 * CR + (size_t)a.nl * FC * sizeof(float) + 2 * 1024 * sizeof(float);
     if (ldsz > 160 * 1024) return set_fail(SET_E_UNSUPPORTED, "set_diffnet_layers_fwd_bf16", "tiles do not fit LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void *ks[] = {reinterpret_cast<const void *>(diffnet_layers_reg_bf16_kernel<false, 4>),
-                            reinterpret_cast<const void *>(diffnet_layers_t128_bf16_kernel<false, 1>)};
-        for (const void *k : ks) SET_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "layers bf16 attr");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 160 * 1024, "layers bf16 attr", diffnet_layers_reg_bf16_kernel<false, 4>,
+                               diffnet_layers_t128_bf16_kernel<false, 1>))
+        return rc;
     dim3 grid((a.T + la.nv - 1) / la.nv, a.B);
     // Shipped instantiations only.  Measured in round 4 and left out (B = 32, T = 800, sustained us per layer; profiles/r04_bf16_ab.log):
     // 128-frame shape with 0 / 1 / 2 / 3 / 4 column blocks of the skip rows in registers 40.7 / 39.4 / 39.6 / 39.8 / 41.8 (21 / 45 / 67
@@ -1667,12 +1660,8 @@ extern "C" int set_diffnet_layer_bwd_bf16(const SetDiffnetLayerBf16BwdArgs *args
     const int nt = layer_bwd_tile();
     SET_REQUIRE(nt - 2 * a.dil >= 32, "set_diffnet_layer_bwd_bf16 (dilation too large for the tile)");
     const size_t ldsz = (size_t)(nt + 2 * a.dil) * DR;
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(diffnet_layer_bwd_bf16_kernel<128>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "layer bwd bf16 attr");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 160 * 1024, "layer bwd bf16 attr", diffnet_layer_bwd_bf16_kernel<128>)) return rc;
     dim3 grid(set_diffnet_layer_bwd_bf16_tiles(a.T, a.dil), a.B);
     hipLaunchKernelGGL(diffnet_layer_bwd_bf16_kernel<128>, grid, dim3(512), ldsz, (hipStream_t)stream, a);
     return set_check_launch("set_diffnet_layer_bwd_bf16");

@@ -671,12 +671,8 @@ __global__ void __launch_bounds__(512 / NU, NU) diffnet_stack_x3_kernel(SetDiffn
 
 template <typename S, int NU, int NCB>
 int launch_x3(const SetDiffnetStackArgs &a, int n_cu, int fault_tile, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(diffnet_stack_x3_kernel<S, NU, NCB>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024), "set_diffnet_stack(x3 attr)");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 160 * 1024, "set_diffnet_stack(x3 attr)", diffnet_stack_x3_kernel<S, NU, NCB>)) return rc;
     const int Q = a.B * ((a.T + 31) / 32);                    // 32-frame column blocks of the batch
     const int ntiles = (Q + NCB - 1) / NCB, tiles_per_utt = ntiles;  // tiles are cut from the batch's block list (see X3Tile)
     const int64_t ntasks64 = (int64_t)ntiles * a.L;
@@ -1336,12 +1332,8 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
 
 template <int NB>
 int launch_x3v(const SetDiffnetStackArgs &a, int n_cu, int fault_tile, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(diffnet_stack_x3v_kernel<NB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-                "set_diffnet_stack(x3v attr)");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 160 * 1024, "set_diffnet_stack(x3v attr)", diffnet_stack_x3v_kernel<NB>)) return rc;
     const int Q = a.B * ((a.T + 31) / 32);
     const int ntiles = (Q + NB - 1) / NB;
     const int64_t ntasks64 = (int64_t)ntiles * a.L;
@@ -1692,25 +1684,17 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
 
 // called by set_diffnet_stack (csrc/diffnet.hip) for the row-split variant when two-piece fp16 images are given
 int set_launch_diffnet_stack_split_x2(const SetDiffnetStackArgs &a, int fault_tile, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(diffnet_stack_split_x2_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024), "set_diffnet_stack(split x2 attr)");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 80 * 1024, "set_diffnet_stack(split x2 attr)", diffnet_stack_split_x2_kernel)) return rc;
     const int tiles = (a.T + 31) / 32, nt = a.B * tiles;
     const int max_dil = 1 << (a.dilation_cycle_length - 1);
     const unsigned piece_bytes = (unsigned)((32 + 2 * max_dil) * XR);
     const size_t ldsz = (size_t)2 * piece_bytes + (64 * 32 + XC) * sizeof(float) + 16;
     SET_HIP(set_zero_async(a.sync_ws, (size_t)(4 + 2 * nt) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
     // 8 L2-warmer blocks (one per XCD) when the chip has CUs to spare and the block -> XCD round-robin lines them up with the parts
-    static int warm = -1, n_cu = 0;
-    if (warm < 0) {
-        warm = 1;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n_cu = 0;
-    }
-    const int extra = (warm && 4 * nt + 8 <= n_cu && a.L > 1) ? 8 : 0;  // (block q: XCD q % 8, part q & 3 = (q % 8) & 3 -- consistent)
+    int n_cu = 0;
+    (void)set_cu_count(&n_cu);  // (stays 0 when the query fails: no warmers)
+    const int extra = (4 * nt + 8 <= n_cu && a.L > 1) ? 8 : 0;  // (block q: XCD q % 8, part q & 3 = (q % 8) & 3 -- consistent)
     // agent-scope loads for the tiles other blocks produced instead of an acquire fence after each wait (measured in round 3 against
     // the fences: 62.7 -> 61.4 ms per 100 steps at B = 1, 66.9 -> 62.3 at B = 2 (T = 800), bit-identical either way)
     const int nofence = 1;

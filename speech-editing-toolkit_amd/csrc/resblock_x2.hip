@@ -359,12 +359,8 @@ int launch_pair(const SetResblockPairArgs &a, hipStream_t s) {
     const int NV = NB - 2 * h2;
     const size_t lds1 = (size_t)2 * (NB + 2 * h1) * RP_ROWB, lds2 = (size_t)2 * (NB + 2 * h2) * (CP * 2 + 16);
     const size_t lds = lds1 > lds2 ? lds1 : lds2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        SET_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(resblock_pair_x2_kernel<WM, WN, RBW, NCB>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024), "resblock pair attr");
-        attr_set = true;
-    }
+    static SetDeviceOnce lds_once;
+    if (int rc = set_lds_optin(lds_once, 96 * 1024, "resblock pair attr", resblock_pair_x2_kernel<WM, WN, RBW, NCB>)) return rc;
     if (lds > 96 * 1024) return set_fail(SET_E_UNSUPPORTED, "set_resblock_pair_x2", "tile does not fit LDS");
     dim3 grid((a.T + NV - 1) / NV, a.B), block(256);
     hipLaunchKernelGGL((resblock_pair_x2_kernel<WM, WN, RBW, NCB>), grid, block, lds, s, a, CP, NV);

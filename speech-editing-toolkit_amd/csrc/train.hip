@@ -1453,16 +1453,17 @@ extern "C" int set_scale_bcast(const float *a, const float *w, float *out, int64
                        scale_dev, scale);
     return set_check_launch("set_scale_bcast");
 }
+// c_gauss is per device: each device gets its own upload
 static int ssim_upload_window() {
-    static bool done = false;
-    if (done) return SET_OK;
-    // utils/metrics/ssim.py:12-14: gaussian(11, 1.5), computed in fp32 like torch.Tensor([...]) / sum
-    float g[11], s = 0.0f;
-    for (int x = 0; x < 11; ++x) { g[x] = (float)exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5)); s += g[x]; }
-    for (int x = 0; x < 11; ++x) g[x] /= s;
-    SET_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_gauss), g, sizeof(g)), "ssim window");
-    done = true;
-    return SET_OK;
+    static SetDeviceOnce once;
+    return once.run([] {
+        // utils/metrics/ssim.py:12-14: gaussian(11, 1.5), computed in fp32 like torch.Tensor([...]) / sum
+        float g[11], s = 0.0f;
+        for (int x = 0; x < 11; ++x) { g[x] = (float)exp(-(double)((x - 5) * (x - 5)) / (2.0 * 1.5 * 1.5)); s += g[x]; }
+        for (int x = 0; x < 11; ++x) g[x] /= s;
+        SET_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_gauss), g, sizeof(g)), "ssim window");
+        return SET_OK;
+    });
 }
 extern "C" int set_ssim_filter(const float *img1, const float *img2, float bias, float *mu1, float *mu2, float *s11,
                                float *s22, float *s12, int32_t B, int32_t H, int32_t W, void *stream) {

@@ -66,6 +66,20 @@ def test_no_oracle_import_in_product():
             assert "oracle" not in src.replace("# oracle", ""), fn
 
 
+def test_launch_state_is_set_up_per_device_in_common_h():
+    """LDS opt-ins, CU counts and constant uploads go through common.h (SetDeviceOnce, set_lds_optin, set_cu_count), once per
+    device: no source keeps a per-process flag or a device query of its own."""
+    csrc = os.path.join(ROOT, "speech-editing-toolkit_amd", "csrc")
+    for fn in sorted(os.listdir(csrc)):
+        if fn == "common.h" or not fn.endswith((".hip", ".h")):
+            continue
+        src = open(os.path.join(csrc, fn)).read()
+        for pat in ("attr_set", "hipFuncSetAttribute", "hipDeviceAttributeMultiprocessorCount", "hipGetDeviceProperties"):
+            assert pat not in src, (fn, pat)
+        flags = re.findall(r"^\s+static (?:bool|int) \w+ = ", src, flags=re.M)
+        assert not flags, (fn, flags)
+
+
 def test_state_dict_layout_matches_reference():
     from set_amd.diffnet import DiffNet
     from set_amd.hifigan import HifiGanGenerator

@@ -1528,6 +1528,45 @@ def test_x3v_shape_sweep_against_the_direct_form(dev, monkeypatch, form):
         assert _maxdiff(sw, sd) < 1e-5 * max(1.0, float(sd.abs().max())), (B, T, _maxdiff(sw, sd))
 
 
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs 2 GPUs")
+def test_second_device_computes_what_the_first_does(dev, monkeypatch):
+    """Launch-time state is set up once per device (csrc/common.h): the SSIM window in __constant__ memory, the LDS opt-ins of the x3v
+    stack kernel and the bf16 conv, the CU count behind the kernel choice.  The same seeded inputs on cuda:0 and then cuda:1 give the
+    same bits, SSIM backward (autograd's device thread) included."""
+    from set_amd import autograd_ops as A, ops
+    for k in ("SET_AMD_X3", "SET_AMD_SPLIT", "SET_AMD_WINO", "SET_AMD_SPLIT_OPERAND", "SET_AMD_STACK_NCB", "SET_AMD_X3_WINO",
+              "SET_AMD_X3_TILE", "SET_AMD_STACK_GRID"):
+        monkeypatch.delenv(k, raising=False)
+
+    def run(d):
+        out = {}
+        with torch.cuda.device(d):
+            g = torch.Generator().manual_seed(7)
+            pred = (torch.randn(3, 60, 80, generator=g) * 0.5 - 3.0).to(d).requires_grad_(True)
+            target = torch.clamp(torch.randn(3, 60, 80, generator=g) * 1.5 - 3.0, -6, 1.5).to(d)
+            with torch.enable_grad():
+                loss = A.ssim_loss(pred, target, A.frame_weights(target))
+                loss.backward()
+            out["ssim"], out["ssim_grad"] = loss.detach(), pred.grad
+            assert ops.stack_x3_winograd(32, 800, 1) == 3  # the x3v kernel, 96-frame tiles
+            x0, cp, dtab, packs, *_ = _random_stack(d, 32, 800, 4, 41, 2)
+            xa, xb, skip = x0.clone(), torch.full_like(x0, float("nan")), torch.full_like(x0, float("nan"))
+            ws = ops.diffnet_stack(xa, xb, skip, cp, dtab.data_ptr() + 4, 0, 3, 256 * 3, packs, 1)
+            out["stack_x"], out["stack_skip"] = xa, skip
+            x = torch.randn(2, 256, 300, generator=g).to(d)
+            wd = (torch.randn(512, 256, 3, generator=g) / 27.7).to(d)
+            cw = ops.ConvWeight(lambda: wd, 512, 256, 3)
+            out["conv_bf16"] = ops.conv1d(x, cw, torch.randn(512, generator=g).to(d), pad=1,
+                                          in_chan_add=torch.randn(2, 256, generator=g).to(d), impl="bf16")
+            torch.cuda.synchronize()
+            assert int(ws[1]) == 0, "dependency wait timed out"
+        return {k: v.cpu() for k, v in out.items()}
+
+    first, second = run(torch.device("cuda:0")), run(torch.device("cuda:1"))
+    for k in first:
+        assert torch.equal(first[k], second[k]), k
+
+
 @pytest.mark.parametrize("form", ["2", "3"])
 @pytest.mark.parametrize("case", ["infer_full800", "infer_tiny", "infer_pad", "infer_ragged", "infer_drift100"])
 def test_full_inference_matches_reference_with_x3v_forced(dev, monkeypatch, case, form):
