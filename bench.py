@@ -1,7 +1,7 @@
 """Headline benchmark: diffusion mel-frames/s of one full GaussianDiffusion.forward(infer=True)
 (conditioner once + 100 x (DiffNet + posterior step)) at B=32 per GPU, T=800, fp32.
 
-  python bench.py --gpus N --steps K --warmup W [--mode infer|train] [--dtype f32|bf16] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--mode infer|train] [--dtype f32|bf16] [--dump-outputs DIR] [--full]
 
 With N > 1 and no WORLD_SIZE in the environment the script re-launches itself as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...`
@@ -17,8 +17,13 @@ One "step" = one pass of the hot path over one synthetic batch.
       set-up; reports samples/s, all-reduce bytes per step and the exposed (not hidden by backward) exchange time.
 Timing = barrier + synchronize on both sides, MAX over ranks.  Rank 0 prints ONE JSON line with the contract fields plus
 `roofline` (dominant kernel = the persistent DiffNet layer-stack kernel, one launch = all 20 residual layers of one
-denoise step, measured with hipEvents on the launch stream inside the timed region) and, at N=1, `cpu_baseline` (the CPU
-oracle = a port of the reference's torch-CPU path, timed on bounded samples: SURVEY.md 8(d)'s protocol).
+denoise step, measured with hipEvents on the launch stream inside the timed region).
+
+A plain run does only that: set up, warm up, time the steps, write --dump-outputs, print the line.  --full adds what
+takes runs of its own: in --mode infer at N=1 the quality against the CPU oracle, the same loop on the other operand
+paths, `cpu_baseline` (the CPU oracle = a port of the reference's torch-CPU path, timed on bounded samples: SURVEY.md
+8(d)'s protocol) and the other BASELINE configs in sub-processes; in --mode train the dominant kernel's `roofline` over
+5 extra steps.  The --no-* options drop single parts of --full.
 """
 import argparse
 import json
@@ -519,7 +524,7 @@ def run_infer(args, rank, world, dev):
             traffic_note = "PMC passes of this kernel build (%s, source sha256 matches)" % tname
         else:
             traffic_note = "withheld: the kernel sources changed since the PMC passes in %s" % tname
-    extras = rank == 0 and world == 1 and not stub  # the comparison lines and sub-benchmarks of the 1-GPU default run
+    extras = args.full and rank == 0 and world == 1 and not stub  # the comparison lines and sub-benchmarks of a 1-GPU --full run
     out = {
         "metric": "diffusion mel-frames/s (100-step p_sample, B=32/GPU, T=800)" if not stub else
                   "STUB (toy torch-CPU model over gloo: exercises bench.py's launch / sharding / timing path, measures nothing of this framework)",
@@ -663,8 +668,8 @@ def _sub_bench(argv, timeout=420):
 
 def train_line(model, dtype):
     """BASELINE configs[1] (spec_denoiser, B=32, T=800, bf16) / configs[4] per GPU (CampNet, B=16, T=800): `bench.py --mode train` in a
-    sub-process."""
-    d = _sub_bench(["--mode", "train", "--model", model, "--dtype", dtype, "--steps", "20", "--warmup", "5"])
+    sub-process, with --full for its dominant kernel's roofline."""
+    d = _sub_bench(["--mode", "train", "--model", model, "--dtype", dtype, "--steps", "20", "--warmup", "5", "--full"])
     if "error" in d:
         return d
     out = {"metric": d["metric"], "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "dtype": d["dtype"],
@@ -1038,7 +1043,7 @@ def run_train(args, rank, world, dev):
         torch.distributed.all_reduce(hi, op=torch.distributed.ReduceOp.MAX)
         same_after = float(lo) == float(hi)
         assert same_after, "the replicas diverged during the timed steps"
-    dominant = None if stub_device() else _train_dominant_kernel(args, step_fn, sample, dev, bpg)
+    dominant = _train_dominant_kernel(args, step_fn, sample, dev, bpg) if args.full and not stub_device() else None
     n_samples = bpg * world * args.steps
     flop = (CAMPNET_TRAIN_FLOP_PER_FRAME if campnet else TRAIN_FLOP_PER_FRAME) * bpg * T * args.steps  # per rank
     peak = PEAK_BF16_MFMA_TFLOPS if args.dtype == "bf16" else PEAK_F32_MFMA_TFLOPS
@@ -1074,7 +1079,8 @@ def run_train(args, rank, world, dev):
         "param_broadcast_bytes": bcast_bytes, "grad_elems": opt.n, "grad_elems_exchanged": opt.n_exchanged,
         "loss": float(total), "lr": lr, "losses": {k: float(v) for k, v in parts.items()},
         # roofline = the step's dominant kernel (largest share of the GPU time; hipEvents on its launch stream over extra steps right
-        # behind the timed ones -- inside them, the ~100 event records per step would cost the step itself 0.4 ms of host time);
+        # behind the timed ones -- inside them, the ~100 event records per step would cost the step itself 0.4 ms of host time; --full
+        # only, None otherwise);
         # whole_step = the algorithmic FLOPs of the step over the step time
         "roofline": dominant,
         "whole_step": None if stub_device() else {"bound": "mfma", "achieved": ach, "peak": peak, "unit": "TFLOP/s", "frac": ach / peak,
@@ -1091,13 +1097,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--mode", choices=("infer", "train"), default="infer")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32", help="train mode only: MFMA operand type")
-    ap.add_argument("--cpu-baseline", choices=("full", "quick", "off"), default="full")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: infer at N=1 adds the quality against the CPU "
+                         "oracle, the other operand paths of the loop, the CPU baseline and the other BASELINE configs; train adds the "
+                         "dominant kernel's roofline over 5 extra steps")
+    ap.add_argument("--cpu-baseline", choices=("full", "quick", "off"), default="full", help="with --full: the CPU baseline's protocol")
     ap.add_argument("--no-cpu-baseline", action="store_const", const="off", dest="cpu_baseline")
-    ap.add_argument("--no-native-fp32", action="store_true", help="skip the fp32-MFMA-pipe comparison run of the same loop")
-    ap.add_argument("--no-bf16-loop", action="store_true", help="skip the extra (non-headline) bf16-operand loop line")
-    ap.add_argument("--no-bf16x3-loop", action="store_true", help="skip the exact three-piece splitting of the same loop")
-    ap.add_argument("--no-quality", action="store_true", help="skip the MCD / max |dmel| of the shipped path against the CPU oracle")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the sub-benchmarks of BASELINE configs[1], [3], [4] (sub-processes)")
+    ap.add_argument("--no-native-fp32", action="store_true", help="with --full: skip the fp32-MFMA-pipe comparison run of the same loop")
+    ap.add_argument("--no-bf16-loop", action="store_true", help="with --full: skip the extra (non-headline) bf16-operand loop line")
+    ap.add_argument("--no-bf16x3-loop", action="store_true", help="with --full: skip the exact three-piece splitting of the same loop")
+    ap.add_argument("--no-quality", action="store_true", help="with --full: skip the MCD / max |dmel| of the shipped path against the CPU oracle")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="with --full: skip the sub-benchmarks of BASELINE configs[1], [3], [4] (sub-processes)")
     ap.add_argument("--model", choices=("spec_denoiser", "campnet"), default="spec_denoiser",
                     help="train mode only: campnet = BASELINE configs[4] (B=16/GPU, T=800)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,

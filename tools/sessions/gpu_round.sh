@@ -11,7 +11,7 @@ timeout 900 python -m pytest tests -q -m gpu -p no:cacheprovider ${PYTEST_ARGS:-
 echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $OUT/smoke.log
 echo "== bench"
-timeout 600 python bench.py --gpus 1 --steps ${BENCH_STEPS:-3} --warmup 1 2>&1 | tail -1 | tee $OUT/bench.log
+timeout 600 python bench.py --gpus 1 --steps ${BENCH_STEPS:-3} --warmup 1 --full 2>&1 | tail -1 | tee $OUT/bench.log
 echo "== rocprofv3 kernel trace"
 rm -rf $OUT/prof
 ( cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$OUT/prof" -o trace -- python "$OLDPWD/bench.py" --gpus 1 --steps 1 --warmup 0 --no-cpu-baseline > "$OLDPWD/$OUT/rocprof_bench.log" 2>&1 )
