@@ -585,7 +585,7 @@ def mha(W, p, query, key, n_heads, key_padding_mask=None, fill=float("-inf")):
     s = torch.bmm(q, k.transpose(1, 2))
     if key_padding_mask is not None:
         s = s.view(B, n_heads, Tq, Tk).masked_fill(key_padding_mask[:, None, None, :], fill).view(B * n_heads, Tq, Tk)
-    pr = F.softmax(s, dim=-1, dtype=torch.float32)
+    pr = F.softmax(s, dim=-1, dtype=torch.promote_types(s.dtype, torch.float32))  # fp32 at least (fp64 under an fp64 evaluation)
     o = torch.bmm(pr, v).transpose(0, 1).contiguous().view(Tq, B, H)
     return F.linear(o, W[p + "out_proj.weight"]), pr.view(B, n_heads, Tq, Tk)
 
@@ -745,7 +745,7 @@ def l1_loss(pred, target):
 def _ssim_map(img1, img2, window_size=11, sigma=1.5):
     g = torch.tensor([math.exp(-(x - window_size // 2) ** 2 / float(2 * sigma ** 2)) for x in range(window_size)])
     g = (g / g.sum()).unsqueeze(1)
-    window = g.mm(g.t()).float()[None, None]
+    window = g.mm(g.t()).float().to(img1.dtype)[None, None]  # the fp32 window, also under an fp64 evaluation
     p = window_size // 2
     mu1, mu2 = F.conv2d(img1, window, padding=p), F.conv2d(img2, window, padding=p)
     mu1_sq, mu2_sq, mu12 = mu1.pow(2), mu2.pow(2), mu1 * mu2
@@ -765,7 +765,7 @@ def ssim_loss(pred, target, bias=6.0):
 def dur_losses(dur_pred, mel2ph, txt_tokens, sil_ids, lam_p, lam_w):
     B, T = txt_tokens.shape
     nonpad = (txt_tokens != 0).float()
-    dur_gt = mel2token_to_dur(mel2ph, T).float() * nonpad
+    dur_gt = mel2token_to_dur(mel2ph, T).to(dur_pred.dtype) * nonpad
     is_sil = torch.zeros_like(txt_tokens).bool()
     for i in sil_ids:
         is_sil = is_sil | (txt_tokens == i)
