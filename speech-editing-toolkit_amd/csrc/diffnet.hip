@@ -518,11 +518,7 @@ __device__ __forceinline__ void wino_main(const LayerTile &a, f32x16 (&m)[2][4],
                     const float v = (rb == 1 && first) ? acc[rb][cb][r] : acc[rb][cb][r] + prev[rb][cb][r];
                     // agent-scope write-through (sc1): once vmcnt drains, the tile is visible to every XCD, so the
                     // publish needs no L2 write-back (a release fence = buffer_wbl2 of the whole XCD L2: -5 %)
-#ifdef SET_WINO_FENCED
-                    buf_store(v * (rb == 0 ? 0.70710678118654752440f : 1.0f), rb == 0 ? rxout : rskp, so, ur * T4);
-#else
                     buf_store_agent(v * (rb == 0 ? 0.70710678118654752440f : 1.0f), rb == 0 ? rxout : rskp, so, ur * T4);
-#endif
                 }
         }
     }
@@ -533,13 +529,7 @@ __device__ __forceinline__ void wino_main(const LayerTile &a, f32x16 (&m)[2][4],
 // ---- persistent layer stack: (layer, tile) task queue + per-tile epoch flags -----------------------------------
 // Inter-workgroup hand-off follows cdna_hip_programming.md Guideline 16: producer = every wave drains vmcnt,
 // __syncthreads, ONE lane agent-scope release fence + asm vmcnt(0) + relaxed agent flag store; consumer = ONE lane
-// polls relaxed, ONE agent-scope acquire, __syncthreads, then plain loads.  Every spin is bounded.
-constexpr unsigned STACK_SPIN_LIMIT = 1u << 22;  // x s_sleep(8) ~ 1 s
-
-__device__ __forceinline__ int ld_agent(const int *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
+// polls relaxed, ONE agent-scope acquire, __syncthreads, then plain loads.  Every spin is bounded (ld_agent, STACK_SPIN_LIMIT: common.h).
 template <int NCB, int GS, int WPS>
 __global__ void __launch_bounds__(256, WPS) diffnet_stack_kernel(SetDiffnetStackArgs a, int tiles_per_utt, int ntiles,
                                                                 int ntasks, int task_slot) {
@@ -628,7 +618,6 @@ __global__ void __launch_bounds__(256, WPS) diffnet_stack_kernel(SetDiffnetStack
 // ([16][KS][64], set_diffnet_stack's w1s_all / w2s_all).
 constexpr int SP_XW = 32 + 2 * WN_MAXD;      // widest x tile (d = 8)
 constexpr int SP_LDS_FLOATS = DC * SP_XW + 64 * 32 + 4;
-constexpr unsigned SP_SPIN_LIMIT = 1u << 20;  // polls of ~1 us each (two agent-scope loads + s_sleep(1)): ~1-2 s
 
 // GEMM of the row-split kernel: ONE 32x32 accumulator per wave, so one MFMA (64 cycles) per k-step and nothing else in
 // the wave to hide operand latency behind.  The weight images are cold in L2 at every layer (2 MiB per layer, read once per
@@ -686,7 +675,7 @@ __device__ __forceinline__ bool split_wait(const int *f0, const int *f1, const i
         const int v0 = ld_agent(f0), v1 = ld_agent(f1), v2 = ld_agent(f2);
         if (min(v0, min(v1, v2)) >= want) break;
         __builtin_amdgcn_s_sleep(1);
-        if (++spins > SP_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
+        if (++spins > SPLIT_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
             __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (err_flag) __hip_atomic_store(err_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return false;
@@ -921,10 +910,7 @@ __global__ void __launch_bounds__(512, 2) diffnet_stack_wino_kernel(SetDiffnetSt
 #endif
         if (tid == 0 && i_done >= 0) {
             const uint64_t tf0 = __builtin_amdgcn_s_memtime();
-#ifdef SET_WINO_FENCED
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
+            // no release fence: the tile's stores are agent-scope write-through (wino_main's epilogue), drained above
             // (fault_tile >= 0: test hook, SET_AMD_FAULT_TILE -- that tile of layer 0 is never published, so its
             // consumers must run into the spin limit and the launch must report it)
             if (!(l_done == 0 && i_done == fault_tile))

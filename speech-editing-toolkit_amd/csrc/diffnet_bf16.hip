@@ -837,9 +837,8 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
 // =====================================================================================================================
 // acc[NRB][4] += A B over NKS k-steps in groups of 4 with the pinned schedule of gemm_reg_run; ring A[4 D][NRB].
 // aoff(ks, rb): wave-uniform byte offset of the fragment block; avo: per-lane byte offset inside it.
-#ifndef SET_T128_EXP
-#define SET_T128_EXP 0
-#endif
+// (What each operand stream of the layer costs -- weight refills, B-fragment reads, skip traffic -- was measured with builds that drop it,
+// results wrong by construction: profiles/r04_t128_exp.log.)
 template <int NRB, int NKS, int D, bool TOGGLE, bool BDB, typename AO, typename BG>
 __device__ __forceinline__ void gemm_t128_run(f32x16 (&acc)[NRB][4], u32x4_t (&A)[4 * D][NRB], rsrc_t img, unsigned avo, AO aoff,
                                               const unsigned char *lds, BG bgrp) {
@@ -859,13 +858,6 @@ __device__ __forceinline__ void gemm_t128_run(f32x16 (&acc)[NRB][4], u32x4_t (&A
         if (BDB && more) bgrp(kb + 4, n0, ns);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-#if (SET_T128_EXP & 2)  // measurement build (tools/build_exp.sh): no B-fragment reads after the first k-step (results are wrong)
-            if (kb == 0 && p == 0) {
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) Bq[0][cb] = *reinterpret_cast<const u32x4_t *>(lds + b0 + cb * bs);
-                if (BDB) { for (int cb = 0; cb < 4; ++cb) Bq[1][cb] = Bq[0][cb]; }
-            }
-#else
             if (!BDB) {
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) Bq[0][cb] = *reinterpret_cast<const u32x4_t *>(lds + b0 + cb * bs + 32 * p);
@@ -876,7 +868,6 @@ __device__ __forceinline__ void gemm_t128_run(f32x16 (&acc)[NRB][4], u32x4_t (&A
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) Bq[0][cb] = *reinterpret_cast<const u32x4_t *>(lds + n0 + cb * ns);
             }
-#endif
             __builtin_amdgcn_sched_barrier(0);
             if (TOGGLE) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -884,12 +875,10 @@ __device__ __forceinline__ void gemm_t128_run(f32x16 (&acc)[NRB][4], u32x4_t (&A
 #pragma unroll
                 for (int cb = 0; cb < 4; ++cb) acc[rb][cb] = mma16(A[4 * slot + p][rb], Bq[BDB ? (p & 1) : 0][cb], acc[rb][cb]);
             if (TOGGLE) __builtin_amdgcn_s_setprio(0);
-#if !(SET_T128_EXP & 1)  // measurement build: bit 0 = no weight-fragment refills (results are wrong)
             if (refill) {
 #pragma unroll
                 for (int rb = 0; rb < NRB; ++rb) A[4 * slot + p][rb] = buf_load_u4(img, avo, aoff(kb + p + 4 * D, rb));
             }
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -1097,8 +1086,8 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
         // layer of the group unless it is the first of the network, from the private copy afterwards) and the first weight fragments are
         // requested here: they travel while this wave waits for the others and through the skip pass
         gemm_t128_prefetch<1, 4 * D2>(A2, rw2, lane16, aoff2r(1));
-        const bool sk_zero = (SET_T128_EXP & 4) ? true : (a.first != 0 && m == 0);  // measurement build bit 2: no skip traffic between the layers
-        if (m == 0 || (SET_T128_EXP & 4)) {
+        const bool sk_zero = a.first != 0 && m == 0;
+        if (m == 0) {
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -1109,7 +1098,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
                 if (st[cb]) {  // the frames this block stores: the others never leave the tile
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
-                        const f32x4 v = (SET_T128_EXP & 8) ? buf_load4(rps, lane16, (unsigned)((cb * 4 + g4) * 1024)) : buf_load4_stream(rps, lane16, (unsigned)((cb * 4 + g4) * 1024));
+                        const f32x4 v = buf_load4_stream(rps, lane16, (unsigned)((cb * 4 + g4) * 1024));
 #pragma unroll
                         for (int e = 0; e < 4; ++e) sko[cb][4 * g4 + e] = v[e];
                     }
@@ -1153,17 +1142,15 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
                 for (int cb = 0; cb < NSKR; ++cb)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) sko[cb][r] = acc[0][cb][r] + sko[cb][r];
-                if (!(SET_T128_EXP & 4)) {
 #pragma unroll
-                    for (int cb = NSKR; cb < NCB; ++cb) {
-                        if (st[cb]) {
+                for (int cb = NSKR; cb < NCB; ++cb) {
+                    if (st[cb]) {
 #pragma unroll
-                            for (int g4 = 0; g4 < 4; ++g4) {
-                                f32x4 v;
+                        for (int g4 = 0; g4 < 4; ++g4) {
+                            f32x4 v;
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) v[e] = acc[0][cb][4 * g4 + e] + sko[cb][4 * g4 + e];
-                                if (SET_T128_EXP & 8) buf_store4(v, rps, lane16, (unsigned)((cb * 4 + g4) * 1024)); else buf_store4_stream(v, rps, lane16, (unsigned)((cb * 4 + g4) * 1024));
-                            }
+                            for (int e = 0; e < 4; ++e) v[e] = acc[0][cb][4 * g4 + e] + sko[cb][4 * g4 + e];
+                            buf_store4_stream(v, rps, lane16, (unsigned)((cb * 4 + g4) * 1024));
                         }
                     }
                 }

@@ -36,12 +36,6 @@
 
 #include "common.h"
 
-// measurement builds only (tools/build_exp.sh): bit 0 = the A fragments are loaded once per GEMM (no L2 operand stream), bit 1 =
-// every k-step reads the B fragment of k-step 0 (the compiler hoists it: no LDS stream), bit 2 = no s_setprio.  WRONG RESULTS.
-#ifndef SET_X3_EXP
-#define SET_X3_EXP 0
-#endif
-
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
@@ -69,7 +63,6 @@ constexpr int XR = XC * 2 + 16;    // bytes per LDS row
 constexpr int X_KS1 = 48;          // k-steps of GEMM 1 (3 taps x 16)
 constexpr int X_KS2 = 16;          // k-steps of GEMM 2
 constexpr float RSQRT2 = 0.70710678118654752440f;
-constexpr unsigned X_SPIN_LIMIT = 1u << 22;
 
 __device__ __forceinline__ unsigned short f2bf(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
 __device__ __forceinline__ float bf2f(unsigned short u) { return __builtin_bit_cast(float, (unsigned)u << 16); }
@@ -126,13 +119,10 @@ __device__ __forceinline__ float fsig(float x) { return __builtin_amdgcn_rcpf(1.
 __device__ __forceinline__ float ftanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
 __device__ __forceinline__ int urow(int r) { return (r & 3) + 8 * (r >> 2); }  // + 4 * (lane >> 5)
 // read-once streams (the conditioner projection, the running skip sum): nt = evict-first at the L2, which the layer images live in
-#ifndef SET_X3W_NT
-#define SET_X3W_NT 1  // measured (round 6, profiles/r06_x3w_nt_ab.log): 1.664 against 1.688 ms per launch; 0 = plain loads
-#endif
+constexpr int X_NT = 2;  // cache policy bit nt; measured (round 6, profiles/r06_x3w_nt_ab.log): 1.664 against 1.688 ms per launch with plain loads
 __device__ __forceinline__ float buf_load_nt(rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, SET_X3W_NT ? 2 : 0));
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, X_NT));
 }
-__device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ---- weight images --------------------------------------------------------------------------------------------------
 // lane l of a fragment holds row (l & 31), k = 8 (l >> 5) + e, e < 8:
@@ -194,7 +184,9 @@ __global__ void __launch_bounds__(256) pack_layer_x3_kernel(const float *wdil, c
 //   A: image block of (w8, ks, rb, piece) at byte offset abase + u * ustride + ((ks * 2 + rb) * NP + piece) * 1024 (+ lane * 16)
 //   B: piece q of this lane's fragment for (ks, cb) at lds + q * piece_bytes + bfrag(ks, cb)
 //   PF: A prefetch distance in k-steps.  Every accumulator sees its products in the same order whatever NU is.
-template <typename S, int NKS, int NU, int NCB, int PF, int SLP = 0, typename BF>
+// (Round 3 measured this loop without its A stream, without its B stream and without s_setprio, results wrong by construction:
+// profiles/r03_x3_pair_probe.log.)
+template <typename S, int NKS, int NU, int NCB, int PF, typename BF>
 __device__ __forceinline__ void gemm_x3(f32x16 (&acc)[NU][2][NCB], rsrc_t img, unsigned lane16, unsigned abase, unsigned ustride,
                                         const unsigned char *lds, unsigned piece_bytes, BF bfrag) {
     constexpr int NP = S::NP;
@@ -216,7 +208,7 @@ __device__ __forceinline__ void gemm_x3(f32x16 (&acc)[NU][2][NCB], rsrc_t img, u
             u32x4_t Bv[NCB][NP];
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
-                const unsigned bo = bfrag((SET_X3_EXP & 2) ? 0 : ks, cb);  // (experiment 2: no B stream)
+                const unsigned bo = bfrag(ks, cb);
 #pragma unroll
                 for (int q = 0; q < NP; ++q) Bv[cb][q] = *reinterpret_cast<const u32x4_t *>(lds + q * piece_bytes + bo);
             }
@@ -224,8 +216,7 @@ __device__ __forceinline__ void gemm_x3(f32x16 (&acc)[NU][2][NCB], rsrc_t img, u
             // (Copying the slot to temporaries and refilling it BEFORE the MFMAs -- the earlier form -- made the compiler rotate the ring
             // through v_mov chains behind s_waitcnt vmcnt(0) at the end of every PF k-steps: the ring drained once per loop iteration.)
             __builtin_amdgcn_sched_barrier(0);
-            if (SLP) __builtin_amdgcn_s_sleep(SLP);  // (x3v: the wave's own rate cap, see SET_X3V_SLEEP)
-            if (!(SET_X3_EXP & 4)) __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(1);
             // the accumulators interleave, so consecutive MFMAs never depend on each other
 #pragma unroll
             for (int t = 0; t < S::NPROD; ++t)
@@ -236,8 +227,8 @@ __device__ __forceinline__ void gemm_x3(f32x16 (&acc)[NU][2][NCB], rsrc_t img, u
 #pragma unroll
                         for (int cb = 0; cb < NCB; ++cb)
                             acc[u][rb][cb] = S::mma(A[p][u][rb][S::qa(t)], Bv[cb][S::qb(t)], acc[u][rb][cb]);
-            if (!(SET_X3_EXP & 4)) __builtin_amdgcn_s_setprio(0);
-            const int kn = (SET_X3_EXP & 1) ? p : min(ks + PF, NKS - 1);  // tail: harmless re-load of the last k-step (experiment 1: no A stream)
+            __builtin_amdgcn_s_setprio(0);
+            const int kn = min(ks + PF, NKS - 1);  // tail: harmless re-load of the last k-step
 #pragma unroll
             for (int u = 0; u < NU; ++u)
 #pragma unroll
@@ -452,7 +443,7 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
     X3_PHASE(1)
 
     // ---- GEMM 1: y = Wdil (*) (x + d); k-step ks -> tap ks / 16 (a row shift of tap * d), channels 16 (ks % 16) ..
-    gemm_x3<S, X_KS1, NU, NCB, (NU == 1 ? S::PF : S::PF2), 0>(
+    gemm_x3<S, X_KS1, NU, NCB, (NU == 1 ? S::PF : S::PF2)>(
         acc, rw, lane16, (unsigned)(NU * w * X_KS1 * 2 * NP * 1024), (unsigned)(X_KS1 * 2 * NP * 1024), lds, piece_bytes, [&](int ks, int cb) {
             return (unsigned)((cb * RB + l31 + (ks >> 4) * d) * XR + ((ks & 15) * 16 + half * 8) * 2);
         });
@@ -535,7 +526,7 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
     X3_PHASE(3)
 
     // ---- GEMM 2: o = Wout z
-    gemm_x3<S, X_KS2, NU, NCB, (NU == 1 ? S::PF : S::PF2), 0>(
+    gemm_x3<S, X_KS2, NU, NCB, (NU == 1 ? S::PF : S::PF2)>(
         acc, rw, lane16, (unsigned)(x_n1<S>() * 2 + NU * w * X_KS2 * 2 * NP * 1024), (unsigned)(X_KS2 * 2 * NP * 1024), lds, piece_bytes,
         [&](int ks, int cb) { return (unsigned)((cb * 32 + l31) * XR + (ks * 16 + half * 8) * 2); });
     X3_PHASE(4)
@@ -637,7 +628,7 @@ __global__ void __launch_bounds__(512 / NU, NU) diffnet_stack_x3_kernel(SetDiffn
                     const int v0 = ld_agent(f0), v1 = ld_agent(fl), v2 = ld_agent(fr);
                     if (min(v0, min(v1, v2)) >= l) break;
                     __builtin_amdgcn_s_sleep(8);
-                    if (++spins > X_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
+                    if (++spins > STACK_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
                         __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if (a.err_flag) __hip_atomic_store(a.err_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         ok = 0;
@@ -716,7 +707,7 @@ __device__ __forceinline__ f32x2 buf_load2(rsrc_t r, unsigned voff, unsigned sof
 }
 // (measured and not kept: the epilogue's write-through stores as nt stores too -- 1.719 against 1.659 ms per launch, profiles/r06_x3w_nt_ab.log)
 __device__ __forceinline__ f32x2 buf_load2_nt(rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, SET_X3W_NT ? 2 : 0));
+    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, X_NT));
 }
 // Measured on the first form and not kept (round 6): touching the NEXT task's conditioner-projection rows under GEMM 2 (1.669 against 1.650 ms,
 // profiles/r06_x3w_prefetch_ab.log); XCD-aware task claiming -- the blocks of one XCD (blockIdx.x % 8) taking their tasks from a chunk of
@@ -745,7 +736,8 @@ __device__ __forceinline__ f32x2 buf_load2_nt(rsrc_t r, unsigned voff, unsigned 
 // Measured and not kept: 128-frame tiles (NB = 4; 15 spilled registers) at B = 64 / 48, where every CU has a chain of them: +0.2 / -0.3 %
 // (profiles/r06_x3v_nb4_ab.log) -- beyond 96 frames the weight-fragment stream is no longer what the time follows; GEMM 2 on the 16-wide
 // instruction in its transposed form (lane = one output row at four consecutive frames): -19 % with 8-byte, -3 % with 16-byte epilogue accesses
-// (half-line accesses; profiles/r06_x3v_gemm2_16wide_ab.log); skip rows fetched before GEMM 2 / a 4-deep GEMM 2 ring: +-0.3 %.
+// (half-line accesses; profiles/r06_x3v_gemm2_16wide_ab.log); skip rows fetched before GEMM 2 / a 4-deep GEMM 2 ring: +-0.3 %
+// (profiles/r06_x3v_pf2_skearly_ab2.log).
 // Per-task timeline (tools/x3_timeline_probe.py, profiles/r06_x3v_timeline.log; 68 us per task at B = 32, T = 800): the two waves of a SIMD do not share
 // the matrix pipe evenly -- the older one (waves 0-3) finishes every GEMM pass ~4 us before the younger one and runs ~10 us ahead at the task boundary,
 // so its epilogue and next accumulator-start loads run under the younger waves' GEMM 2 (17 us against 9.4 us of MFMA issue: the younger wave alone is
@@ -764,40 +756,14 @@ __device__ __forceinline__ f32x2 buf_load2_nt(rsrc_t r, unsigned voff, unsigned 
 // rows {0-3, 12-15} of one k group with rows 4-11 of the next: with the 528-byte rows of the other tiles (16-byte quads 1 apart per row) two of
 // its lanes share a bank (PMC: SQ_LDS_BANK_CONFLICT 41 % of SQ_LDS_IDX_ACTIVE, profiles/r06_pmc_x3_lds.log); with quads 2 apart per row none do.
 // The z tile keeps 528-byte rows -- GEMM 2 reads it with the 32-wide layout, for which odd quad distances are the conflict-free ones.
-#ifndef SET_X3V_XRV
-#define SET_X3V_XRV (XC * 2 + 32)
-#endif
-constexpr int XRV = SET_X3V_XRV;
+constexpr int XRV = XC * 2 + 32;
 template <int NB> constexpr unsigned xv_piece() { return 16 * NB * XRV; }     // one piece of one plane of the V tile (16 NB pair rows)
 template <int NB> constexpr unsigned xv_plane() { return 2 * xv_piece<NB>(); }
 template <int NB> constexpr unsigned xv_zpiece() { return 32 * NB * XR; }     // one piece of the z tile (32 NB frame rows), which overlays the V tile
 template <int NB> constexpr unsigned xv_tile() { return 2 * xv_plane<NB>() > 2 * xv_zpiece<NB>() ? 2 * xv_plane<NB>() : 2 * xv_zpiece<NB>(); }  // NB = 3: 104,448 bytes
-#ifndef SET_X3V_PF
-#define SET_X3V_PF 2                              // fragment ring depth of GEMM 1 in k-steps of 32 (8 fragments = 32 registers each)
-#endif
-#ifndef SET_X3V_PF2
-#define SET_X3V_PF2 2                             // fragment ring depth of GEMM 2 in k-steps of 16
-#endif
-#ifndef SET_X3V_WAVE_PUBLISH
-#define SET_X3V_WAVE_PUBLISH 1                    // 1 = every wave publishes its part of a finished tile (flag = waves done, 8 per layer); 0 = one store per block behind a barrier
-#endif
-#define X3V_FLAG_UNIT (SET_X3V_WAVE_PUBLISH ? 8 : 1)
-#ifndef X3V_LEAD
-#define X3V_LEAD 0                                // the thread that claims the next task and looks at the dependency flags.  Lane 0 of wave 7 (448) -- one of the
-#endif                                            // waves that reach the task boundary last, so its look is the freshest (spins in 51 of 256 tasks instead of 242)
-                                                  // -- waits for its claim behind its own 48 accumulator-start loads: +2.3 us per task (profiles/r06_x3v_e_ab.log)
-#ifndef SET_X3V_GATE2
-#define SET_X3V_GATE2 1                           // gate as one quotient (3 transcendentals per value) instead of sigmoid x tanh (4)
-#endif
-#ifndef SET_X3V_SLEEP
-#define SET_X3V_SLEEP 0                           // s_sleep argument (x 64 clocks) in front of every k-step's MFMA burst of GEMM 1 (36 MFMAs = 576 clocks)
-#endif
-#ifndef SET_X3V_SLEEP2
-#define SET_X3V_SLEEP2 0                          // same for GEMM 2 (18 MFMAs of 32 clocks)
-#endif
-#ifndef SET_X3V_SK_EARLY
-#define SET_X3V_SK_EARLY 0                        // 1 = the running skip rows are fetched before GEMM 2 (48 more live registers through it)
-#endif
+constexpr int XV_PF = 2;          // fragment ring depth of GEMM 1 in k-steps of 32 (8 fragments = 32 registers each)
+constexpr int XV_PF2 = 2;         // fragment ring depth of GEMM 2 in k-steps of 16
+constexpr int X3V_FLAG_UNIT = 8;  // every wave publishes its part of a finished tile: a tile's flag counts waves done, 8 per layer
 
 __device__ __forceinline__ f32x4 mma16(u32x4_t a, u32x4_t b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
@@ -942,7 +908,6 @@ __device__ __forceinline__ void x3v_plane(f32x4 (&acc)[4][NB], u32x4_t (&A)[PFV]
 #pragma unroll
                 for (int q = 0; q < 2; ++q) Bv[nb][q] = *reinterpret_cast<const u32x4_t *>(bplane + q * xv_piece<NB>() + boff + (unsigned)(nb * 16 * XRV) + (unsigned)kc * 64u);
             __builtin_amdgcn_sched_barrier(0);
-            if (SET_X3V_SLEEP) __builtin_amdgcn_s_sleep(SET_X3V_SLEEP);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int t = 0; t < S::NPROD; ++t)
@@ -987,7 +952,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
 #endif
     X3V_PHASE(0)
     typedef SplitF16x2 S;
-    constexpr int PFV = SET_X3V_PF;
+    constexpr int PFV = XV_PF;
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));
     const int lane = tid & 63;
@@ -1003,7 +968,6 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
     const float s2 = sc[2], is2 = sc[3];
     const float is1w = reinterpret_cast<const float *>(a.img + x_nimg<S>() - 8)[1];
     const float cg2 = is1w * -1.4426950408889634f, cf2 = is1w * 2.8853900817779268f;  // (is1w: a power of two)
-    (void)cg2; (void)cf2;
     // (dsh: staged by the kernel's task loop in front of the dependency wait -- the offsets depend on nothing the layer below wrote)
     // ---- GEMM 1, first pair of planes
     const unsigned abase = (unsigned)((x_n1<S>() + x_n2<S>() + 8) * 2) + (unsigned)(w * X_KSV * 4 * 2 * 1024);
@@ -1087,15 +1051,11 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
                 float zz[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-#if SET_X3V_GATE2
-                    // sigmoid(a) tanh(b) = (v - 1) / ((1 + u) (1 + v)), u = e^-a, v = e^2b: three transcendentals instead of four.  v is capped at 2^64
-                    // (tanh = 1 to fp32 from 2^25 on; inf - 1 times 1 / inf would be NaN); u may overflow: the quotient then is the limit, 0.
+                    // sigmoid(a) tanh(b) = (v - 1) / ((1 + u) (1 + v)), u = e^-a, v = e^2b: three transcendentals instead of four (profiles/r06_gate_quotient_ab.log).
+                    // v is capped at 2^64 (tanh = 1 to fp32 from 2^25 on; inf - 1 times 1 / inf would be NaN); u may overflow: the quotient then is the limit, 0.
                     const float u = __builtin_amdgcn_exp2f(PQ[eo][m][nb][i] * cg2);
                     const float v = __builtin_amdgcn_exp2f(fminf(PQ[eo][m + 2][nb][i] * cf2, 64.0f));
                     const float g = (v - 1.0f) * __builtin_amdgcn_rcpf((1.0f + u) * (1.0f + v));
-#else
-                    const float g = fsig(PQ[eo][m][nb][i] * is1w) * ftanh(PQ[eo][m + 2][nb][i] * is1w);
-#endif
                     zz[i] = tvp ? g : 0.0f;
                 }
                 unsigned plo[2], phi[2];
@@ -1124,24 +1084,14 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
             for (int cb = 0; cb < NB; ++cb) acc[0][rb][cb][r] = (rb == 0 ? bias + xres[cb][r] : bias) * s2;
         }
     }
-#if SET_X3V_SK_EARLY
-    float sk[NB][16];
-#pragma unroll
-    for (int cb = 0; cb < NB; ++cb) {
-        const rsrc_t rsk = make_rsrc(a.skp + ub[cb]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sk[cb][r] = buf_load_nt(rsk, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
-    }
-#endif
     X3V_TS(16)
     __syncthreads();
     X3V_PHASE(8)
-    gemm_x3<S, X_KS2, 1, NB, SET_X3V_PF2, SET_X3V_SLEEP2>(acc, rw, lane16, (unsigned)(x_n1<S>() * 2 + w * X_KS2 * 2 * 2 * 1024), (unsigned)(X_KS2 * 2 * 2 * 1024), lds,
-                                             xv_zpiece<NB>(), [&](int ks, int cb) { return (unsigned)((cb * 32 + l31) * XR + (ks * 16 + half * 8) * 2); });
+    gemm_x3<S, X_KS2, 1, NB, XV_PF2>(acc, rw, lane16, (unsigned)(x_n1<S>() * 2 + w * X_KS2 * 2 * 2 * 1024), (unsigned)(X_KS2 * 2 * 2 * 1024), lds,
+                                     xv_zpiece<NB>(), [&](int ks, int cb) { return (unsigned)((cb * 32 + l31) * XR + (ks * 16 + half * 8) * 2); });
     X3V_PHASE(9)
     // ---- epilogue
     const bool first = a.first != 0;
-#if !SET_X3V_SK_EARLY
     float sk[NB][16];
     if (!first) {
 #pragma unroll
@@ -1151,7 +1101,6 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
             for (int r = 0; r < 16; ++r) sk[cb][r] = buf_load_nt(rsk, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
         }
     }
-#endif
 #pragma unroll
     for (int cb = 0; cb < NB; ++cb) {
         if (tv[cb]) {
@@ -1221,10 +1170,10 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
         lt.nbu = (a.T + 31) / 32; lt.Q = a.B * lt.nbu; lt.q0 = i * NB;  // (x3v)
         f32x4 PQ[2][4][NB];
         X3V_KTS(0)
-#if SET_X3V_WAVE_PUBLISH
         // the finished tile is published by every wave on its own, as soon as ITS stores are complete (agent-scope write-through stores: complete =
         // visible to every XCD): the tile's flag counts waves, 8 per layer.  (The block-wide form -- drain, barrier, one store -- published ~5 us
-        // after the last wave's stores were issued, behind the next task's accumulator-start loads; profiles/r06_x3v_timeline.log.)
+        // after the last wave's stores were issued, behind the next task's accumulator-start loads; profiles/r06_x3v_timeline.log,
+        // profiles/r06_x3v_wave_publish_ab.log.)
         if (i_done >= 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if ((tid & 63) == 0 && !(l_done == 0 && i_done == fault_tile))
@@ -1232,7 +1181,6 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
             i_done = -1;
         }
         __builtin_amdgcn_sched_barrier(0);
-#endif
         // step offsets of the column blocks' utterances: loaded first, stored to LDS behind the wait below, published by the task-slot barrier
         // (the previous task read its offsets for the last time in its second staging pass, several barriers ago)
         float dsv[(NB * XC + 511) / 512];
@@ -1245,7 +1193,10 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
         __builtin_amdgcn_sched_barrier(0);
         const int *f0 = done + i, *fl = done + (i > 0 ? i - 1 : i), *fr = done + (i < ntiles - 1 ? i + 1 : i);
         int peek = l, claimed = 0;
-        if (tid == X3V_LEAD) {
+        // thread 0 claims the next task and looks at the dependency flags.  (Lane 0 of wave 7, one of the waves that reach the task boundary
+        // last, looks fresher -- spins in 51 of 256 tasks instead of 242 -- but waits for its claim behind its own 48 accumulator-start loads:
+        // +2.3 us per task, profiles/r06_x3v_e_ab.log.)
+        if (tid == 0) {
             if (l > 0) peek = min(ld_agent(f0), min(ld_agent(fl), ld_agent(fr))) / X3V_FLAG_UNIT;
             claimed = atomicAdd(counter, 1);
         }
@@ -1258,27 +1209,22 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
             for (int j = 0; j < (NB * XC + 511) / 512; ++j)
                 if (tid + 512 * j < NB * XC) dsh[tid + 512 * j] = dsv[j];
         }
-        if (tid == X3V_LEAD) {
+        if (tid == 0) {
             if (peek >= l) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             s_task[0] = claimed;
             s_task[1] = peek >= l ? 1 : 2;
         }
         __syncthreads();
         X3V_KTS(3)
-#if !SET_X3V_WAVE_PUBLISH
-        if (tid == 0 && i_done >= 0 && !(l_done == 0 && i_done == fault_tile))
-            __hip_atomic_store(done + i_done, l_done + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        i_done = -1;
-#endif
         if (__builtin_amdgcn_readfirstlane(s_task[1]) == 2) {
-            if (tid == X3V_LEAD) {
+            if (tid == 0) {
                 int ok = 1;
                 unsigned spins = 0;
                 for (;;) {
                     const int v0 = ld_agent(f0), v1 = ld_agent(fl), v2 = ld_agent(fr);
                     if (min(v0, min(v1, v2)) >= l * X3V_FLAG_UNIT) break;
                     __builtin_amdgcn_s_sleep(8);
-                    if (++spins > X_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
+                    if (++spins > STACK_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
                         __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if (a.err_flag) __hip_atomic_store(a.err_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         ok = 0;
@@ -1320,14 +1266,8 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#if SET_X3V_WAVE_PUBLISH
     if ((tid & 63) == 0 && i_done >= 0 && !(l_done == 0 && i_done == fault_tile))
         (void)__hip_atomic_fetch_add(done + i_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-    __syncthreads();
-    if (tid == 0 && i_done >= 0 && !(l_done == 0 && i_done == fault_tile))
-        __hip_atomic_store(done + i_done, l_done + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
 }
 
 template <int NB>
@@ -1368,7 +1308,6 @@ int launch_x3v(const SetDiffnetStackArgs &a, int n_cu, int fault_tile, hipStream
 //   with 8-byte agent-scope stores of 4 channels, copied to LDS with 16-byte loads.
 // Same products in the same order per accumulator as diffnet_stack_x3_kernel<SplitF16x2>: bit-identical to it.
 // =====================================================================================================================
-constexpr unsigned SX_SPIN_LIMIT = 1u << 20;
 constexpr int SX_PF = 8;  // A prefetch distance in k-steps (2 x 16 bytes each).  The images are cold in L2 at every layer (42 MB
                           // cycle through 4 MB per XCD), so a memory-side round trip per SX_PF k-steps bounds the GEMMs.  The kernel
                           // only runs with one block per CU (launch bounds (256, 1): the ring may spill into AGPRs): 4 -> 8 k-steps
@@ -1392,7 +1331,7 @@ __device__ __forceinline__ bool sx_wait(const int *f0, const int *f1, const int 
         const int v0 = ld_agent(f0), v1 = ld_agent(f1), v2 = ld_agent(f2);
         if (min(v0, min(v1, v2)) >= want) break;
         __builtin_amdgcn_s_sleep(1);
-        if (++spins > SX_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
+        if (++spins > SPLIT_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
             __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (err_flag) __hip_atomic_store(err_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return false;
@@ -1465,7 +1404,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
             unsigned spins = 0;
             while (l >= 2 && ld_agent(ready) < 4 * (l - 1)) {  // tile 0 has finished layer l - 2: it is on layer l - 1 now
                 __builtin_amdgcn_s_sleep(8);
-                if (++spins > SX_SPIN_LIMIT || ld_agent(abort_flag) != 0) return;
+                if (++spins > SPLIT_SPIN_LIMIT || ld_agent(abort_flag) != 0) return;
             }
             const unsigned char *img = reinterpret_cast<const unsigned char *>(a.wx3_all) + (int64_t)l * x_nimg<S>() * 2;
             const rsrc_t r1 = make_rsrc(img + (size_t)(2 * hp) * X_KS1 * 4 * 1024);

@@ -5,6 +5,7 @@ import ctypes as C
 import json
 import os
 import re
+import shutil
 
 import numpy as np
 import pytest
@@ -78,6 +79,52 @@ def test_launch_state_is_set_up_per_device_in_common_h():
             assert pat not in src, (fn, pat)
         flags = re.findall(r"^\s+static (?:bool|int) \w+ = ", src, flags=re.M)
         assert not flags, (fn, flags)
+
+
+def test_dropped_experiment_switches_stay_out_of_csrc():
+    """The compile-time switches of measured and dropped experiments (some of them wrong by design) are gone from the kernel sources: only
+    the shipped branch is left, the logs under profiles/ are the record.  The flag load and the spin limits of the stack kernels live in common.h."""
+    csrc = os.path.join(ROOT, "speech-editing-toolkit_amd", "csrc")
+    removed = re.compile(r"\b(SET_X3_EXP|SET_T128_EXP|SET_WINO_FENCED|SET_NO_TRAILING_SB|SET_X3V_\w*|X3V_LEAD|SET_X3W_NT|"
+                         r"X_SPIN_LIMIT|SP_SPIN_LIMIT|SX_SPIN_LIMIT)\b")
+    defined = []
+    for fn in sorted(os.listdir(csrc)):
+        if not fn.endswith((".hip", ".h")):
+            continue
+        src = open(os.path.join(csrc, fn)).read()
+        assert not removed.search(src), (fn, removed.findall(src))
+        if re.search(r"\bint\s+ld_agent\s*\(", src):
+            defined.append(fn)
+    assert defined == ["common.h"], defined
+
+
+INSTRUMENT_BUILDS = (("diffnet_x3.hip", "-DSET_X3_PROBE=1"), ("diffnet_x3.hip", "-DSET_X3_PROBE=2"), ("diffnet.hip", "-DSET_WINO_PHASES"),
+                     ("bf16.hip", "-DSET_CONV_PROBE=1"), ("diffnet_bf16.hip", "-DSET_BF16_PROBE=1"), ("resblock_x2.hip", "-DSET_RP_PROBE=1"))
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+def test_instrument_builds_compile():
+    """The phase-stamp builds that the live probes in tools/ load (tools/build_exp.sh) still compile for gfx950; the default build never
+    compiles their branches.  Device only, the flags of tools/isa_scan.py, in parallel."""
+    import importlib.util
+    import subprocess
+    import tempfile
+    from concurrent.futures import ThreadPoolExecutor
+    spec = importlib.util.spec_from_file_location("isa_scan", os.path.join(ROOT, "tools", "isa_scan.py"))
+    isa_scan = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(isa_scan)
+
+    def one(build):
+        f, define = build
+        out = os.path.join(tempfile.gettempdir(), "instrument_test_%d_%s_%s.s" % (os.getpid(), f, re.sub(r"\W", "_", define)))
+        r = subprocess.run(["hipcc"] + isa_scan.FLAGS + [define, "-o", out, os.path.join(isa_scan.CS, f)], capture_output=True, text=True)
+        if os.path.exists(out):
+            os.remove(out)
+        return f, define, r.returncode, r.stderr[-2000:]
+
+    with ThreadPoolExecutor(max_workers=len(INSTRUMENT_BUILDS)) as ex:
+        failed = [(f, d, err) for f, d, rc, err in ex.map(one, INSTRUMENT_BUILDS) if rc != 0]
+    assert not failed, failed
 
 
 def test_state_dict_layout_matches_reference():
@@ -532,7 +579,6 @@ def test_concurrent_cold_builds_compile_once_and_never_expose_a_partial_library(
     released by a barrier onto a COLD copy of the sources (no objects, no library): exactly one of them compiles (flock on
     libset_amd.so.lock, staleness re-checked under the lock), the others wait and return the finished file; the library appears by an
     atomic rename (no rank can dlopen a half-written file) and no temporary is left behind."""
-    import shutil
     import torch.multiprocessing as mp
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     copy = str(tmp_path / "tree")
