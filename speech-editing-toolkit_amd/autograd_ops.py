@@ -13,7 +13,7 @@ import torch
 from . import _lib, ops
 from ._lib import SetAmdError  # noqa: E402
 from ._lib import ACT, PRO, IMPL_MFMA, IMPL_NAIVE, check
-from .ops import _p, _stream, ConvWeight
+from .ops import _p, _stream, _uniform_stride, ConvWeight
 
 # no-gradient ops: identical to the inference path
 abs_sum_mask = ops.abs_sum_mask
@@ -282,18 +282,25 @@ def _gzeros(shape, device):
     return torch.zeros(shape, dtype=torch.float32, device=device)
 
 
-def _zeros_like(t):
-    return _gzeros(t.shape, t.device)
-
-
 def grad_sink(param):
-    """(target, owner): the optimizer-owned .grad view to accumulate a parameter gradient into, or (None, None) when the
-    gradient has to travel through autograd (no flat optimizer, first step, parameter used more than once)."""
+    """The optimizer-owned .grad view to accumulate a parameter gradient into, or None when the gradient has to travel through
+    autograd (no flat optimizer, first step, parameter used more than once).  Asking counts as a use of the parameter during the
+    optimizer's first step (FlatAdamW.sink): once per parameter and backward node, never for a row slice of a parameter."""
     owner = getattr(param, "_flat_owner", None) if param is not None else None
-    if owner is None:
-        return None, None
-    t = owner.sink(param)
-    return (t, owner) if t is not None else (None, None)
+    return owner.sink(param) if owner is not None else None
+
+
+def _tape_tgt(param, dev, cw=None):
+    """(accumulation target, gradient to hand to autograd or None when the kernel writes the optimizer's .grad view in place): THE rule
+    of every backward node below -- the .grad view when the flat optimizer owns the parameter, else a zeroed temporary of its shape.
+    cw: the ConvWeight the node's conv reads the parameter through; a row slice of a larger parameter (packed q / k / v projections)
+    never goes in place (and does not ask for the sink)."""
+    whole = cw is None or (cw.base == 0 and param.numel() == cw.Cout * cw.Cin * cw.K)
+    sink = grad_sink(param) if whole else None
+    if sink is not None:
+        return sink, None
+    tmp = _gzeros(param.shape, dev)
+    return tmp, tmp
 
 
 def _wgrad_impl(T):
@@ -378,13 +385,12 @@ def _grouped_targets(params, dev):
     """Where the gradients of one parameter kind of all layers go: (base pointer, element stride between layers, what to hand to
     autograd per layer).  In place when the flat optimizer owns every one of them at a uniform stride (its layout is: each layer's
     parameters contiguous, in the same order); otherwise one zeroed [L, ...] temporary whose slices autograd accumulates."""
-    sinks = [grad_sink(p_)[0] for p_ in params]
+    sinks = [grad_sink(p_) for p_ in params]
     n = params[0].numel()
     if all(t is not None for t in sinks):
-        ptrs = [t.data_ptr() for t in sinks]
-        step = (ptrs[1] - ptrs[0]) if len(ptrs) > 1 else 4 * n
-        if step % 4 == 0 and step >= 4 * n and all(ptrs[i] == ptrs[0] + i * step for i in range(len(ptrs))):
-            return ptrs[0], step // 4, [None] * len(params)
+        step = _uniform_stride(sinks)
+        if step is not None:
+            return sinks[0].data_ptr(), step, [None] * len(params)
         # owned, but not at a uniform stride (never seen with FlatAdamW): through autograd like unowned parameters
     tmp = _gzeros(len(params) * n, dev).view(len(params), *params[0].shape)
     return tmp.data_ptr(), n, [tmp[l] for l in range(len(params))]
@@ -434,35 +440,27 @@ class _Conv1dFn(torch.autograd.Function):
             if has_add and ctx.needs_input_grad[3]:
                 dadd = torch.empty(B, Cin, dtype=torch.float32, device=dy.device)
                 check(L().set_row_sum(_p(dx), _p(dadd), B * Cin, T_in, 1.0, _stream()), "set_row_sum")
-        dw = db = None
+        dw = db = r_w = r_b = None
         want_w, want_b = ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
-        w_sink = b_sink = None
         if want_w:
-            w = cw.raw()
             # plain [Cout,Cin,K] rows, possibly a row slice of a larger parameter (packed q/k/v projections)
             assert cw.stap == 1 and cw.sci == cw.K and cw.sco == cw.Cin * cw.K, "plain conv layout"
-            whole = cw.base == 0 and w.numel() == Cout * Cin * cw.K
-            w_sink = grad_sink(ctx.wparam)[0] if whole else None
-            dw = w_sink if w_sink is not None else _gzeros(w.shape, dy.device)
+            dw, r_w = _tape_tgt(ctx.wparam, dy.device, cw)
         if want_b:
-            b_sink = grad_sink(ctx.bparam)[0] if ctx.bparam.numel() == Cout else None
-            db = b_sink if b_sink is not None else _gzeros(Cout, dy.device)
+            db, r_b = _tape_tgt(ctx.bparam, dy.device)  # (a bias is never a slice: autograd takes a [Cout] gradient for a [Cout] input only)
         # gradients that go straight into .grad are leaves of this backward pass (the optimizer is their next reader): leaf stream
         # (g may be the engine's own gradient buffer dy, or be handed on as the residual's gradient: the autograd engine accumulates a later
         # arrival into such a buffer IN PLACE only while it holds the last reference to it (input_buffer.cpp: can_accumulate_inplace), and
         # leaf_work keeps a reference to its operands until the streams are joined -- so nothing rewrites g under the leaf kernels)
-        on_leaf = (not want_w or w_sink is not None) and (not want_b or b_sink is not None) and (want_w or want_b)
+        on_leaf = r_w is None and r_b is None and (want_w or want_b)
         with leaf_work(dy.device, on_leaf, g, x, chan_add):
             if want_w:
                 conv_wgrad(g, x, chan_add, dw, B, Cin, Cout, cw.K, dil, pad, T, T_in, PRO[pro], pro_param,
                            dw_ptr=dw.data_ptr() + 4 * cw.base)
             if want_b:
                 channel_sum_(g, db, B, Cout, T)
-        if w_sink is not None:
-            dw = None  # written in place; autograd still fires the parameter's post-accumulate hook (bucket launch)
-        if b_sink is not None:
-            db = None
-        return (dx if ctx.needs_input_grad[0] else None, dw, db, dadd, dres, None, None, None, None, None, None, None,
+        # (a gradient written in place is handed on as None; autograd still fires the parameter's post-accumulate hook: bucket launch)
+        return (dx if ctx.needs_input_grad[0] else None, r_w, r_b, dadd, dres, None, None, None, None, None, None, None,
                 None, None, None)
 
 
@@ -526,14 +524,11 @@ class _LayerNormChFn(torch.autograd.Function):
         dy = dy.contiguous()
         B, Cc, T = x.shape
         dx = torch.empty_like(x)
-        sg, _ = grad_sink(ctx.gparam)
-        sb, _ = grad_sink(ctx.bparam)
-        dg = sg if sg is not None else _zeros_like(gamma)
-        db = sb if sb is not None else _zeros_like(gamma)
+        (dg, r_g), (db, r_b) = _tape_tgt(ctx.gparam, x.device), _tape_tgt(ctx.bparam, x.device)
         part = _det_scratch(x.device, L().set_layernorm_ch_bwd_scratch(B, Cc, T))  # per-block partial rows (reused: stream-ordered)
         check(L().set_layernorm_ch_bwd(_p(x), _p(gamma), _p(mask), _p(dy), _p(dx), _p(dg), _p(db), _p(part), B, Cc, T,
                                        float(ctx.eps), _stream()), "set_layernorm_ch_bwd")
-        return dx, (None if sg is not None else dg), (None if sb is not None else db), None, None
+        return dx, r_g, r_b, None, None
 
 
 def layernorm_ch(x, gamma, beta, mask=None, eps=1e-5, out=None):
@@ -578,15 +573,6 @@ class _PreLnFfnFn(torch.autograd.Function):
         B, Cc, T = dy.shape
         Cmid, T1, T_in = z.shape[1], z.shape[2], h.shape[2]
         dev = dy.device
-
-        def tgt(param, cw=None):  # (accumulation target, gradient to hand to autograd or None when written in place)
-            whole = cw is None or (cw.base == 0 and param.numel() == cw.Cout * cw.Cin * cw.K)
-            sink = grad_sink(param)[0] if whole else None
-            if sink is not None:
-                return sink, None
-            tmp = _gzeros(param.shape, dev)
-            return tmp, tmp
-
         # ---- second conv (1x1, + residual, * mask): G2 = dy * mask is also the residual's gradient
         if ctx.drop is not None:  # the branch's gradient is keep * G2 / (1 - p) (same Philox keys as the forward)
             g2, gb = torch.empty_like(dy), torch.empty_like(dy)
@@ -600,7 +586,7 @@ class _PreLnFfnFn(torch.autograd.Function):
             check(L().set_conv_epilogue_bwd(_p(dy), None, _p(mask), _p(g2), B, Cc, T, 0, 1.0, _stream()), "set_conv_epilogue_bwd")
             gb = g2
         df = ops.conv1d(gb, cw2.transposed(), None, dil=-1, pad=0, T_iter=T1, T_out=T1)
-        (t_w2, r_w2), (t_b2, r_b2) = tgt(p_w2, cw2), tgt(p_b2)
+        (t_w2, r_w2), (t_b2, r_b2) = _tape_tgt(p_w2, dev, cw2), _tape_tgt(p_b2, dev)
         with leaf_work(dev, r_w2 is None and r_b2 is None, gb, f):  # (gb may be dy itself: kept referenced, see _Conv1dFn.backward)
             conv_wgrad(gb, f, None, t_w2, B, Cmid, Cc, 1, 1, 0, T, T1, dw_ptr=t_w2.data_ptr() + 4 * cw2.base)
             channel_sum_(gb, t_b2, B, Cc, T)
@@ -608,16 +594,12 @@ class _PreLnFfnFn(torch.autograd.Function):
         g1 = torch.empty_like(z)
         check(L().set_act_bwd_scaled(_p(z), _p(df), _p(g1), z.numel(), ACT[act], float(act_param), float(alpha), _stream()), "set_act_bwd_scaled")
         dh = ops.conv1d(g1, cw1.transposed(), None, dil=-dil, pad=-pad, T_iter=T_in, T_out=T_in)
-        (t_w1, r_w1), (t_b1, r_b1) = tgt(p_w1, cw1), tgt(p_b1)
+        (t_w1, r_w1), (t_b1, r_b1) = _tape_tgt(p_w1, dev, cw1), _tape_tgt(p_b1, dev)
         with leaf_work(dev, r_w1 is None and r_b1 is None, g1, h):
             conv_wgrad(g1, h, None, t_w1, B, Cc, Cmid, cw1.K, dil, pad, T1, T_in, dw_ptr=t_w1.data_ptr() + 4 * cw1.base)
             channel_sum_(g1, t_b1, B, Cmid, T1)
         # ---- LayerNorm backward, then the residual branch joins (same order as the fan-out node of the per-op tape: LN branch + residual)
-        dxl = torch.empty_like(x)
-        (t_g, r_g), (t_bt, r_bt) = tgt(p_gamma), tgt(p_beta)
-        part = _det_scratch(dev, L().set_layernorm_ch_bwd_scratch(B, Cc, T_in))
-        check(L().set_layernorm_ch_bwd_add(_p(x), _p(gamma), None, _p(dh), _p(g2), _p(dxl), _p(t_g), _p(t_bt), _p(part), B, Cc, T_in, float(eps),
-                                           _stream()), "set_layernorm_ch_bwd_add")  # dx = LN gradient + residual gradient, one launch
+        dxl, r_g, r_bt = _preln_tail(x, gamma, p_gamma, p_beta, dh, g2, eps)
         return (dxl, r_g, r_bt, r_w1, r_b1, r_w2, r_b2) + (None,) * 11
 
 
@@ -721,15 +703,14 @@ class _EmbeddingFn(torch.autograd.Function):
         (n_rows, Cc), scale, has_base = ctx.cfg
         dout = dout.contiguous()
         B, T = idx.shape
-        sink, _ = grad_sink(ctx.tparam)  # (a table that is a parameter used once: its gradient goes straight into .grad, on the leaf stream)
-        dtab = sink if sink is not None else _gzeros((n_rows, Cc), dout.device)
+        dtab, r_tab = _tape_tgt(ctx.tparam, dout.device)  # (a table that is a parameter used once: its gradient goes straight into .grad, on the leaf stream)
         # ordered scatter (no atomics): gradient rows transposed to [B][T][C], per-(utterance, segment) partial tables
         doutT = ops.bct_to_btc(dout)
         S = L().set_scatter_rows_segments(T)
-        with leaf_work(dout.device, sink is not None, dout, doutT, idx):
+        with leaf_work(dout.device, r_tab is None, dout, doutT, idx):
             check(L().set_scatter_rows_det(_p(idx), _p(doutT), _p(dtab), B, T, Cc, n_rows, float(scale), ctx.padding_idx, 0,
                                            _p(_det_scratch(dout.device, B * S * n_rows * Cc)), _stream()), "set_scatter_rows_det")
-        return None, (None if sink is not None else dtab), (dout if has_base else None), None, None
+        return None, r_tab, (dout if has_base else None), None, None
 
 
 def embedding_bct(idx, table, scale=1.0, out=None, accumulate=False, padding_idx=None):
@@ -964,7 +945,7 @@ class _DiffNetStackFn(torch.autograd.Function):
         layers = list(dn.residual_layers)
         dskip = dskip.contiguous()
         need_cond = ctx.needs_input_grad[2]
-        dcond = _zeros_like(cond) if need_cond else None
+        dcond = _gzeros(cond.shape, dev) if need_cond else None
         dd = torch.empty(B, L_ * C_, dtype=torch.float32, device=dev)
         dx = _gzeros((B, C_, T), dev)  # the last layer's x output feeds nothing
         grads = []
@@ -976,16 +957,12 @@ class _DiffNetStackFn(torch.autograd.Function):
             d_o = torch.empty(B, 2 * C_, T, dtype=torch.float32, device=dev)
             check(L().set_res_skip_bwd(_p(dx), _p(dskip), _p(dxr), _p(d_o), B, C_, T, _stream()), "set_res_skip_bwd")
             # output_projection (1x1, 256 -> 512)
-            def tgt(param):  # the optimizer's .grad view when it owns the parameter, else a zeroed temporary
-                sk, _ = grad_sink(param)
-                return (sk, True) if sk is not None else (_zeros_like(param), False)
-
-            dw_out, d1 = tgt(layer.output_projection.weight)
-            db_out, d2 = tgt(layer.output_projection.bias)
-            dw_cond, d3 = tgt(layer.conditioner_projection.weight)
-            db, d4 = tgt(layer.conditioner_projection.bias)
-            db2, d5 = tgt(layer.dilated_conv.bias)
-            dw_dil, d6 = tgt(layer.dilated_conv.weight)
+            dw_out, r_wo = _tape_tgt(layer.output_projection.weight, dev)
+            db_out, r_bo = _tape_tgt(layer.output_projection.bias, dev)
+            dw_cond, r_wc = _tape_tgt(layer.conditioner_projection.weight, dev)
+            db, r_bc = _tape_tgt(layer.conditioner_projection.bias, dev)
+            db2, r_bd = _tape_tgt(layer.dilated_conv.bias, dev)
+            dw_dil, r_wd = _tape_tgt(layer.dilated_conv.weight, dev)
             dz = ops.conv1d(d_o, layer._w_out.transposed(), None, dil=-1, pad=0, T_iter=T, T_out=T)
             # gate
             dy = torch.empty(B, 2 * C_, T, dtype=torch.float32, device=dev)
@@ -1002,15 +979,15 @@ class _DiffNetStackFn(torch.autograd.Function):
             dd[:, l * C_:(l + 1) * C_] = ddl
             dx = ops.sum_div(dxd, dxr)
             # the layer's six parameter gradients: leaves (leaf stream when they go straight into .grad)
-            with leaf_work(dev, d1 and d2 and d3 and d4 and d5 and d6, d_o, dy, z_all, cond, x_all, dl):
+            in_place = all(r is None for r in (r_wo, r_bo, r_wc, r_bc, r_bd, r_wd))
+            with leaf_work(dev, in_place, d_o, dy, z_all, cond, x_all, dl):
                 conv_wgrad(d_o, z_all[l], None, dw_out, B, C_, 2 * C_, 1, 1, 0, T, T)
                 channel_sum_(d_o, db_out, B, 2 * C_, T)
                 conv_wgrad(dy, cond, None, dw_cond, B, H, 2 * C_, 1, 1, 0, T, T)
                 channel_sum_(dy, db, B, 2 * C_, T)  # = db_cond = db_dil
                 channel_sum_(dy, db2, B, 2 * C_, T)
                 conv_wgrad(dy, x_all[l], dl, dw_dil, B, C_, 2 * C_, 3, dil, dil, T, T)
-            grads.append((None if d3 else dw_cond, None if d4 else db, None if d6 else dw_dil, None if d5 else db2,
-                          None if d1 else dw_out, None if d2 else db_out))
+            grads.append((r_wc, r_bc, r_wd, r_bd, r_wo, r_bo))
         grads.reverse()
         flat = [g for tup in grads for g in tup]
         return (None, dx, dcond, dd, *flat)
@@ -1076,7 +1053,7 @@ class _DiffNetStackBf16Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dskip):
-        dn, imgs, per = ctx.dn, ctx.imgs, ctx.per
+        dn, per = ctx.dn, ctx.per
         cond, dmat, x_all, y16, z16 = ctx.saved_tensors
         L_, C_ = dn.n_layers, dn.C
         B, H, T = cond.shape
@@ -1096,128 +1073,118 @@ class _DiffNetStackBf16Fn(torch.autograd.Function):
         dy16_all = torch.empty(n_slab, B, 2 * C_, T, dtype=torch.bfloat16, device=dev)
         do16_all = torch.empty(n_slab, B, 2 * C_, T, dtype=torch.bfloat16, device=dev)
         dx = [torch.empty(B, C_, T, dtype=torch.float32, device=dev) for _ in range(2)]
-        G16, GX16 = _lib.DTYPE_BF16_G16, _lib.DTYPE_BF16_G16_X16
         a = _lib.SetDiffnetLayerBf16BwdArgs()
         a.dskip, a.dcond = dskip.data_ptr(), dcond.data_ptr()
         a.B, a.T = B, T
-        grads = []
-        cur = None  # gradient w.r.t. the current layer's x_out (None for the last layer: its x_out feeds nothing)
-        # grouped: the per-tile partial sums (bias / step-offset gradients) of ALL layers are kept and reduced by ONE launch after the sweep
-        # (L x ~2 MB at B = 32, T = 800) instead of one 5 us launch per layer in the middle of the chain of layer kernels
-        if grouped:
-            tiles_g = L().set_diffnet_layer_bwd_bf16_tiles(T, layers[0].dilation)
-            pdbo_all = torch.empty(L_, B * tiles_g, 2 * C_, dtype=torch.float32, device=dev)
-            pdby_all = torch.empty(L_, B * tiles_g, 2 * C_, dtype=torch.float32, device=dev)
-            pdd_all = torch.empty(L_, B * tiles_g, C_, dtype=torch.float32, device=dev)
-        if SWEEP_EVENTS is not None:  # measurement hook (bench.py): hipEvents around the L launches of diffnet_layer_bwd_bf16_kernel
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-        if grouped:  # the sweep as 20 launches on integer addresses (see forward); everything else of this form happens after the loop
-            dy0, do0, y0, s16 = dy16_all.data_ptr(), do16_all.data_ptr(), y16.data_ptr(), 2 * B * 2 * C_ * T
-            pb0, py0, pd0, sp = pdbo_all.data_ptr(), pdby_all.data_ptr(), pdd_all.data_ptr(), 4 * B * tiles_g * C_
-            dxp = (dx[0].data_ptr(), dx[1].data_ptr())
-            fn, st, ref = L().set_diffnet_layer_bwd_bf16, _stream(), C.byref(a)
-            a.dil = layers[0].dilation
-            curp = None
-            for l in range(L_ - 1, -1, -1):
-                a.dy16, a.do16, a.y16 = dy0 + l * s16, do0 + l * s16, y0 + l * s16
-                a.dx_out, a.img, a.dx = curp, per[l][0], dxp[l & 1]
-                a.part_dbo, a.part_dby, a.part_dd = pb0 + l * 2 * sp, py0 + l * 2 * sp, pd0 + l * sp
-                a.dcond_first = int(l == L_ - 1)
-                check(fn(ref, st), "set_diffnet_layer_bwd_bf16")
-                grads.append([None] * 6)
-                curp = dxp[l & 1]
-            cur = dx[0]
-        for l in (range(L_ - 1, -1, -1) if not grouped else ()):
-            layer = layers[l]
-            dil = layer.dilation
-            tiles = L().set_diffnet_layer_bwd_bf16_tiles(T, dil)
-            if grouped:
-                pdbo_c, pdby_c, pdd_c = pdbo_all[l], pdby_all[l], pdd_all[l]
-            else:
-                pdbo_c = torch.empty(B * tiles, 2 * C_, dtype=torch.float32, device=dev)
-                pdby_c = torch.empty(B * tiles, 2 * C_, dtype=torch.float32, device=dev)
-                pdd_c = torch.empty(B * tiles, C_, dtype=torch.float32, device=dev)
-            out = dx[l & 1]
-            dy16, do16 = dy16_all[l if grouped else 0], do16_all[l if grouped else 0]
-            a.dy16, a.do16 = dy16.data_ptr(), do16.data_ptr()
-            a.dx_out = None if cur is None else cur.data_ptr()
-            a.y16, a.img, a.dx = y16[l].data_ptr(), imgs[l].data_ptr(), out.data_ptr()
-            a.part_dbo, a.part_dby, a.part_dd = pdbo_c.data_ptr(), pdby_c.data_ptr(), pdd_c.data_ptr()
-            a.dil, a.dcond_first = dil, int(l == L_ - 1)
-            check(L().set_diffnet_layer_bwd_bf16(C.byref(a), _stream()), "set_diffnet_layer_bwd_bf16")
-            # bias / step-offset gradients: ordered sums of the per-tile partials, one launch per layer (straight into
-            # .grad when the flat optimizer owns it, else into a zeroed temporary that autograd accumulates)
-            def btgt(param):  # (accumulation target, gradient to hand to autograd or None when written in place)
-                sink, _ = grad_sink(param)
-                if sink is not None:
-                    return sink, None
-                tmp = _gzeros(2 * C_, dev)
-                return tmp, tmp
-
-            def wg(param, *args, **kw):
-                sink, owner = grad_sink(param)
-                tgt = sink if sink is not None else _zeros_like(param)
-                conv_wgrad(args[0], args[1], args[2], tgt, *args[3:], **kw)  # (compute stream: the next layer's launch overwrites dy16 / do16)
-                return None if sink is not None else tgt
-
-            if grouped:
-                dw_out = dw_cond = dw_dil = db_out = db_dil = db_cond = None  # filled in below
-            else:
-                (t_out, db_out), (t_dil, db_dil), (t_cond, db_cond) = (btgt(layer.output_projection.bias),
-                                                                       btgt(layer.dilated_conv.bias),
-                                                                       btgt(layer.conditioner_projection.bias))
-                check(L().set_diffnet_layer_bwd_reduce(_p(pdbo_c), _p(pdby_c), _p(pdd_c), B, tiles, _p(t_out), _p(t_dil), _p(t_cond),
-                                                       dd.data_ptr() + 4 * l * C_, dd.stride(0), _stream()), "set_diffnet_layer_bwd_reduce")
-                dw_out = wg(layer.output_projection.weight, do16, z16[l], None, B, C_, 2 * C_, 1, 1, 0, T, T, dtype=GX16)
-                dw_cond = wg(layer.conditioner_projection.weight, dy16, cond, None, B, H, 2 * C_, 1, 1, 0, T, T, dtype=G16)
-                dl = dmat[:, l * C_:(l + 1) * C_].contiguous()
-                dw_dil = wg(layer.dilated_conv.weight, dy16, x_all[l], dl, B, C_, 2 * C_, 3, dil, dil, T, T, dtype=G16)
-            grads.append([dw_cond, db_cond, dw_dil, db_dil, dw_out, db_out])
-            cur = out
-        if SWEEP_EVENTS is not None:
-            ev1.record()
-            SWEEP_EVENTS.append((ev0, ev1, L_ if grouped else 4 * L_))  # (grouped: nothing but the L layer launches lies between the events)
-        grads.reverse()
-        if grouped:
-            dil = layers[0].dilation
-            n_act = B * 2 * C_ * T
-            pb_o, sb_o, rb_o = _grouped_targets([ly.output_projection.bias for ly in layers], dev)
-            pb_d, sb_d, rb_d = _grouped_targets([ly.dilated_conv.bias for ly in layers], dev)
-            pb_c, sb_c, rb_c = _grouped_targets([ly.conditioner_projection.bias for ly in layers], dev)
-            check(L().set_diffnet_layers_bwd_reduce(_p(pdbo_all), _p(pdby_all), _p(pdd_all), B, tiles_g, L_, C.c_void_p(pb_o), sb_o,
-                                                    C.c_void_p(pb_d), sb_d, C.c_void_p(pb_c), sb_c, _p(dd), dd.stride(0), C_, _stream()),
-                  "set_diffnet_layers_bwd_reduce")
-            for l in range(L_):
-                grads[l][1], grads[l][3], grads[l][5] = rb_c[l], rb_d[l], rb_o[l]
-            p_out, s_out, r_out = _grouped_targets([ly.output_projection.weight for ly in layers], dev)
-            p_c, s_c, r_c = _grouped_targets([ly.conditioner_projection.weight for ly in layers], dev)
-            p_d, s_d, r_d = _grouped_targets([ly.dilated_conv.weight for ly in layers], dev)
-            dl_all = dmat.view(B, L_, C_).transpose(0, 1).contiguous()  # [L][B][C] step offsets (the conv's input is x + d)
-            # written straight into .grad (every r_* entry None): leaves of the backward pass -- 2.3 ms of chip-filling GEMMs that run on the
-            # leaf stream under the conditioner's backward (hundreds of 5-40 us kernels on a few dozen workgroups each)
-            in_place = all(r is None for r in r_out + r_c + r_d)
-            with leaf_work(dev, in_place, do16_all, dy16_all, z16, cond, x_all, dl_all):
-                conv_wgrad_grouped(do16_all, z16, None, p_out, L_, n_act, B * C_ * T, 0, s_out, B, C_, 2 * C_, 1, 1, 0, T, T, GX16)
-                conv_wgrad_grouped(dy16_all, cond, None, p_c, L_, n_act, 0, 0, s_c, B, H, 2 * C_, 1, 1, 0, T, T, G16)
-                conv_wgrad_grouped(dy16_all, x_all, dl_all, p_d, L_, n_act, B * C_ * T, B * C_, s_d, B, C_, 2 * C_, 3, dil, dil, T, T, G16)
-            for l in range(L_):
-                grads[l][0], grads[l][2], grads[l][4] = r_c[l], r_d[l], r_out[l]
-        flat = [g for tup in grads for g in tup]
+        # measurement hook (bench.py): hipEvents that the sweep records around its diffnet_layer_bwd_bf16_kernel launches
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if SWEEP_EVENTS is not None else None
+        sweep = _bf16_stack_bwd_grouped if grouped else _bf16_stack_bwd_per_layer
+        cur, grads = sweep(a, layers, per, cond, dmat, x_all, y16, z16, dy16_all, do16_all, dx, dd, ev)
         need_cond = ctx.needs_input_grad[2]
-        return (None, cur, dcond if need_cond else None, dd, *flat)
+        return (None, cur, dcond if need_cond else None, dd, *[g for tup in grads for g in tup])
 
 
-def _uniform_stride(tensors):
-    """Element stride between the (equal-shaped, contiguous fp32) tensors when they sit at one stride in memory, else None."""
-    ptrs = [t.data_ptr() for t in tensors]
-    n = tensors[0].numel()
-    step = (ptrs[1] - ptrs[0]) if len(ptrs) > 1 else 4 * n
-    if step % 4 or step < 4 * n or any(ptrs[i] != ptrs[0] + i * step for i in range(len(ptrs))):
-        return None
-    if any((not t.is_contiguous()) or t.dtype != torch.float32 for t in tensors):
-        return None
-    return step // 4
+def _sweep_done(ev, launches):
+    if ev is not None:
+        ev[1].record()
+        SWEEP_EVENTS.append((ev[0], ev[1], launches))
+
+
+def _bf16_stack_bwd_grouped(a, layers, per, cond, dmat, x_all, y16, z16, dy16_all, do16_all, dx, dd, ev):
+    """The layers share one dilation: the sweep is L launches on integer addresses that keep dy / d_o and the per-tile partial sums
+    (bias / step-offset gradients, L x ~2 MB at B = 32, T = 800) of EVERY layer; after it ONE launch reduces the partials and three
+    grouped launches compute the weight gradients of all layers, instead of a 5 us reduce and three GEMMs per layer in the middle of the
+    chain of layer kernels.  Returns (gradient w.r.t. the stack's input, per layer (W_cond, b_cond, W_dil, b_dil, W_out, b_out))."""
+    L_, (B, H, T), C_, dev = len(layers), cond.shape, x_all.shape[2], cond.device
+    dil = layers[0].dilation
+    tiles = L().set_diffnet_layer_bwd_bf16_tiles(T, dil)
+    pdbo_all = torch.empty(L_, B * tiles, 2 * C_, dtype=torch.float32, device=dev)
+    pdby_all = torch.empty(L_, B * tiles, 2 * C_, dtype=torch.float32, device=dev)
+    pdd_all = torch.empty(L_, B * tiles, C_, dtype=torch.float32, device=dev)
+    if ev is not None:
+        ev[0].record()
+    # per-layer addresses as integers, the function, the stream and the byref bound once (see the forward)
+    dy0, do0, y0, s16 = dy16_all.data_ptr(), do16_all.data_ptr(), y16.data_ptr(), 2 * B * 2 * C_ * T
+    pb0, py0, pd0, sp = pdbo_all.data_ptr(), pdby_all.data_ptr(), pdd_all.data_ptr(), 4 * B * tiles * C_
+    dxp = (dx[0].data_ptr(), dx[1].data_ptr())
+    fn, st, ref = L().set_diffnet_layer_bwd_bf16, _stream(), C.byref(a)
+    a.dil = dil
+    curp = None  # gradient w.r.t. the current layer's x_out (None for the last layer: its x_out feeds nothing)
+    for l in range(L_ - 1, -1, -1):
+        a.dy16, a.do16, a.y16 = dy0 + l * s16, do0 + l * s16, y0 + l * s16
+        a.dx_out, a.img, a.dx = curp, per[l][0], dxp[l & 1]
+        a.part_dbo, a.part_dby, a.part_dd = pb0 + l * 2 * sp, py0 + l * 2 * sp, pd0 + l * sp
+        a.dcond_first = int(l == L_ - 1)
+        check(fn(ref, st), "set_diffnet_layer_bwd_bf16")
+        curp = dxp[l & 1]
+    _sweep_done(ev, L_)  # (nothing but the L layer launches lies between the events)
+    n_act = B * 2 * C_ * T
+    pb_o, sb_o, rb_o = _grouped_targets([ly.output_projection.bias for ly in layers], dev)
+    pb_d, sb_d, rb_d = _grouped_targets([ly.dilated_conv.bias for ly in layers], dev)
+    pb_c, sb_c, rb_c = _grouped_targets([ly.conditioner_projection.bias for ly in layers], dev)
+    check(L().set_diffnet_layers_bwd_reduce(_p(pdbo_all), _p(pdby_all), _p(pdd_all), B, tiles, L_, C.c_void_p(pb_o), sb_o,
+                                            C.c_void_p(pb_d), sb_d, C.c_void_p(pb_c), sb_c, _p(dd), dd.stride(0), C_, _stream()),
+          "set_diffnet_layers_bwd_reduce")
+    p_out, s_out, r_out = _grouped_targets([ly.output_projection.weight for ly in layers], dev)
+    p_c, s_c, r_c = _grouped_targets([ly.conditioner_projection.weight for ly in layers], dev)
+    p_d, s_d, r_d = _grouped_targets([ly.dilated_conv.weight for ly in layers], dev)
+    dl_all = dmat.view(B, L_, C_).transpose(0, 1).contiguous()  # [L][B][C] step offsets (the conv's input is x + d)
+    # written straight into .grad (every r_* entry None): leaves of the backward pass -- 2.3 ms of chip-filling GEMMs that run on the
+    # leaf stream under the conditioner's backward (hundreds of 5-40 us kernels on a few dozen workgroups each)
+    G16, GX16 = _lib.DTYPE_BF16_G16, _lib.DTYPE_BF16_G16_X16
+    in_place = all(r is None for r in r_out + r_c + r_d)
+    with leaf_work(dev, in_place, do16_all, dy16_all, z16, cond, x_all, dl_all):
+        conv_wgrad_grouped(do16_all, z16, None, p_out, L_, n_act, B * C_ * T, 0, s_out, B, C_, 2 * C_, 1, 1, 0, T, T, GX16)
+        conv_wgrad_grouped(dy16_all, cond, None, p_c, L_, n_act, 0, 0, s_c, B, H, 2 * C_, 1, 1, 0, T, T, G16)
+        conv_wgrad_grouped(dy16_all, x_all, dl_all, p_d, L_, n_act, B * C_ * T, B * C_, s_d, B, C_, 2 * C_, 3, dil, dil, T, T, G16)
+    return dx[0], list(zip(r_c, rb_c, r_d, rb_d, r_out, rb_o))
+
+
+def _bf16_wgrad(param, g, x, chan_add, *shape, dtype):
+    """One layer weight gradient of the per-layer form, on the compute stream (the next layer's launch overwrites dy16 / do16)."""
+    tgt, ret = _tape_tgt(param, g.device)
+    conv_wgrad(g, x, chan_add, tgt, *shape, dtype=dtype)
+    return ret
+
+
+def _bf16_stack_bwd_per_layer(a, layers, per, cond, dmat, x_all, y16, z16, dy16_all, do16_all, dx, dd, ev):
+    """Mixed dilations, or dy / d_o of all layers over the memory budget: one dy / d_o slab, and per layer the fused launch, one
+    ordered reduce of its per-tile partials (bias / step-offset gradients) and three weight-gradient GEMMs.  Returns what
+    _bf16_stack_bwd_grouped returns."""
+    L_, (B, H, T), C_, dev = len(layers), cond.shape, x_all.shape[2], cond.device
+    G16, GX16 = _lib.DTYPE_BF16_G16, _lib.DTYPE_BF16_G16_X16
+    dy16, do16 = dy16_all[0], do16_all[0]
+    a.dy16, a.do16 = dy16.data_ptr(), do16.data_ptr()
+    grads = []
+    cur = None  # gradient w.r.t. the current layer's x_out (None for the last layer: its x_out feeds nothing)
+    if ev is not None:
+        ev[0].record()
+    for l in range(L_ - 1, -1, -1):
+        layer = layers[l]
+        dil = layer.dilation
+        tiles = L().set_diffnet_layer_bwd_bf16_tiles(T, dil)
+        pdbo = torch.empty(B * tiles, 2 * C_, dtype=torch.float32, device=dev)
+        pdby = torch.empty(B * tiles, 2 * C_, dtype=torch.float32, device=dev)
+        pdd = torch.empty(B * tiles, C_, dtype=torch.float32, device=dev)
+        out = dx[l & 1]
+        a.dx_out = None if cur is None else cur.data_ptr()
+        a.y16, a.img, a.dx = y16[l].data_ptr(), per[l][0], out.data_ptr()
+        a.part_dbo, a.part_dby, a.part_dd = pdbo.data_ptr(), pdby.data_ptr(), pdd.data_ptr()
+        a.dil, a.dcond_first = dil, int(l == L_ - 1)
+        check(L().set_diffnet_layer_bwd_bf16(C.byref(a), _stream()), "set_diffnet_layer_bwd_bf16")
+        (t_out, db_out), (t_dil, db_dil), (t_cond, db_cond) = (
+            _tape_tgt(m.bias, dev) for m in (layer.output_projection, layer.dilated_conv, layer.conditioner_projection))
+        check(L().set_diffnet_layer_bwd_reduce(_p(pdbo), _p(pdby), _p(pdd), B, tiles, _p(t_out), _p(t_dil), _p(t_cond),
+                                               dd.data_ptr() + 4 * l * C_, dd.stride(0), _stream()), "set_diffnet_layer_bwd_reduce")
+        dw_out = _bf16_wgrad(layer.output_projection.weight, do16, z16[l], None, B, C_, 2 * C_, 1, 1, 0, T, T, dtype=GX16)
+        dw_cond = _bf16_wgrad(layer.conditioner_projection.weight, dy16, cond, None, B, H, 2 * C_, 1, 1, 0, T, T, dtype=G16)
+        dl = dmat[:, l * C_:(l + 1) * C_].contiguous()
+        dw_dil = _bf16_wgrad(layer.dilated_conv.weight, dy16, x_all[l], dl, B, C_, 2 * C_, 3, dil, dil, T, T, dtype=G16)
+        grads.append((dw_cond, db_cond, dw_dil, db_dil, dw_out, db_out))
+        cur = out
+    _sweep_done(ev, 4 * L_)
+    grads.reverse()
+    return cur, grads
 
 
 class _StepProjFn(torch.autograd.Function):
@@ -1382,15 +1349,6 @@ def self_attention(qkv, heads, key_padding_mask=None, fill=float("-inf"), alpha=
 
 def cross_attention(q, kv, heads, key_padding_mask=None, fill=-1e8, alpha=1.0, want_p=True):
     return _CrossAttnFn.apply(q, kv, heads, key_padding_mask, fill, alpha, want_p)
-
-
-def _tape_tgt(param, dev, whole=True):
-    """(accumulation target, gradient to hand to autograd or None when the kernel writes the optimizer's .grad view in place)."""
-    sink = grad_sink(param)[0] if whole else None
-    if sink is not None:
-        return sink, None
-    tmp = _gzeros(param.shape, dev)
-    return tmp, tmp
 
 
 def _preln_tail(x, gamma, p_gamma, p_beta, dh, g2, eps):

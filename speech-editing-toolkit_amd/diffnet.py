@@ -85,10 +85,10 @@ class DiffNet(nn.Module):
         return self.can_fuse()
 
     def fused_packs(self, inference=True):
-        """Contiguous [L][...] packed weights + biases for the fused layer / persistent stack kernels (re-packed when any
-        layer parameter changes): (w1p, w2p, b_dil, b_out, w1w, w2w [Winograd], w1s, w2s [row-split], wx3 [split-operand]).
-        inference=False (the training forward, whose weights change every step): only what the Winograd training kernel
-        reads -- the last three are None (no extra 40 MB permutation and no per-layer scale read-backs per step)."""
+        """The ops.StackImages of the fused layer / persistent stack kernels: contiguous [L][...] packed weights + biases, re-packed
+        when any layer parameter changes.  inference=False (the training forward, whose weights change every step): only what the
+        Winograd training kernel reads -- w1s, w2s and wx3 stay None (no extra 40 MB permutation and no per-layer scale read-backs
+        per step)."""
         layers = list(self.residual_layers)
         key = ops.weights_key([p for l in layers for p in
                                (l.dilated_conv.weight, l.output_projection.weight, l.dilated_conv.bias, l.output_projection.bias)])
@@ -101,9 +101,8 @@ class DiffNet(nn.Module):
             wino = self.dilation_cycle_length <= 4  # Winograd F(2,3) images for the persistent stack kernel (d <= 8)
             w1w = torch.empty(L, 512 * 256 * 4, dtype=torch.float32, device=dev) if wino else None
             w2w = torch.empty(L, 512 * 256, dtype=torch.float32, device=dev) if wino else None
-            from .autograd_ops import _uniform_stride
             wds, wos = [l.dilated_conv.weight.detach() for l in layers], [l.output_projection.weight.detach() for l in layers]
-            sd, so = _uniform_stride(wds), _uniform_stride(wos)
+            sd, so = ops._uniform_stride(wds), ops._uniform_stride(wos)
             if sd is not None and so is not None and wds[0].is_cuda:  # (the flat optimizer's layout) every layer in one launch per image family
                 from . import _lib
                 _lib.check(_lib.lib().set_pack_diffnet_layers(ops._p(wds[0]), ops._p(wos[0]), sd, so, ops._p(w1), ops._p(w2), ops._p(w1w),
@@ -115,20 +114,21 @@ class DiffNet(nn.Module):
                         ops.pack_diffnet_layer_wino(wds[i], wos[i], w1w[i], w2w[i])
             bd = torch.stack([l.dilated_conv.bias for l in layers]).contiguous()
             bo = torch.stack([l.output_projection.bias for l in layers]).contiguous()
-            return w1, w2, bd, bo, w1w, w2w
+            return ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, w1w=w1w, w2w=w2w)
         packs = self._packs.get(key, build)
         if not inference:
-            return packs + (None, None, None)
+            return packs
 
         def build_extra(_):
-            w1s, w2s = ops.split_images(packs[0], packs[1])  # small-batch (row-split) stack kernel
+            w1s, w2s = ops.split_images(packs.w1p, packs.w2p)  # small-batch (row-split) stack kernel
             wx3 = None
             if self.dilation_cycle_length <= 4:  # split-operand images of the throughput kernel (csrc/diffnet_x3.hip)
                 wx3 = ops.SplitOperandImages(L, ops.split_operand_mode(), dev)
                 for i, l in enumerate(layers):
                     wx3.pack(i, l.dilated_conv.weight.detach(), l.output_projection.weight.detach())
             return w1s, w2s, wx3
-        return packs + self._packs_extra.get((key, ops.split_operand_mode()), build_extra)
+        w1s, w2s, wx3 = self._packs_extra.get((key, ops.split_operand_mode()), build_extra)
+        return packs._replace(w1s=w1s, w2s=w2s, wx3=wx3)
 
     def stack_params(self):
         """Every residual layer's conditioner projection, dilated conv and output projection, weight then bias: the parameters of the
@@ -145,12 +145,11 @@ class DiffNet(nn.Module):
 
         def build(_):
             from . import _lib
-            from .autograd_ops import _uniform_stride
             layers = list(self.residual_layers)
             L = len(layers)
             img = torch.empty(L, _lib.lib().set_diffnet_layer_bf16_image_size(), dtype=torch.bfloat16, device=ps[0].device)
             wd, wc, wo = ps[2::6], ps[0::6], ps[4::6]
-            strides = self._img16_strides.get(tuple(a for a, _ in key[-1]), lambda _: [_uniform_stride(ws) for ws in (wd, wc, wo)])
+            strides = self._img16_strides.get(tuple(a for a, _ in key[-1]), lambda _: [ops._uniform_stride(ws) for ws in (wd, wc, wo)])
             if all(st is not None for st in strides):  # (the flat optimizer's layout: every layer's tensors at one stride) one launch
                 _lib.check(_lib.lib().set_pack_diffnet_layers_bf16(ops._p(wd[0]), ops._p(wc[0]), ops._p(wo[0]), strides[0], strides[1],
                                                                    strides[2], ops._p(img), L, ops._stream()), "set_pack_diffnet_layers_bf16")

@@ -9,6 +9,7 @@ import collections
 import ctypes as C
 import math
 import os
+import typing
 
 import torch
 
@@ -188,6 +189,18 @@ def _p(t):
     """Device address of a tensor as a plain int (ctypes converts it for a `void *` parameter; wrapping it in c_void_p here cost 0.25 us per
     pointer, ~3,000 pointers per training step)."""
     return None if t is None else t.data_ptr()
+
+
+def _uniform_stride(tensors):
+    """Element stride between the (equal-shaped, contiguous fp32) tensors when they sit at one stride in memory, else None."""
+    ptrs = [t.data_ptr() for t in tensors]
+    n = tensors[0].numel()
+    step = (ptrs[1] - ptrs[0]) if len(ptrs) > 1 else 4 * n
+    if step % 4 or step < 4 * n or any(ptrs[i] != ptrs[0] + i * step for i in range(len(ptrs))):
+        return None
+    if any((not t.is_contiguous()) or t.dtype != torch.float32 for t in tensors):
+        return None
+    return step // 4
 
 
 def _chk(t, dtype=torch.float32, name="tensor"):
@@ -797,22 +810,24 @@ class split_operand_mode_as:
         _SPLIT_MODE_OVERRIDE[0] = self.prev
 
 
+def _images_mask(have_wino, have_split, x3_mode):
+    """The `images` bit mask of set_diffnet_stack_variant / _x3_winograd: which weight images the caller holds."""
+    m = split_operand_mode() if x3_mode is None else int(x3_mode)
+    return int(bool(have_wino)) | (2 if have_split else 0) | (4 if m == 3 else 0) | (8 if m == 2 else 0)
+
+
 def stack_variant(B, T, dilation_cycle_length, have_wino=True, have_split=True, x3_mode=None):
     """0 / 1: direct kernel (64- / 32-frame tiles), 2: Winograd kernel, 3: row-split kernel (small batches), 4 / 5: split-operand
     kernel (3 x bf16 / 2 x fp16) -- what set_diffnet_stack would pick.  x3_mode: 0 (no split-operand images), 2, 3, or None =
     split_operand_mode()."""
-    m = split_operand_mode() if x3_mode is None else int(x3_mode)
-    bits = int(bool(have_wino)) | (2 if have_split else 0) | (4 if m == 3 else 0) | (8 if m == 2 else 0)
-    return int(_lib.lib().set_diffnet_stack_variant(int(B), int(T), int(dilation_cycle_length), bits))
+    return int(_lib.lib().set_diffnet_stack_variant(int(B), int(T), int(dilation_cycle_length), _images_mask(have_wino, have_split, x3_mode)))
 
 
 def stack_x3_winograd(B, T, dilation_cycle_length, have_wino=True, have_split=True, x3_mode=None):
     """Non-zero when variant 5 (two-piece fp16 split-operand kernel) runs GEMM 1 in its Winograd F(2,3) form for this shape (round 6,
     diffnet_stack_x3v_kernel): the number of 32-frame column blocks per tile -- 3 = 96-frame tiles (shapes with a tile chain for every CU),
     2 = 64-frame tiles; 0 = the direct form."""
-    m = split_operand_mode() if x3_mode is None else int(x3_mode)
-    bits = int(bool(have_wino)) | (2 if have_split else 0) | (4 if m == 3 else 0) | (8 if m == 2 else 0)
-    return int(_lib.lib().set_diffnet_stack_x3_winograd(int(B), int(T), int(dilation_cycle_length), bits))
+    return int(_lib.lib().set_diffnet_stack_x3_winograd(int(B), int(T), int(dilation_cycle_length), _images_mask(have_wino, have_split, x3_mode)))
 
 
 STACK_VARIANT_NAMES = {0: "diffnet_stack_kernel<2,4,2>", 1: "diffnet_stack_kernel<1,8,2>", 2: "diffnet_stack_wino_kernel",
@@ -849,43 +864,66 @@ def split_images(w1p_all, w2p_all):
     return tuple(w.view(L, 4, -1, 64, 4).permute(0, 1, 4, 2, 3).contiguous().view(L, -1) for w in (w1p_all, w2p_all))
 
 
-def _split_images(a, packs, B, T, dcl, dev):
-    """Row-split images + z workspace of the small-batch stack kernel into the args struct (only for shapes the kernel
-    is picked for); returns the workspace (the caller keeps it alive; stream-ordered reuse is safe)."""
-    x3 = packs[8] if len(packs) >= 9 else None
+class StackImages(typing.NamedTuple):
+    """The weight images of the DiffNet layer stack, each a contiguous [L][...] buffer (DiffNet.fused_packs() builds them; tests and probes
+    build their own).  Which kernel reads which field (None = no such image: set_diffnet_stack picks among the kernels it has images for):
+    w1p, w2p      packed fp32 images of the dilated conv / output projection (set_pack_diffnet_layer): the direct stack kernel (variants
+                  0 / 1) and the per-layer kernels of the non-persistent reverse loop
+    b_dil, b_out  [L, 512] biases: every kernel; b_dil.shape[0] is the number of layers of the launch
+    w1w, w2w      Winograd F(2,3) images (set_pack_diffnet_layer_wino): the Winograd kernel (variant 2), also the training forward
+    w1s, w2s      row-split images (split_images(w1p, w2p)): the small-batch row-split kernel (variant 3)
+    wx3           SplitOperandImages: the split-operand kernel (variants 4 / 5, by wx3.mode)"""
+    w1p: torch.Tensor
+    w2p: torch.Tensor
+    b_dil: torch.Tensor
+    b_out: torch.Tensor
+    w1w: typing.Optional[torch.Tensor] = None
+    w2w: typing.Optional[torch.Tensor] = None
+    w1s: typing.Optional[torch.Tensor] = None
+    w2s: typing.Optional[torch.Tensor] = None
+    wx3: typing.Optional[SplitOperandImages] = None
+
+
+def _set_images(a, images, B, T, dcl, dev):
+    """The image fields of a SetDiffnetStackArgs / SetDiffLoopArgs from a StackImages.  The row-split images and their z workspace go in
+    only for shapes the row-split kernel (variant 3) is picked for; returns that workspace or None (the caller keeps it alive until the
+    launch is enqueued; stream-ordered reuse is safe)."""
+    if not isinstance(images, StackImages):
+        raise TypeError("the layer stack takes its weight images as an ops.StackImages (fields by name), not %s: a bare tuple in the "
+                        "wrong order would launch on the wrong image" % type(images).__name__)
+    a.w1p_all, a.w2p_all = images.w1p.data_ptr(), images.w2p.data_ptr()
+    a.b_dil_all, a.b_out_all = images.b_dil.data_ptr(), images.b_out.data_ptr()
+    if images.w1w is not None:
+        a.w1w_all, a.w2w_all = images.w1w.data_ptr(), images.w2w.data_ptr()
+    x3 = images.wx3
     if x3 is not None:
         a.wx3_all, a.x3_mode = x3.data.data_ptr(), x3.mode
-    if len(packs) < 8 or packs[6] is None or stack_variant(B, T, dcl, x3_mode=x3.mode if x3 is not None else 0) != 3:
+    if images.w1s is None or stack_variant(B, T, dcl, x3_mode=x3.mode if x3 is not None else 0) != 3:
         return None
-    a.w1s_all, a.w2s_all = packs[6].data_ptr(), packs[7].data_ptr()
+    a.w1s_all, a.w2s_all = images.w1s.data_ptr(), images.w2s.data_ptr()
     z_ws = torch.empty(B * ((T + 31) // 32) * 256 * 32, dtype=torch.float32, device=dev)
     a.z_ws = z_ws.data_ptr()
     return z_ws
 
 
-def diffnet_stack(xa, xb, skip, condproj, dstep_ptr, d_bs, d_cs, d_ls, packs, dilation_cycle_length, sync_ws=None,
+def diffnet_stack(xa, xb, skip, condproj, dstep_ptr, d_bs, d_cs, d_ls, images, dilation_cycle_length, sync_ws=None,
                   x_all=None, save_y=None, save_z=None, err_flag=None):
-    """All L layers in one persistent launch.  condproj [B, L*512, T]; packs = (w1p_all, w2p_all, b_dil_all, b_out_all
-    [, w1w_all, w2w_all [, w1s_all, w2s_all [, wx3_all]]]).  Training forward (Winograd kernel only): x_all [L+1,B,256,T] (slab 0 = input) replaces the
-    xa/xb ping-pong, save_y [L,B,512,T] / save_z [L,B,256,T] receive what the backward pass needs.
+    """All L layers in one persistent launch.  condproj [B, L*512, T]; images: a StackImages (a bare tuple is a TypeError).
+    Training forward (Winograd kernel only): x_all [L+1,B,256,T] (slab 0 = input) replaces the xa/xb ping-pong, save_y [L,B,512,T] /
+    save_z [L,B,256,T] receive what the backward pass needs.
     Returns sync_ws (int32; [1] != 0 means a dependency wait timed out)."""
-    _f(xa), _f(xb), _f(skip), _f(condproj)
     B, Cc, T = xa.shape
     assert Cc == 256
-    w1p_all, w2p_all, b_dil_all, b_out_all = packs[:4]
-    L = b_dil_all.shape[0]
+    a = SetDiffnetStackArgs()  # (the images first: a bare tuple is refused before anything else is looked at)
+    z_ws = _set_images(a, images, B, T, dilation_cycle_length, xa.device)  # noqa: F841 (kept alive until the launch is enqueued)
+    _f(xa), _f(xb), _f(skip), _f(condproj)
+    L = images.b_dil.shape[0]
     if sync_ws is None:
         sync_ws = torch.empty(sync_ws_size(B, T), dtype=torch.int32, device=xa.device)
-    a = SetDiffnetStackArgs()
     a.xa, a.xb, a.skip = xa.data_ptr(), xb.data_ptr(), skip.data_ptr()
     a.condproj, a.dstep = condproj.data_ptr(), dstep_ptr
-    a.w1p_all, a.w2p_all = w1p_all.data_ptr(), w2p_all.data_ptr()
-    a.b_dil_all, a.b_out_all = b_dil_all.data_ptr(), b_out_all.data_ptr()
-    if len(packs) >= 6 and packs[4] is not None:
-        a.w1w_all, a.w2w_all = packs[4].data_ptr(), packs[5].data_ptr()
     if x_all is not None:
         a.x_all, a.save_y, a.save_z = _f(x_all).data_ptr(), _f(save_y).data_ptr(), _f(save_z).data_ptr()
-    z_ws = _split_images(a, packs, B, T, dilation_cycle_length, xa.device)  # noqa: F841 (kept alive until the launch is enqueued)
     if err_flag is not None:  # optional sticky int32 error word (1: a dependency wait timed out, 2: out of the fp16 split range)
         a.err_flag = err_flag.data_ptr()
     a.sync_ws = sync_ws.data_ptr()
@@ -971,6 +1009,7 @@ def diffusion_loop(*, x, noise, seed, condproj, dstep, coef4, w_in, b_in, packs,
                    w_outp, b_outp, L, steps, dilation_cycle_length, want_layer_spans=False, n_groups=None,
                    persistent=None, bf16=None):
     """Enqueue the whole reverse loop (set_diffusion_loop).  x [B,M,T] is updated in place.
+    packs: the layer stack's StackImages (DiffNet.fused_packs()).
     bf16 = dict(cond=[B,192,T] fp32, imgs=[L, n] bf16 layer images, b_cond=[L,512]): the opt-in bf16-operand loop
     (condproj is then unused and may be None)."""
     _f(x), _f(noise), _f(condproj), _f(dstep), _f(coef4)
@@ -995,12 +1034,7 @@ def diffusion_loop(*, x, noise, seed, condproj, dstep, coef4, w_in, b_in, packs,
             bf16_ws = torch.empty(n_ws, dtype=torch.float32, device=dev)  # noqa: F841 (kept alive until the loop is enqueued: stream-ordered free)
             a.bf16_ws, a.bf16_ws_floats = bf16_ws.data_ptr(), n_ws
     a.w_in_p, a.b_in = w_in.packed().data_ptr(), b_in.data_ptr()
-    w1p_all, w2p_all, b_dil_all, b_out_all = packs[:4]
-    a.w1p_all, a.w2p_all = w1p_all.data_ptr(), w2p_all.data_ptr()
-    a.b_dil_all, a.b_out_all = b_dil_all.data_ptr(), b_out_all.data_ptr()
-    if len(packs) >= 6 and packs[4] is not None:
-        a.w1w_all, a.w2w_all = packs[4].data_ptr(), packs[5].data_ptr()
-    z_ws = _split_images(a, packs, B, T, dilation_cycle_length, dev)  # noqa: F841
+    z_ws = _set_images(a, packs, B, T, dilation_cycle_length, dev)  # noqa: F841 (kept alive until the loop is enqueued)
     a.persistent = int(default_persistent() if persistent is None else bool(persistent))
     sync_ws = torch.empty(sync_ws_size(B, T), dtype=torch.int32, device=dev)
     a.sync_ws = sync_ws.data_ptr()

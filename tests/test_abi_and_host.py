@@ -486,17 +486,76 @@ def test_uniform_stride_of_layer_parameters():
     """Host logic of the grouped step projections (autograd_ops.step_projections): the per-layer weights must sit at ONE element stride
     (what the flat optimizer's buffer gives); anything else -> None -> one conv per layer."""
     import torch
-    from set_amd import autograd_ops as A
+    from set_amd import ops
     flat = torch.zeros(3 * 70 + 5)
     same = [flat[0:64].view(8, 8), flat[70:134].view(8, 8), flat[140:204].view(8, 8)]
-    assert A._uniform_stride(same) == 70
-    assert A._uniform_stride([same[0]]) == 64
-    assert A._uniform_stride([same[0], same[1], flat[141:205].view(8, 8)]) is None      # uneven gap
-    assert A._uniform_stride([same[1], same[0]]) is None                                 # descending addresses
-    assert A._uniform_stride([same[0], same[1].t()]) is None                             # not contiguous
-    assert A._uniform_stride([same[0], same[1].double()]) is None                        # another dtype
-    r = A._uniform_stride([torch.zeros(8, 8), torch.zeros(8, 8), torch.zeros(8, 8)])  # separate allocations: None or a real stride
+    assert ops._uniform_stride(same) == 70
+    assert ops._uniform_stride([same[0]]) == 64
+    assert ops._uniform_stride([same[0], same[1], flat[141:205].view(8, 8)]) is None      # uneven gap
+    assert ops._uniform_stride([same[1], same[0]]) is None                                 # descending addresses
+    assert ops._uniform_stride([same[0], same[1].t()]) is None                             # not contiguous
+    assert ops._uniform_stride([same[0], same[1].double()]) is None                        # another dtype
+    r = ops._uniform_stride([torch.zeros(8, 8), torch.zeros(8, 8), torch.zeros(8, 8)])  # separate allocations: None or a real stride
     assert r is None or r >= 64
+
+
+def test_tape_tgt_is_the_one_gradient_target_rule():
+    """autograd_ops._tape_tgt: the optimizer's .grad view (handing autograd None) when the owner gives one, else a zeroed temporary of the
+    parameter's shape that autograd accumulates; a ConvWeight row slice of a larger parameter never goes in place and never asks the owner
+    (FlatAdamW.sink counts every request during its first step: a second one would switch in-place gradients off for the parameter)."""
+    import torch
+    from set_amd import autograd_ops as A, ops
+
+    class Owner:
+        def __init__(self):
+            self.calls = {}
+
+        def sink(self, param):
+            self.calls[id(param)] = self.calls.get(id(param), 0) + 1
+            return param.grad
+
+    dev = torch.device("cpu")
+    owner = Owner()
+    owned = torch.nn.Parameter(torch.randn(6, 4, 3))
+    owned.grad = torch.ones(6, 4, 3)
+    owned._flat_owner = owner
+    assert A.grad_sink(owned) is owned.grad and A.grad_sink(None) is None
+    owner.calls.clear()
+    tgt, ret = A._tape_tgt(owned, dev)
+    assert tgt is owned.grad and ret is None and owner.calls == {id(owned): 1}
+    tgt, ret = A._tape_tgt(owned, dev, ops.ConvWeight(owned, 6, 4, 3))           # a conv over the whole parameter: the same
+    assert tgt is owned.grad and ret is None and owner.calls == {id(owned): 2}
+    free = torch.nn.Parameter(torch.randn(5, 7))
+    tgt, ret = A._tape_tgt(free, dev)
+    assert tgt is ret and tuple(tgt.shape) == (5, 7) and tgt.dtype == torch.float32 and not tgt.any()
+    assert A.grad_sink(free) is None
+    # rows [2, 6) of the owned parameter (a packed projection read through base != 0), and rows [0, 2) (base 0, but not the whole of it)
+    owner.calls.clear()
+    for cw in (ops.ConvWeight(owned, 4, 4, 3, base=2 * 4 * 3), ops.ConvWeight(owned, 2, 4, 3)):
+        tgt, ret = A._tape_tgt(owned, dev, cw)
+        assert tgt is ret and tgt is not owned.grad and tuple(tgt.shape) == (6, 4, 3) and not tgt.any()
+    assert owner.calls == {}
+    # an owner that declines (first step, parameter used more than once): a temporary, after exactly one request
+    owned.grad = None
+    tgt, ret = A._tape_tgt(owned, dev)
+    assert tgt is ret and not tgt.any() and owner.calls == {id(owned): 1}
+
+
+def test_diffnet_stack_refuses_a_bare_tuple():
+    """ops.diffnet_stack takes its weight images as an ops.StackImages (fields by name): a tuple in the old positional order is a TypeError
+    before anything is launched (refused on the host: no device needed)."""
+    import pytest as _pt
+    import torch
+    from set_amd import ops
+    assert ops.StackImages._fields == ("w1p", "w2p", "b_dil", "b_out", "w1w", "w2w", "w1s", "w2s", "wx3")
+    L, B, T = 2, 1, 32
+    w1, w2, bd, bo = torch.zeros(L, 512 * 768), torch.zeros(L, 512 * 256), torch.zeros(L, 512), torch.zeros(L, 512)
+    imgs = ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo)
+    assert imgs.w1w is None and imgs.w2w is None and imgs.w1s is None and imgs.w2s is None and imgs.wx3 is None
+    x, cp = torch.zeros(B, 256, T), torch.zeros(B, L * 512, T)
+    for bare in ((w1, w2, bd, bo), (w1, w2, bd, bo, None, None, None, None, None), [w1, w2, bd, bo]):
+        with _pt.raises(TypeError, match="StackImages"):
+            ops.diffnet_stack(x, x.clone(), x.clone(), cp, 0, 0, 1, 256, bare, 1)
 
 
 def test_unreachable_parameters_sit_behind_the_exchanged_part_of_the_flat_buffer():

@@ -409,7 +409,7 @@ def test_persistent_stack_bit_identical_to_layer_launches(dev):
         torch.cuda.synchronize()
         for rep in range(reps):
             xa, xb, skip = x0.clone(), torch.full_like(x0, float("nan")), torch.full_like(x0, float("nan"))
-            ws = ops.diffnet_stack(xa, xb, skip, cp, dtab.data_ptr() + 4 * col, 0, 3, 256 * 3, (w1, w2, bd, bo), dcl)
+            ws = ops.diffnet_stack(xa, xb, skip, cp, dtab.data_ptr() + 4 * col, 0, 3, 256 * 3, ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo), dcl)
             torch.cuda.synchronize()
             assert int(ws[1]) == 0, "dependency wait timed out"
             assert int(ws[0]) >= L * B * ((T + 63) // 64)
@@ -437,7 +437,8 @@ def test_row_split_stack_bit_identical_to_layer_launches(dev, monkeypatch):
             wd = (torch.randn(512, 256, 3, generator=g) / 27.7).to(dev)
             wo = (torch.randn(512, 256, 1, generator=g) / 16.0).to(dev)
             ops.pack_diffnet_layer(wd, wo, w1[l], w2[l])
-        packs = (w1, w2, bd, bo, None, None) + ops.split_images(w1, w2)
+        w1s, w2s = ops.split_images(w1, w2)
+        packs = ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, w1s=w1s, w2s=w2s)
         col = 2
         h, nxt, skip_ref = x0.clone(), torch.empty_like(x0), torch.empty_like(x0)
         for l in range(L):
@@ -533,7 +534,8 @@ def _random_stack(dev, B, T, L, seed, x3_mode=3):
         ops.pack_diffnet_layer(wd, wo, w1[l], w2[l])
         wx3.pack(l, wd, wo)
         wds.append(wd), wos.append(wo)
-    packs = (w1, w2, bd, bo, None, None) + ops.split_images(w1, w2) + (wx3,)
+    w1s, w2s = ops.split_images(w1, w2)
+    packs = ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, w1s=w1s, w2s=w2s, wx3=wx3)
     return x0, cp, dtab, packs, wds, wos, bd, bo
 
 
@@ -758,7 +760,7 @@ def test_winograd_stack_matches_direct_stack(dev, monkeypatch):
             wo = (torch.randn(512, 256, 1, generator=g) / 16.0).to(dev)
             ops.pack_diffnet_layer(wd, wo, w1[l], w2[l])
             ops.pack_diffnet_layer_wino(wd, wo, w1w[l], w2w[l])
-        packs = (w1, w2, bd, bo, w1w, w2w)
+        packs = ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, w1w=w1w, w2w=w2w)
 
         def run(mode):
             monkeypatch.setenv("SET_AMD_WINO", mode)
@@ -782,7 +784,7 @@ def test_winograd_stack_matches_direct_stack(dev, monkeypatch):
     for dcl, Ld in ((2, 4), (3, 6), (4, 8)):
         monkeypatch.setenv("SET_AMD_WINO", "2")
         xa, xb, skip = x0.clone(), torch.empty_like(x0), torch.empty_like(x0)
-        pk = tuple(p[:Ld] if p is not None else None for p in packs)
+        pk = ops.StackImages(**{k: (p[:Ld] if p is not None else None) for k, p in packs._asdict().items()})
         ops.diffnet_stack(xa, xb, skip, cp, dtab.data_ptr() + 4, 0, 3, 256 * 3, pk, dcl)
         monkeypatch.setenv("SET_AMD_WINO", "0")
         ya, yb, skip2 = x0.clone(), torch.empty_like(x0), torch.empty_like(x0)
@@ -834,7 +836,7 @@ def test_winograd_stack_soak_is_bit_stable(dev, monkeypatch):
         wo = (torch.randn(512, 256, 1, generator=g) / 16.0).to(dev)
         ops.pack_diffnet_layer(wd, wo, w1[l], w2[l])
         ops.pack_diffnet_layer_wino(wd, wo, w1w[l], w2w[l])
-    packs = (w1, w2, bd, bo, w1w, w2w)
+    packs = ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, w1w=w1w, w2w=w2w)
     ref = None
     n_runs = 0
     for grid in (None, "256", "200", "131", "64"):
@@ -1474,7 +1476,8 @@ def test_split_operand_stack_on_heavy_tailed_weights_and_activations(dev, monkey
         ops.pack_diffnet_layer(wd, wo, w1[l], w2[l])
         wx3.pack(l, wd, wo)
         wds.append(wd), wos.append(wo)
-    packs = (w1, w2, bd, bo, None, None) + ops.split_images(w1, w2) + (wx3,)
+    w1s, w2s = ops.split_images(w1, w2)
+    packs = ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, w1s=w1s, w2s=w2s, wx3=wx3)
 
     def run(x3, wino):
         monkeypatch.setenv("SET_AMD_X3", x3)

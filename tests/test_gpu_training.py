@@ -614,7 +614,7 @@ def test_step_projections_of_all_layers_equal_the_per_layer_linears(dev, L_, Cc,
     """diffusion_projection of every residual layer in one launch (reference diffnet.py:66,72; csrc/train.hip step_proj_*): forward
     and every gradient against fp64 torch Linear layers; parameters at one stride inside a flat buffer (what the flat optimizer
     builds), gradients handed back through autograd (no sinks here).  fp32 FMA chains: 1e-5 relative."""
-    from set_amd import autograd_ops as A
+    from set_amd import autograd_ops as A, ops
     g = torch.Generator().manual_seed(L_ * 1000 + Cc + N)
     per = Cc * Cc + Cc + gap
     flat = (torch.randn(L_ * per, generator=g) / math.sqrt(Cc)).to(dev)
@@ -622,7 +622,7 @@ def test_step_projections_of_all_layers_equal_the_per_layer_linears(dev, L_, Cc,
     bs = [flat[l * per + Cc * Cc:l * per + Cc * Cc + Cc].requires_grad_(True) for l in range(L_)]
     h = torch.randn(1, Cc, N, generator=g).to(dev).requires_grad_(True)
     gy = torch.randn(N, L_ * Cc, generator=g).to(dev)
-    assert A._uniform_stride(ws) == per and A._uniform_stride(bs) == per
+    assert ops._uniform_stride(ws) == per and ops._uniform_stride(bs) == per
     with torch.enable_grad():
         out = A._StepProjFn.apply(h, per, per, *ws, *bs)
         out.backward(gy)
@@ -646,19 +646,19 @@ def test_step_projections_of_all_layers_equal_the_per_layer_linears(dev, L_, Cc,
 
 
 def test_step_projections_fall_back_when_the_layers_are_not_at_one_stride(dev):
-    from set_amd import autograd_ops as A
+    from set_amd import autograd_ops as A, ops
     ws = [torch.randn(64, 64, device=dev), torch.randn(64, 64, device=dev), torch.randn(70, 64, device=dev)[:64]]
     ws2 = [torch.randn(64, 64, device=dev) for _ in range(2)] + [torch.randn(64, 64, device=dev).t()]
-    assert A._uniform_stride(ws2) is None
+    assert ops._uniform_stride(ws2) is None
     flat = torch.randn(3 * 64 * 64 + 5, device=dev)
-    assert A._uniform_stride([flat[0:4096].view(64, 64), flat[4096:8192].view(64, 64), flat[8197:].view(64, 64)]) is None
+    assert ops._uniform_stride([flat[0:4096].view(64, 64), flat[4096:8192].view(64, 64), flat[8197:].view(64, 64)]) is None
 
 
 def test_training_step_with_grouped_step_projections_equals_the_per_layer_path(dev, monkeypatch):
     """The whole loss + gradient computation (fp32, fused layer stack) with the 20 diffusion_projection layers laid out at one stride
     (as the flat optimizer lays them out) -> `set_step_proj_*` -- against the same step with SET_AMD_STEP_PROJ=0 (one 1x1 conv per
     layer): losses to 1e-6, every gradient to 2e-5 of its largest entry."""
-    from set_amd import autograd_ops as A
+    from set_amd import autograd_ops as A, ops
     monkeypatch.setenv("SET_AMD_WINO", "2")  # two utterances: force the kernel choice (and with it the fused path) of the big batches
     task, _ = _train_setup(dev, 8, 18)
     layers = list(task.model.denoise_fn.residual_layers)
@@ -671,7 +671,7 @@ def test_training_step_with_grouped_step_projections_equals_the_per_layer_path(d
         flat[l * per + Cc * Cc:(l + 1) * per].copy_(b.data)
         w.data = flat[l * per:l * per + Cc * Cc].view(Cc, Cc)
         b.data = flat[l * per + Cc * Cc:(l + 1) * per]
-    assert A._uniform_stride([ly.diffusion_projection.weight for ly in layers]) == per
+    assert ops._uniform_stride([ly.diffusion_projection.weight for ly in layers]) == per
     calls = []
     real = A._StepProjFn.apply
     monkeypatch.setattr(A, "step_projections", (lambda f: (lambda dn, h: (calls.append(1), f(dn, h))[1]))(A.step_projections))
@@ -909,11 +909,11 @@ def test_batched_fp32_image_repack_equals_the_per_image_packs_and_marks_them_cur
     packs = net.fused_packs(inference=False)
     for i, l in enumerate(net.residual_layers):
         w1, w2 = ops.pack_diffnet_layer(l.dilated_conv.weight.detach(), l.output_projection.weight.detach())
-        assert torch.equal(packs[0][i], w1) and torch.equal(packs[1][i], w2), i
-        if packs[4] is not None:
-            a, b = torch.empty_like(packs[4][i]), torch.empty_like(packs[5][i])
+        assert torch.equal(packs.w1p[i], w1) and torch.equal(packs.w2p[i], w2), i
+        if packs.w1w is not None:
+            a, b = torch.empty_like(packs.w1w[i]), torch.empty_like(packs.w2w[i])
             ops.pack_diffnet_layer_wino(l.dilated_conv.weight.detach(), l.output_projection.weight.detach(), a, b)
-            assert torch.equal(packs[4][i], a) and torch.equal(packs[5][i], b), i
+            assert torch.equal(packs.w1w[i], a) and torch.equal(packs.w2w[i], b), i
     # nothing left for the lazy path: a third step asks for the same images and finds them current
     calls = []
     real = L.set_pack_conv_weight

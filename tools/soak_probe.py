@@ -25,7 +25,7 @@ for (B, T, L, dcl, wino) in SHAPES:
     ref, bad, aborts = None, 0, 0
     for it in range(N):
         xa, xb, skip = x0.clone(), torch.empty_like(x0), torch.empty_like(x0)
-        ws = ops.diffnet_stack(xa, xb, skip, cp, dtab.data_ptr(), 0, 1, 256, (w1, w2, bd, bo, w1w, w2w), dcl)
+        ws = ops.diffnet_stack(xa, xb, skip, cp, dtab.data_ptr(), 0, 1, 256, ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, w1w=w1w, w2w=w2w), dcl)
         out = xa if L % 2 == 0 else xb
         if ref is None:
             ref = (out.clone(), skip.clone())

@@ -28,7 +28,8 @@ for (B, T, L, dcl, mode, env) in SHAPES:
     for l in range(L):
         wd = (torch.randn(512, 256, 3, generator=g) / 27.7).to(dev); wo = (torch.randn(512, 256, 1, generator=g) / 16.0).to(dev)
         ops.pack_diffnet_layer(wd, wo, w1[l], w2[l]); wx3.pack(l, wd, wo)
-    packs = (w1, w2, bd, bo, None, None) + ops.split_images(w1, w2) + (wx3,)
+    w1s, w2s = ops.split_images(w1, w2)
+    packs = ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, w1s=w1s, w2s=w2s, wx3=wx3)
     for k in ("SET_AMD_X3", "SET_AMD_SPLIT", "SET_AMD_X3_TILE", "SET_AMD_SPLIT_F32"):
         os.environ.pop(k, None)
     os.environ.update(env)

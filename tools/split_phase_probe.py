@@ -20,7 +20,8 @@ if os.environ.get("X2", "1") != "0":  # the two-piece fp16 variant of the row-sp
     g2 = torch.Generator().manual_seed(1)
     for l in range(L):
         wx3.pack(l, (torch.randn(512, 256, 3, generator=g2) / 27.7).to(dev), (torch.randn(512, 256, 1, generator=g2) / 16).to(dev))
-packs = (w1, w2, bd, bo, None, None) + ops.split_images(w1, w2) + (wx3,)
+w1s, w2s = ops.split_images(w1, w2)
+packs = ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, w1s=w1s, w2s=w2s, wx3=wx3)
 buf = torch.zeros(32, dtype=torch.int64, device=dev)
 for B, T in [tuple(int(v) for v in s.split("x")) for s in os.environ.get("SIZES", "1x800,2x800,4x800").split(",")]:
     x0 = torch.randn(B, 256, T, device=dev); cp = torch.randn(B, L * 512, T, device=dev) * 0.5

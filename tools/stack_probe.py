@@ -17,7 +17,7 @@ w2 = torch.randn(L, 512 * 256, generator=g).to(dev) / 16
 bd = torch.zeros(L, 512, device=dev); bo = torch.zeros(L, 512, device=dev)
 xa, xb, skip = x0.clone(), torch.empty_like(x0), torch.empty_like(x0)
 def stack():
-    return ops.diffnet_stack(xa, xb, skip, cp, dtab.data_ptr(), 0, 1, 256, (w1, w2, bd, bo), 1)
+    return ops.diffnet_stack(xa, xb, skip, cp, dtab.data_ptr(), 0, 1, 256, ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo), 1)
 def layers():
     h, nxt = xa, xb
     for l in range(L):

@@ -25,7 +25,7 @@ for mode in ("0", "2"):
     os.environ["SET_AMD_WINO"] = mode
     xa, xb, skip = x0.clone(), torch.zeros_like(x0), torch.zeros_like(x0)
     def stack():
-        return ops.diffnet_stack(xa, xb, skip, cp, dtab.data_ptr(), 0, 1, 256, (w1, w2, bd, bo, w1w, w2w), 1)
+        return ops.diffnet_stack(xa, xb, skip, cp, dtab.data_ptr(), 0, 1, 256, ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, w1w=w1w, w2w=w2w), 1)
     ws = stack(); torch.cuda.synchronize()
     out = (xa if L % 2 == 0 else xb).clone(); res[mode] = (out, skip.clone())
     for _ in range(2): stack()

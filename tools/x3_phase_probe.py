@@ -16,7 +16,7 @@ for l in range(L):
     wd, wo = (torch.randn(512, 256, 3, generator=g) / 27.7).to(dev), (torch.randn(512, 256, 1, generator=g) / 16).to(dev)
     ops.pack_diffnet_layer(wd, wo, w1[l], w2[l]); wx3.pack(l, wd, wo)
 bd = torch.zeros(L, 512, device=dev); bo = torch.zeros(L, 512, device=dev)
-packs = (w1, w2, bd, bo, None, None, None, None, wx3)
+packs = ops.StackImages(w1p=w1, w2p=w2, b_dil=bd, b_out=bo, wx3=wx3)
 buf = torch.zeros(32, dtype=torch.int64, device=dev)
 os.environ["SET_AMD_X3"] = "2"
 for B, T in [tuple(int(v) for v in s.split("x")) for s in os.environ.get("SIZES", "32x800").split(",")]:
