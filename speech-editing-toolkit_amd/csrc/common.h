@@ -168,13 +168,6 @@ __device__ __forceinline__ void buf_store_agent(float v, rsrc_t r, unsigned voff
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, (int)soff, 16);
 }
 
-// ---- inter-block flags of the persistent stack kernels (diffnet.hip, diffnet_x3.hip) ------------------------------
-// relaxed agent-scope load of a flag that other blocks publish; the waiting lane follows its wait with one acquire fence
-__device__ __forceinline__ int ld_agent(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// polls before a bounded wait gives up, raises the abort flag and fails the launch
-constexpr unsigned STACK_SPIN_LIMIT = 1u << 22;  // task-queue dependency waits, s_sleep(8) per poll: ~1 s
-constexpr unsigned SPLIT_SPIN_LIMIT = 1u << 20;  // row-split kernels (small batches), ~1 us per poll (two agent-scope loads + s_sleep(1)): ~1-2 s
-
 // two fp32 values -> their two-piece fp16 splittings (a0 + a1 = a to 22 significand bits), each piece pair packed into one dword with the
 // first value in the low half: v_cvt_pk_f16_f32, two back-conversions, v_pk_add_f32, v_cvt_pk_f16_f32 -- five instructions where two
 // scalar splittings and their packing take ten.  Same roundings (to nearest even, twice) as `h0 = (f16)a; h1 = (f16)(a - (float)h0)`.

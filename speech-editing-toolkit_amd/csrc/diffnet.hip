@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "boundary_x2.h"
+#include "stack_queue.h"
 
 namespace {
 
@@ -529,16 +530,16 @@ __device__ __forceinline__ void wino_main(const LayerTile &a, f32x16 (&m)[2][4],
 // ---- persistent layer stack: (layer, tile) task queue + per-tile epoch flags -----------------------------------
 // Inter-workgroup hand-off follows cdna_hip_programming.md Guideline 16: producer = every wave drains vmcnt,
 // __syncthreads, ONE lane agent-scope release fence + asm vmcnt(0) + relaxed agent flag store; consumer = ONE lane
-// polls relaxed, ONE agent-scope acquire, __syncthreads, then plain loads.  Every spin is bounded (ld_agent, STACK_SPIN_LIMIT: common.h).
+// polls relaxed, ONE agent-scope acquire, __syncthreads, then plain loads.  Every spin is bounded (stack_wait: stack_queue.h).
 template <int NCB, int GS, int WPS>
 __global__ void __launch_bounds__(256, WPS) diffnet_stack_kernel(SetDiffnetStackArgs a, int tiles_per_utt, int ntiles,
                                                                 int ntasks, int task_slot) {
     constexpr int NTt = 32 * NCB;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int *s_task = reinterpret_cast<int *>(smem + task_slot);  // inside the ONE dynamic LDS array
-    int *counter = a.sync_ws, *abort_flag = a.sync_ws + 1, *done = a.sync_ws + 4;
+    int *counter = a.sync_ws + SQ_COUNTER, *abort_flag = a.sync_ws + SQ_ABORT, *done = a.sync_ws + SQ_FLAGS;
     const int tid = threadIdx.x;
-    uint64_t wait_ticks = 0, fence_ticks = 0;  // diagnostics (lane 0 only): summed into sync_ws[2], sync_ws[3]
+    uint64_t wait_ticks = 0, fence_ticks = 0;  // diagnostics (lane 0 only): summed into SQ_WAIT_TICKS, SQ_FENCE_TICKS
     for (;;) {
         __syncthreads();  // LDS (tile + task slot) of the previous task is free
         if (tid == 0) {
@@ -546,20 +547,8 @@ __global__ void __launch_bounds__(256, WPS) diffnet_stack_kernel(SetDiffnetStack
             int n = atomicAdd(counter, 1);
             if (n < ntasks && n >= ntiles) {  // layer >= 1: wait for the three producer tiles of layer l-1
                 const int l = n / ntiles, i = n - l * ntiles, j = i % tiles_per_utt;
-                unsigned spins = 0;
                 const int *f0 = done + i, *fl = done + (j > 0 ? i - 1 : i), *fr = done + (j < tiles_per_utt - 1 ? i + 1 : i);
-                for (;;) {
-                    const int v0 = ld_agent(f0), v1 = ld_agent(fl), v2 = ld_agent(fr);  // three independent loads
-                    if (min(v0, min(v1, v2)) >= l) break;
-                    __builtin_amdgcn_s_sleep(8);
-                    if (++spins > STACK_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
-                        __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (a.err_flag) __hip_atomic_store(a.err_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        n = ntasks;
-                        break;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                n = stack_wait_tiles(f0, fl, fr, l, abort_flag, a.err_flag, n, ntasks);
             }
             wait_ticks += __builtin_amdgcn_s_memtime() - tw0;
             *s_task = n;
@@ -568,8 +557,8 @@ __global__ void __launch_bounds__(256, WPS) diffnet_stack_kernel(SetDiffnetStack
         const int n = __builtin_amdgcn_readfirstlane(*s_task);
         if (n >= ntasks) {
             if (tid == 0) {  // units of 1024 ticks
-                atomicAdd(a.sync_ws + 2, (int)(wait_ticks >> 10));
-                atomicAdd(a.sync_ws + 3, (int)(fence_ticks >> 10));
+                atomicAdd(a.sync_ws + SQ_WAIT_TICKS, (int)(wait_ticks >> 10));
+                atomicAdd(a.sync_ws + SQ_FENCE_TICKS, (int)(fence_ticks >> 10));
             }
             break;
         }
@@ -596,7 +585,7 @@ __global__ void __launch_bounds__(256, WPS) diffnet_stack_kernel(SetDiffnetStack
         __syncthreads();
         if (tid == 0) {
             const uint64_t tf0 = __builtin_amdgcn_s_memtime();
-            __hip_atomic_store(done + i, l + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            stack_publish_store(done, i, l, STACK_NO_FAULT_TILE, false);
             fence_ticks += __builtin_amdgcn_s_memtime() - tf0;
         }
     }
@@ -667,30 +656,12 @@ __device__ __forceinline__ void split_gemm(f32x16 &acc, const float *wp, float (
 // debug: lane 0 of block (tile 1, part 1) adds the s_memtime ticks of its phases, summed over the layers, to buf[0..7]
 __device__ uint64_t *g_split_phase_buf = nullptr;
 
-// lane 0 of the block: wait until all three counters reach `want`; false = gave up (spin limit or another block aborted)
-__device__ __forceinline__ bool split_wait(const int *f0, const int *f1, const int *f2, int want, int *abort_flag,
-                                           int *err_flag) {
-    unsigned spins = 0;
-    for (;;) {
-        const int v0 = ld_agent(f0), v1 = ld_agent(f1), v2 = ld_agent(f2);
-        if (min(v0, min(v1, v2)) >= want) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > SPLIT_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
-            __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (err_flag) __hip_atomic_store(err_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return false;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    return true;
-}
-
 __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetStackArgs a, int tiles_per_utt, int ntiles,
                                                                     int fault_tile) {
     extern __shared__ __attribute__((aligned(16))) float smem[];  // x tile [256][32 + 2d]; the z tile [256][32] overlays it
     float *gs = smem + DC * SP_XW;                                // [64][32] tanh(filter rows) of this part
     int *s_ok = reinterpret_cast<int *>(gs + 64 * 32);
-    int *abort_flag = a.sync_ws + 1, *ready = a.sync_ws + 4, *zcnt = a.sync_ws + 4 + ntiles;
+    int *abort_flag = a.sync_ws + SQ_ABORT, *ready = a.sync_ws + SQ_FLAGS, *zcnt = a.sync_ws + sq_flags2(ntiles);
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
     const int j = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = blockIdx.x >> 2, h = blockIdx.x & 3;
@@ -729,7 +700,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
         float Ap[64];  // first 64 k-steps of the wave's weight rows (cold in L2): in flight during the wait and the staging
         const float *wp1 = a.w1s_all + (int64_t)l * (512 * 768) + (int64_t)vr * KS1 * 64 + lane;
         split_preload(Ap, wp1);
-        if (tid == 0) *s_ok = (l == 0 || split_wait(ready + i, ready + il, ready + ir, 4 * l, abort_flag, a.err_flag)) ? 1 : 0;
+        if (tid == 0) *s_ok = l == 0 ? 1 : stack_wait_parts(ready + i, ready + il, ready + ir, 4 * l, abort_flag, a.err_flag, true);
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(*s_ok) == 0) return;
         SP_PHASE(0)
@@ -772,7 +743,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the z rows of this wave are visible to every XCD
         __syncthreads();
-        if (tid == 0) __hip_atomic_fetch_add(zcnt + i, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) stack_publish_add(zcnt, i, l, fault_tile, false);
         SP_PHASE(3)
         // ---- GEMM 2 accumulator = b_out + x (residual rows) / + running skip sum (skip rows): these rows were written
         //      by this very wave one layer ago; the loads fly while lane 0 waits for the other parts' z rows
@@ -795,7 +766,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
         }
         const float *wp2 = a.w2s_all + (int64_t)l * (512 * 256) + (int64_t)vr * KS2 * 64 + lane;
         split_preload(Ap, wp2);
-        if (tid == 0) *s_ok = split_wait(zcnt + i, zcnt + i, zcnt + i, 4 * (l + 1), abort_flag, a.err_flag) ? 1 : 0;
+        if (tid == 0) *s_ok = stack_wait_parts(zcnt + i, zcnt + i, zcnt + i, 4 * (l + 1), abort_flag, a.err_flag, true);
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(*s_ok) == 0) return;
         SP_PHASE(4)
@@ -824,8 +795,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // every store of the block has completed; the LDS tile is free for the next layer
-        if (tid == 0 && !(l == 0 && i == fault_tile && h == 0))
-            __hip_atomic_fetch_add(ready + i, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) stack_publish_add(ready, i, l, fault_tile, h == 0);
         SP_PHASE(7)
     }
 #undef SP_PHASE
@@ -841,7 +811,7 @@ __global__ void __launch_bounds__(512, 2) diffnet_stack_wino_kernel(SetDiffnetSt
                                                                     int ntasks, int concat, int fault_tile) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int *s_task = reinterpret_cast<int *>(smem + WN_ZS_OFF + DC * WN_NT);
-    int *counter = a.sync_ws, *abort_flag = a.sync_ws + 1, *done = a.sync_ws + 4;
+    int *counter = a.sync_ws + SQ_COUNTER, *abort_flag = a.sync_ws + SQ_ABORT, *done = a.sync_ws + SQ_FLAGS;
     const int tid = threadIdx.x;
     uint64_t wait_ticks = 0, fence_ticks = 0;
     if (tid == 0) s_task[0] = atomicAdd(counter, 1);
@@ -911,10 +881,7 @@ __global__ void __launch_bounds__(512, 2) diffnet_stack_wino_kernel(SetDiffnetSt
         if (tid == 0 && i_done >= 0) {
             const uint64_t tf0 = __builtin_amdgcn_s_memtime();
             // no release fence: the tile's stores are agent-scope write-through (wino_main's epilogue), drained above
-            // (fault_tile >= 0: test hook, SET_AMD_FAULT_TILE -- that tile of layer 0 is never published, so its
-            // consumers must run into the spin limit and the launch must report it)
-            if (!(l_done == 0 && i_done == fault_tile))
-                __hip_atomic_store(done + i_done, l_done + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            stack_publish_store(done, i_done, l_done, fault_tile);
             fence_ticks += __builtin_amdgcn_s_memtime() - tf0;
         }
     };
@@ -929,20 +896,8 @@ __global__ void __launch_bounds__(512, 2) diffnet_stack_wino_kernel(SetDiffnetSt
             int ok_all = 1;
             if (l > 0) {
                 const uint64_t tw0 = __builtin_amdgcn_s_memtime();
-                unsigned spins = 0;
                 const int *f0 = done + i, *fl = done + (j > 0 ? i - 1 : i), *fr = done + (j < tiles_per_utt - 1 ? i + 1 : i);
-                for (;;) {
-                    const int v0 = ld_agent(f0), v1 = ld_agent(fl), v2 = ld_agent(fr);  // three independent loads
-                    if (min(v0, min(v1, v2)) >= l) break;
-                    __builtin_amdgcn_s_sleep(8);
-                    if (++spins > STACK_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
-                        __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (a.err_flag) __hip_atomic_store(a.err_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ok_all = 0;
-                        break;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                ok_all = stack_wait_tiles(f0, fl, fr, l, abort_flag, a.err_flag);
                 wait_ticks += __builtin_amdgcn_s_memtime() - tw0;
             }
             s_task[1] = ok_all;
@@ -964,11 +919,11 @@ __global__ void __launch_bounds__(512, 2) diffnet_stack_wino_kernel(SetDiffnetSt
     publish();
 #ifdef SET_WINO_PHASES
     if (tid == 0)
-        for (int k = 0; k < 9; ++k) atomicAdd(a.sync_ws + 4 + ntiles + k, (int)(ph[k] >> 10));
+        for (int k = 0; k < 9; ++k) atomicAdd(a.sync_ws + sq_flags2(ntiles) + k, (int)(ph[k] >> 10));
 #endif
     if (tid == 0) {  // units of 1024 ticks
-        atomicAdd(a.sync_ws + 2, (int)(wait_ticks >> 10));
-        atomicAdd(a.sync_ws + 3, (int)(fence_ticks >> 10));
+        atomicAdd(a.sync_ws + SQ_WAIT_TICKS, (int)(wait_ticks >> 10));
+        atomicAdd(a.sync_ws + SQ_FENCE_TICKS, (int)(fence_ticks >> 10));
     }
 }
 
@@ -1136,7 +1091,7 @@ extern "C" int set_diffnet_stack_variant(int B, int T, int dilation_cycle_length
     return stack_variant(B, T, dilation_cycle_length, (images & 1) != 0, (images & 2) != 0, x3_mode_of_images(images), n_cu);
 }
 
-int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, int n_cu, int fault_tile, hipStream_t s);  // csrc/diffnet_x3.hip
+int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, int n_cu, hipStream_t s);                 // csrc/diffnet_x3.hip
 int set_x3_winograd_selected(int x3_mode, int B, int T, int dilation_cycle_length, int n_cu);                // csrc/diffnet_x3.hip (0 / 1 / 2)
 extern "C" int set_diffnet_stack_x3_winograd(int B, int T, int dilation_cycle_length, int images) {
     int n_cu = 256;
@@ -1145,7 +1100,7 @@ extern "C" int set_diffnet_stack_x3_winograd(int B, int T, int dilation_cycle_le
     if (stack_variant(B, T, dilation_cycle_length, (images & 1) != 0, (images & 2) != 0, x3_mode, n_cu) != 5) return 0;
     return set_x3_winograd_selected(x3_mode, B, T, dilation_cycle_length, n_cu);
 }
-int set_launch_diffnet_stack_split_x2(const SetDiffnetStackArgs &a, int fault_tile, hipStream_t s);      // csrc/diffnet_x3.hip
+int set_launch_diffnet_stack_split_x2(const SetDiffnetStackArgs &a, hipStream_t s);                       // csrc/diffnet_x3.hip
 
 extern "C" int set_diffnet_stack(const SetDiffnetStackArgs *args, void *stream) {
     SET_REQUIRE(args != nullptr, "set_diffnet_stack");
@@ -1169,16 +1124,14 @@ extern "C" int set_diffnet_stack(const SetDiffnetStackArgs *args, void *stream) 
     const bool plain = !a.x_all && !a.save_y && !a.save_z;
     const int variant = stack_variant(a.B, a.T, a.dilation_cycle_length, a.w1w_all && a.w2w_all,
                                       a.w1s_all && a.w2s_all && a.z_ws && plain, (a.wx3_all && plain) ? a.x3_mode : 0, n_cu);
-    int fault_tile = -1;  // test hook: never publish this tile of layer 0 (exercises the time-out / error path)
-    if (const char *e = getenv("SET_AMD_FAULT_TILE")) fault_tile = atoi(e);
-    if (variant >= 4) return set_launch_diffnet_stack_x3(a, n_cu, fault_tile, s);
+    if (variant >= 4) return set_launch_diffnet_stack_x3(a, n_cu, s);
     if (variant == 3 && a.wx3_all && a.x3_mode == 2 && !split_f32_pinned())
-        return set_launch_diffnet_stack_split_x2(a, fault_tile, s);  // the same scheme on the two-piece fp16 operands
+        return set_launch_diffnet_stack_split_x2(a, s);  // the same scheme on the two-piece fp16 operands
     if (variant == 3) {
         const int tiles = (a.T + 31) / 32, nt = a.B * tiles;
-        SET_HIP(set_zero_async(a.sync_ws, (size_t)(4 + 2 * nt) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
+        SET_HIP(set_zero_async(a.sync_ws, stack_sync_words(SQ_ROW_SPLIT, nt) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
         hipLaunchKernelGGL(diffnet_stack_split_kernel, dim3(4 * nt), dim3(256), (size_t)SP_LDS_FLOATS * sizeof(float), s, a,
-                           tiles, nt, fault_tile);
+                           tiles, nt, stack_fault_tile());
         return set_check_launch("set_diffnet_stack");
     }
     const bool wino = variant == 2;
@@ -1199,15 +1152,12 @@ extern "C" int set_diffnet_stack(const SetDiffnetStackArgs *args, void *stream) 
     const int max_dil = 1 << (a.dilation_cycle_length - 1);
     const int task_slot = DC * (ntt + 2 * max_dil);  // float index of the task word
     const size_t lds = (size_t)(task_slot + 4) * sizeof(float);
-    SET_HIP(set_zero_async(a.sync_ws, (size_t)(4 + ntiles + (wino ? 12 : 0)) * sizeof(int32_t), s),
+    SET_HIP(set_zero_async(a.sync_ws, stack_sync_words(wino ? SQ_WINO : SQ_QUEUE, ntiles) * sizeof(int32_t), s),
             "set_diffnet_stack(memset)");
     const int wps = wino ? 1 : 2;  // resident blocks per CU (three 168-VGPR blocks per CU measured slower: see DESIGN.md)
-    int grid = wps * n_cu;
-    if (grid > ntiles * 4 / 5) grid = ntiles * 4 / 5;
-    if (grid < n_cu) grid = n_cu < ntiles ? n_cu : ntiles;
-    if (const char *e = getenv("SET_AMD_STACK_GRID")) grid = atoi(e) > 0 ? atoi(e) : grid;
-    if ((int64_t)grid > ntasks64) grid = (int)ntasks64;
-    if (grid < 1) grid = 1;
+    // capped at 0.8x the tile count (see above), but a block on every CU while there are tiles for them
+    const int grid = stack_grid(wps * n_cu, ntiles, ntasks64, true, n_cu);
+    const int fault_tile = stack_fault_tile();
     if (wino) {
         if (a.dilation_cycle_length == 1)
             hipLaunchKernelGGL(diffnet_stack_wino_kernel<true>, dim3(grid), dim3(512),
@@ -1825,7 +1775,7 @@ static int diffusion_chain(const SetDiffLoopArgs &a, int g, int b0, int Bg, hipS
     float *ws_x0pred = a.ws_x0pred + (int64_t)b0 * per_batch;
     const float *condproj = a.condproj ? a.condproj + (int64_t)b0 * L * 512 * T : nullptr;
     const int tiles_per_utt = (T + NT - 1) / NT;
-    int32_t *sync_ws = a.sync_ws ? a.sync_ws + 16 * (int64_t)g + 2 * (int64_t)b0 * ((T + 31) / 32) : nullptr;  // per-group slice
+    int32_t *sync_ws = a.sync_ws ? a.sync_ws + SQ_GROUP_WORDS * (int64_t)g + 2 * (int64_t)b0 * ((T + 31) / 32) : nullptr;  // per-group slice
     const uint64_t quads_before = (uint64_t)((int64_t)b0 * per_batch / 4);
     const uint64_t quads_total = (uint64_t)(((int64_t)a.B * per_batch + 3) / 4);
     int rc = SET_OK;

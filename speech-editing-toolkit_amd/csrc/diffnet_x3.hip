@@ -35,6 +35,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "stack_queue.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
@@ -570,7 +571,7 @@ __global__ void __launch_bounds__(512 / NU, NU) diffnet_stack_x3_kernel(SetDiffn
                                                                         unsigned piece_bytes, int fault_tile) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     int *s_task = reinterpret_cast<int *>(lds + S::NP * piece_bytes + NCB * XC * sizeof(float));  // [0] next task, [1] peek result, [2] wait result
-    int *counter = a.sync_ws, *abort_flag = a.sync_ws + 1, *done = a.sync_ws + 4;
+    int *counter = a.sync_ws + SQ_COUNTER, *abort_flag = a.sync_ws + SQ_ABORT, *done = a.sync_ws + SQ_FLAGS;
     const int tid = threadIdx.x;
     uint64_t *dbg = (SET_X3_PROBE && blockIdx.x == 0 && tid == 0) ? g_x3_phase_buf : nullptr;
     uint64_t tprev = dbg ? __builtin_amdgcn_s_memtime() : 0;
@@ -585,17 +586,7 @@ __global__ void __launch_bounds__(512 / NU, NU) diffnet_stack_x3_kernel(SetDiffn
     while (n < ntasks) {
         const int l = n / ntiles, i = n - l * ntiles, j = i;  // one chain of tiles over the batch: neighbours are i - 1 / i + 1
         X3Tile lt;
-        lt.xin = (l & 1) ? a.xb : a.xa;
-        lt.xout = (l & 1) ? a.xa : a.xb;
-        lt.skp = a.skip;
-        lt.cp = a.condproj + (int64_t)l * a.cp_ls; lt.cp_bs = a.cp_bs;
-        lt.dstep = a.dstep + (int64_t)l * a.d_ls; lt.d_bs = a.d_bs; lt.d_cs = a.d_cs;
-        lt.img = reinterpret_cast<const unsigned short *>(a.wx3_all) + (int64_t)l * x_nimg<S>();
-        lt.b_dil = a.b_dil_all + (int64_t)l * 512;
-        lt.b_out = a.b_out_all + (int64_t)l * 512;
-        lt.err_flag = a.err_flag;
-        lt.T = a.T; lt.dil = 1 << (l % a.dilation_cycle_length); lt.first = (l == 0);
-        lt.nbu = (a.T + 31) / 32; lt.Q = a.B * lt.nbu; lt.q0 = i * NCB;
+        stack_fill_x3_tile(lt, a, l, i, NCB, 1 << (l % a.dilation_cycle_length), x_nimg<S>());
         f32x16 acc[NU][2][NCB];
         if constexpr (NU == 1) x3_init<NU, NCB>(lt, acc);  // issued before the previous tile's store drain / publish and before the dependency wait
         __builtin_amdgcn_sched_barrier(0);
@@ -617,27 +608,10 @@ __global__ void __launch_bounds__(512 / NU, NU) diffnet_stack_x3_kernel(SetDiffn
             s_task[1] = peek >= l ? 1 : 2;
         }
         __syncthreads();  // (also: the LDS tile is free)
-        if (tid == 0 && i_done >= 0 && !(l_done == 0 && i_done == fault_tile))
-            __hip_atomic_store(done + i_done, l_done + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0 && i_done >= 0) stack_publish_store(done, i_done, l_done, fault_tile);
         i_done = -1;
         if (__builtin_amdgcn_readfirstlane(s_task[1]) == 2) {  // producers not finished at the peek: wait for them now
-            if (tid == 0) {
-                int ok = 1;
-                unsigned spins = 0;
-                for (;;) {
-                    const int v0 = ld_agent(f0), v1 = ld_agent(fl), v2 = ld_agent(fr);
-                    if (min(v0, min(v1, v2)) >= l) break;
-                    __builtin_amdgcn_s_sleep(8);
-                    if (++spins > STACK_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
-                        __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (a.err_flag) __hip_atomic_store(a.err_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ok = 0;
-                        break;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                s_task[2] = ok;
-            }
+            if (tid == 0) s_task[2] = stack_wait_tiles(f0, fl, fr, l, abort_flag, a.err_flag);
             __syncthreads();
             if (__builtin_amdgcn_readfirstlane(s_task[2]) == 0) break;
         }
@@ -656,12 +630,11 @@ __global__ void __launch_bounds__(512 / NU, NU) diffnet_stack_x3_kernel(SetDiffn
     // the last finished tile
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid == 0 && i_done >= 0 && !(l_done == 0 && i_done == fault_tile))
-        __hip_atomic_store(done + i_done, l_done + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0 && i_done >= 0) stack_publish_store(done, i_done, l_done, fault_tile);
 }
 
 template <typename S, int NU, int NCB>
-int launch_x3(const SetDiffnetStackArgs &a, int n_cu, int fault_tile, hipStream_t s) {
+int launch_x3(const SetDiffnetStackArgs &a, int n_cu, hipStream_t s) {
     static SetDeviceOnce lds_once;
     if (int rc = set_lds_optin(lds_once, 160 * 1024, "set_diffnet_stack(x3 attr)", diffnet_stack_x3_kernel<S, NU, NCB>)) return rc;
     const int Q = a.B * ((a.T + 31) / 32);                    // 32-frame column blocks of the batch
@@ -672,16 +645,12 @@ int launch_x3(const SetDiffnetStackArgs &a, int n_cu, int fault_tile, hipStream_
     const int max_dil = 1 << (a.dilation_cycle_length - 1);
     const unsigned piece_bytes = (unsigned)(NCB * (32 + 2 * max_dil) * XR);  // every column block has its own halo rows
     const size_t ldsz = x3_lds_bytes<S, NCB>(max_dil);
-    SET_HIP(set_zero_async(a.sync_ws, (size_t)(4 + ntiles) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
+    SET_HIP(set_zero_async(a.sync_ws, stack_sync_words(SQ_QUEUE, ntiles) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
     // workers stay below the runnable-task count (a tile's layers form a chain: at most `ntiles` tasks are ever runnable;
     // see diffnet.hip).  NU = 2: two blocks fit a CU, and the ones that do not get a partner still run a task at a time.
-    int grid = NU * n_cu;
-    if (grid > ntiles * 4 / 5) grid = ntiles * 4 / 5;
-    if (const char *e = getenv("SET_AMD_STACK_GRID")) grid = atoi(e) > 0 ? atoi(e) : grid;
-    if ((int64_t)grid > ntasks64) grid = (int)ntasks64;
-    if (grid < 1) grid = 1;
+    const int grid = stack_grid(NU * n_cu, ntiles, ntasks64, true, 0);
     hipLaunchKernelGGL((diffnet_stack_x3_kernel<S, NU, NCB>), dim3(grid), dim3(512 / NU), ldsz, s, a, tiles_per_utt, ntiles, (int)ntasks64,
-                       piece_bytes, fault_tile);
+                       piece_bytes, stack_fault_tile());
     return set_check_launch("set_diffnet_stack");
 }
 
@@ -1143,7 +1112,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
     typedef SplitF16x2 S;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     int *s_task = reinterpret_cast<int *>(lds + xv_tile<NB>() + NB * XC * sizeof(float));  // [0] next task, [1] peek result, [2] wait result
-    int *counter = a.sync_ws, *abort_flag = a.sync_ws + 1, *done = a.sync_ws + 4;
+    int *counter = a.sync_ws + SQ_COUNTER, *abort_flag = a.sync_ws + SQ_ABORT, *done = a.sync_ws + SQ_FLAGS;
     const int tid = threadIdx.x;
     uint64_t *dbg = (SET_X3_PROBE == 1 && blockIdx.x == 0 && tid == 0) ? g_x3_phase_buf : nullptr;
     uint64_t tprev = dbg ? __builtin_amdgcn_s_memtime() : 0;
@@ -1152,22 +1121,13 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
     int n = __builtin_amdgcn_readfirstlane(s_task[0]);
     int i_done = -1, l_done = 0;
     uint64_t ts[32] = {};
+#if SET_X3_PROBE == 2
     int n_mine = 0;
-    (void)n_mine;
+#endif
     while (n < ntasks) {
         const int l = n / ntiles, i = n - l * ntiles;
         X3Tile lt;
-        lt.xin = (l & 1) ? a.xb : a.xa;
-        lt.xout = (l & 1) ? a.xa : a.xb;
-        lt.skp = a.skip;
-        lt.cp = a.condproj + (int64_t)l * a.cp_ls; lt.cp_bs = a.cp_bs;
-        lt.dstep = a.dstep + (int64_t)l * a.d_ls; lt.d_bs = a.d_bs; lt.d_cs = a.d_cs;
-        lt.img = reinterpret_cast<const unsigned short *>(a.wx3_all) + (int64_t)l * x_nimg<S>();
-        lt.b_dil = a.b_dil_all + (int64_t)l * 512;
-        lt.b_out = a.b_out_all + (int64_t)l * 512;
-        lt.err_flag = a.err_flag;
-        lt.T = a.T; lt.dil = 1; lt.first = (l == 0);
-        lt.nbu = (a.T + 31) / 32; lt.Q = a.B * lt.nbu; lt.q0 = i * NB;  // (x3v)
+        stack_fill_x3_tile(lt, a, l, i, NB, 1, x_nimg<S>());
         f32x4 PQ[2][4][NB];
         X3V_KTS(0)
         // the finished tile is published by every wave on its own, as soon as ITS stores are complete (agent-scope write-through stores: complete =
@@ -1176,8 +1136,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
         // profiles/r06_x3v_wave_publish_ab.log.)
         if (i_done >= 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if ((tid & 63) == 0 && !(l_done == 0 && i_done == fault_tile))
-                (void)__hip_atomic_fetch_add(done + i_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if ((tid & 63) == 0) stack_publish_add(done, i_done, l_done, fault_tile);
             i_done = -1;
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1217,23 +1176,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
         __syncthreads();
         X3V_KTS(3)
         if (__builtin_amdgcn_readfirstlane(s_task[1]) == 2) {
-            if (tid == 0) {
-                int ok = 1;
-                unsigned spins = 0;
-                for (;;) {
-                    const int v0 = ld_agent(f0), v1 = ld_agent(fl), v2 = ld_agent(fr);
-                    if (min(v0, min(v1, v2)) >= l * X3V_FLAG_UNIT) break;
-                    __builtin_amdgcn_s_sleep(8);
-                    if (++spins > STACK_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
-                        __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (a.err_flag) __hip_atomic_store(a.err_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ok = 0;
-                        break;
-                    }
-                }
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                s_task[2] = ok;
-            }
+            if (tid == 0) s_task[2] = stack_wait_tiles(f0, fl, fr, l * X3V_FLAG_UNIT, abort_flag, a.err_flag);
             __syncthreads();
             if (__builtin_amdgcn_readfirstlane(s_task[2]) == 0) break;
         }
@@ -1266,12 +1209,11 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if ((tid & 63) == 0 && i_done >= 0 && !(l_done == 0 && i_done == fault_tile))
-        (void)__hip_atomic_fetch_add(done + i_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((tid & 63) == 0 && i_done >= 0) stack_publish_add(done, i_done, l_done, fault_tile);
 }
 
 template <int NB>
-int launch_x3v(const SetDiffnetStackArgs &a, int n_cu, int fault_tile, hipStream_t s) {
+int launch_x3v(const SetDiffnetStackArgs &a, int n_cu, hipStream_t s) {
     static SetDeviceOnce lds_once;
     if (int rc = set_lds_optin(lds_once, 160 * 1024, "set_diffnet_stack(x3v attr)", diffnet_stack_x3v_kernel<NB>)) return rc;
     const int Q = a.B * ((a.T + 31) / 32);
@@ -1281,13 +1223,10 @@ int launch_x3v(const SetDiffnetStackArgs &a, int n_cu, int fault_tile, hipStream
     SET_REQUIRE((int64_t)2 * XC * a.T * 4 < ((int64_t)1 << 31), "set_diffnet_stack(split-operand kernel: T too large)");
     SET_REQUIRE(a.dilation_cycle_length == 1 && a.T % 2 == 0, "set_diffnet_stack(x3v: dilation 1 and even T only)");
     const size_t ldsz = (size_t)xv_tile<NB>() + NB * XC * sizeof(float) + 16;
-    SET_HIP(set_zero_async(a.sync_ws, (size_t)(4 + ntiles) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
-    int grid = n_cu;
-    if (NB == 2 && grid > ntiles * 4 / 5) grid = ntiles * 4 / 5;  // (the 64-frame rule of the earlier forms: workers beyond 0.8 tile chains mostly wait)
-    if (const char *e = getenv("SET_AMD_STACK_GRID")) grid = atoi(e) > 0 ? atoi(e) : grid;
-    if ((int64_t)grid > ntasks64) grid = (int)ntasks64;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(diffnet_stack_x3v_kernel<NB>, dim3(grid), dim3(512), ldsz, s, a, ntiles, (int)ntasks64, fault_tile);
+    SET_HIP(set_zero_async(a.sync_ws, stack_sync_words(SQ_QUEUE, ntiles) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
+    // the cap for 64-frame tiles only (the rule of the earlier forms: workers beyond 0.8 tile chains mostly wait)
+    const int grid = stack_grid(n_cu, ntiles, ntasks64, NB == 2, 0);
+    hipLaunchKernelGGL(diffnet_stack_x3v_kernel<NB>, dim3(grid), dim3(512), ldsz, s, a, ntiles, (int)ntasks64, stack_fault_tile());
     return set_check_launch("set_diffnet_stack");
 }
 
@@ -1315,30 +1254,14 @@ constexpr int SX_PF = 8;  // A prefetch distance in k-steps (2 x 16 bytes each).
                           // 16 k-steps: GEMM 1 8.8 / GEMM 2 1.1 us but the x staging doubles (AGPR traffic), 80.6 ms.  An
                           // LDS-fragment ring and an explicit L2 prefetch of the next layer's slices were not faster either.
 
-// agent-scope (sc1) loads: coherent with the sc1 write-through stores of other XCDs without an acquire fence in front of them
+// agent-scope (sc1) loads: coherent with the sc1 write-through stores of other XCDs without an acquire fence in front of them.  With
+// `nofence` the row-split kernel reads everything other blocks produced with them and its waits do not fence: no `buffer_inv sc1`,
+// which would also throw this XCD's copy of the weight images out of the L2 -- twice per layer
 __device__ __forceinline__ float buf_load_sc1(rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 16));
 }
 __device__ __forceinline__ u32x4_t buf_load_u4_sc1(rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 16);
-}
-
-// fence = false: the caller reads everything other blocks produced with agent-scope loads (buf_load_sc1): no `buffer_inv sc1`,
-// which would also throw this XCD's copy of the weight images out of the L2 -- twice per layer
-__device__ __forceinline__ bool sx_wait(const int *f0, const int *f1, const int *f2, int want, int *abort_flag, int *err_flag, bool fence = true) {
-    unsigned spins = 0;
-    for (;;) {
-        const int v0 = ld_agent(f0), v1 = ld_agent(f1), v2 = ld_agent(f2);
-        if (min(v0, min(v1, v2)) >= want) break;
-        __builtin_amdgcn_s_sleep(1);
-        if (++spins > SPLIT_SPIN_LIMIT || ld_agent(abort_flag) != 0) {
-            __hip_atomic_store(abort_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (err_flag) __hip_atomic_store(err_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return false;
-        }
-    }
-    if (fence) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    return true;
 }
 
 // acc += A B over NKS k-steps, ONE accumulator: A fragments of (k-step, piece) at abase + (ks * 4 + piece) * 1024 (the image's
@@ -1390,7 +1313,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
     float *gs = reinterpret_cast<float *>(lds + 2 * piece_bytes);       // [64][32] tanh(filter rows) of this part
     float *dsh = gs + 64 * 32;                                          // [256] step offsets
     int *s_ok = reinterpret_cast<int *>(dsh + XC);
-    int *abort_flag = a.sync_ws + 1, *ready = a.sync_ws + 4, *zcnt = a.sync_ws + 4 + ntiles;
+    int *abort_flag = a.sync_ws + SQ_ABORT, *ready = a.sync_ws + SQ_FLAGS, *zcnt = a.sync_ws + sq_flags2(ntiles);
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, l31 = lane & 31;
     const int j = __builtin_amdgcn_readfirstlane(tid >> 6);
     if ((int)blockIdx.x >= 4 * ntiles) {
@@ -1401,11 +1324,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         // paced by tile 0's progress counter and touches nothing the compute blocks write.
         const int hp = blockIdx.x & 3;
         for (int l = 1; l < a.L; ++l) {
-            unsigned spins = 0;
-            while (l >= 2 && ld_agent(ready) < 4 * (l - 1)) {  // tile 0 has finished layer l - 2: it is on layer l - 1 now
-                __builtin_amdgcn_s_sleep(8);
-                if (++spins > SPLIT_SPIN_LIMIT || ld_agent(abort_flag) != 0) return;
-            }
+            if (l >= 2 && !stack_wait_pace(ready, 4 * (l - 1), abort_flag)) return;  // tile 0 has finished layer l - 2: it is on layer l - 1 now
             const unsigned char *img = reinterpret_cast<const unsigned char *>(a.wx3_all) + (int64_t)l * x_nimg<S>() * 2;
             const rsrc_t r1 = make_rsrc(img + (size_t)(2 * hp) * X_KS1 * 4 * 1024);
             const rsrc_t r2 = make_rsrc(img + x_n1<S>() * 2 + (size_t)(2 * hp) * X_KS2 * 4 * 1024);
@@ -1469,7 +1388,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
             const float blo = bd[urow(r)], bhi = bd[urow(r) + 4];
             acc[r] = (half ? bhi : blo) + buf_load(rcp, vo4, (unsigned)(rb * XC + ch0 + urow(r)) * T4);
         }
-        if (tid == 0) *s_ok = (l == 0 || sx_wait(ready + i, ready + il, ready + ir, 4 * l, abort_flag, a.err_flag, !nofence)) ? 1 : 0;
+        if (tid == 0) *s_ok = l == 0 ? 1 : stack_wait_parts(ready + i, ready + il, ready + ir, 4 * l, abort_flag, a.err_flag, !nofence);
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(*s_ok) == 0) return;
         SX_PHASE(0)
@@ -1558,7 +1477,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the z rows of this wave are visible to every XCD
         __syncthreads();
-        if (tid == 0) __hip_atomic_fetch_add(zcnt + i, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) stack_publish_add(zcnt, i, l, fault_tile, false);
         SX_PHASE(3)
         // ---- GEMM 2: A ring + accumulator start (residual rows: b_out + x; skip rows: b_out, the running sum joins in the
         //      epilogue) -- rows this very wave wrote one layer ago; the loads fly while lane 0 waits for the other parts' z
@@ -1576,7 +1495,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
             const float bias = half ? bhi : blo;
             acc[r] = (rb == 0 ? bias + prev[r] : bias) * s2;
         }
-        if (tid == 0) *s_ok = sx_wait(zcnt + i, zcnt + i, zcnt + i, 4 * (l + 1), abort_flag, a.err_flag, !nofence) ? 1 : 0;
+        if (tid == 0) *s_ok = stack_wait_parts(zcnt + i, zcnt + i, zcnt + i, 4 * (l + 1), abort_flag, a.err_flag, !nofence);
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(*s_ok) == 0) return;
         SX_PHASE(4)
@@ -1612,8 +1531,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // every store of the block has completed; the LDS tile is free for the next layer
-        if (tid == 0 && !(l == 0 && i == fault_tile && h == 0))
-            __hip_atomic_fetch_add(ready + i, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) stack_publish_add(ready, i, l, fault_tile, h == 0);
         SX_PHASE(7)
     }
 #undef SX_PHASE
@@ -1622,22 +1540,24 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
 }  // namespace
 
 // called by set_diffnet_stack (csrc/diffnet.hip) for the row-split variant when two-piece fp16 images are given
-int set_launch_diffnet_stack_split_x2(const SetDiffnetStackArgs &a, int fault_tile, hipStream_t s) {
+int set_launch_diffnet_stack_split_x2(const SetDiffnetStackArgs &a, hipStream_t s) {
     static SetDeviceOnce lds_once;
     if (int rc = set_lds_optin(lds_once, 80 * 1024, "set_diffnet_stack(split x2 attr)", diffnet_stack_split_x2_kernel)) return rc;
     const int tiles = (a.T + 31) / 32, nt = a.B * tiles;
     const int max_dil = 1 << (a.dilation_cycle_length - 1);
     const unsigned piece_bytes = (unsigned)((32 + 2 * max_dil) * XR);
     const size_t ldsz = (size_t)2 * piece_bytes + (64 * 32 + XC) * sizeof(float) + 16;
-    SET_HIP(set_zero_async(a.sync_ws, (size_t)(4 + 2 * nt) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
+    SET_HIP(set_zero_async(a.sync_ws, stack_sync_words(SQ_ROW_SPLIT, nt) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
     // 8 L2-warmer blocks (one per XCD) when the chip has CUs to spare and the block -> XCD round-robin lines them up with the parts
     int n_cu = 0;
     (void)set_cu_count(&n_cu);  // (stays 0 when the query fails: no warmers)
     const int extra = (4 * nt + 8 <= n_cu && a.L > 1) ? 8 : 0;  // (block q: XCD q % 8, part q & 3 = (q % 8) & 3 -- consistent)
     // agent-scope loads for the tiles other blocks produced instead of an acquire fence after each wait (measured in round 3 against
-    // the fences: 62.7 -> 61.4 ms per 100 steps at B = 1, 66.9 -> 62.3 at B = 2 (T = 800), bit-identical either way)
+    // the fences: 62.7 -> 61.4 ms per 100 steps at B = 1, 66.9 -> 62.3 at B = 2 (T = 800), bit-identical either way).  A run-time
+    // argument on purpose: folded into the kernel as a constant it changes the register allocation and measured ~7 % slower at B = 1
     const int nofence = 1;
-    hipLaunchKernelGGL(diffnet_stack_split_x2_kernel, dim3(4 * nt + extra), dim3(256), ldsz, s, a, tiles, nt, piece_bytes, fault_tile, nofence);
+    hipLaunchKernelGGL(diffnet_stack_split_x2_kernel, dim3(4 * nt + extra), dim3(256), ldsz, s, a, tiles, nt, piece_bytes, stack_fault_tile(),
+                       nofence);
     return set_check_launch("set_diffnet_stack");
 }
 
@@ -1685,7 +1605,7 @@ int set_x3_winograd_selected(int x3_mode, int B, int T, int dilation_cycle_lengt
 }
 
 // called by set_diffnet_stack (csrc/diffnet.hip) once it has picked this kernel
-int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, int n_cu, int fault_tile, hipStream_t s) {
+int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, int n_cu, hipStream_t s) {
     SET_REQUIRE(a.x3_mode == 2 || a.x3_mode == 3, "set_diffnet_stack(x3_mode must be 2 = f16x2 or 3 = bf16x3)");
     // tile width: 64 frames from ~0.6 tiles per CU on; below that 32-frame tiles (twice the tasks, each about half as long:
     // the time of a layer is the time of one task while the chip is not full).  SET_AMD_X3_TILE=32|64 overrides.
@@ -1702,9 +1622,9 @@ int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, int n_cu, int faul
     const bool al8 = ((reinterpret_cast<uintptr_t>(a.condproj) | reinterpret_cast<uintptr_t>(a.xa) | reinterpret_cast<uintptr_t>(a.xb)) & 7) == 0 &&
                      ((a.cp_bs | a.cp_ls) & 1) == 0;
     const int wino = al8 ? set_x3_winograd_selected(a.x3_mode, a.B, a.T, a.dilation_cycle_length, n_cu) : 0;
-    if (wino == 3) return launch_x3v<3>(a, n_cu, fault_tile, s);
-    if (wino == 2) return launch_x3v<2>(a, n_cu, fault_tile, s);
+    if (wino == 3) return launch_x3v<3>(a, n_cu, s);
+    if (wino == 2) return launch_x3v<2>(a, n_cu, s);
     if (a.x3_mode == 2)
-        return narrow ? launch_x3<SplitF16x2, 1, 1>(a, n_cu, fault_tile, s) : launch_x3<SplitF16x2, 1, 2>(a, n_cu, fault_tile, s);
-    return narrow ? launch_x3<SplitBf16x3, 1, 1>(a, n_cu, fault_tile, s) : launch_x3<SplitBf16x3, 1, 2>(a, n_cu, fault_tile, s);
+        return narrow ? launch_x3<SplitF16x2, 1, 1>(a, n_cu, s) : launch_x3<SplitF16x2, 1, 2>(a, n_cu, s);
+    return narrow ? launch_x3<SplitBf16x3, 1, 1>(a, n_cu, s) : launch_x3<SplitBf16x3, 1, 2>(a, n_cu, s);
 }

@@ -776,6 +776,7 @@ def pack_diffnet_layer_wino(w_dil, w_out, w1w, w2w):
 
 
 def sync_ws_size(B, T):
+    # the words of one stack (csrc/stack_queue.h: 16 + 2 B ceil(T / 32)) and the fixed words of set_diffusion_loop's utterance groups (8 at the most)
     return 160 + 2 * B * ((T + 31) // 32)
 
 

@@ -83,19 +83,26 @@ def test_launch_state_is_set_up_per_device_in_common_h():
 
 def test_dropped_experiment_switches_stay_out_of_csrc():
     """The compile-time switches of measured and dropped experiments (some of them wrong by design) are gone from the kernel sources: only
-    the shipped branch is left, the logs under profiles/ are the record.  The flag load and the spin limits of the stack kernels live in common.h."""
+    the shipped branch is left, the logs under profiles/ are the record.  The scheduling of the persistent stack kernels -- the flag load, the
+    bounded wait with its sleep and spin limits, the worker-count and fault-tile switches, the sync_ws word layout -- lives in stack_queue.h."""
     csrc = os.path.join(ROOT, "speech-editing-toolkit_amd", "csrc")
     removed = re.compile(r"\b(SET_X3_EXP|SET_T128_EXP|SET_WINO_FENCED|SET_NO_TRAILING_SB|SET_X3V_\w*|X3V_LEAD|SET_X3W_NT|"
-                         r"X_SPIN_LIMIT|SP_SPIN_LIMIT|SX_SPIN_LIMIT)\b")
-    defined = []
+                         r"X_SPIN_LIMIT|SP_SPIN_LIMIT|SX_SPIN_LIMIT|split_wait|sx_wait)\b")
+    only_in_header = ("__builtin_amdgcn_s_sleep", "_SPIN_LIMIT", 'getenv("SET_AMD_STACK_GRID")', 'getenv("SET_AMD_FAULT_TILE")')
+    defined, found = [], {pat: [] for pat in only_in_header}
     for fn in sorted(os.listdir(csrc)):
         if not fn.endswith((".hip", ".h")):
             continue
         src = open(os.path.join(csrc, fn)).read()
         assert not removed.search(src), (fn, removed.findall(src))
+        assert not re.search(r"sync_ws\s*\+\s*\d", src), (fn, re.findall(r"sync_ws\s*\+\s*\d.*", src))  # words by name only
         if re.search(r"\bint\s+ld_agent\s*\(", src):
             defined.append(fn)
-    assert defined == ["common.h"], defined
+        for pat in only_in_header:
+            if pat in src:
+                found[pat].append(fn)
+    assert defined == ["stack_queue.h"], defined
+    assert all(fns == ["stack_queue.h"] for fns in found.values()), found
 
 
 INSTRUMENT_BUILDS = (("diffnet_x3.hip", "-DSET_X3_PROBE=1"), ("diffnet_x3.hip", "-DSET_X3_PROBE=2"), ("diffnet.hip", "-DSET_WINO_PHASES"),

@@ -9,9 +9,11 @@ CS=speech-editing-toolkit_amd/csrc
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -I include"
 mkdir -p build/exp/obj
 for f in conv1d conv_x2 resblock_x2 glue diffnet diffnet_x3 train attention attention_fused bf16 diffnet_bf16 stutter; do
-  if [ ! -f build/exp/obj/$f.o ] || [ $CS/$f.hip -nt build/exp/obj/$f.o ] || [ $CS/common.h -nt build/exp/obj/$f.o ]; then
-    /opt/rocm/bin/hipcc $FLAGS -c $CS/$f.hip -o build/exp/obj/$f.o &
-  fi
+  stale=0
+  for d in $CS/$f.hip $CS/*.h; do
+    if [ ! -f build/exp/obj/$f.o ] || [ $d -nt build/exp/obj/$f.o ]; then stale=1; fi
+  done
+  if [ $stale = 1 ]; then /opt/rocm/bin/hipcc $FLAGS -c $CS/$f.hip -o build/exp/obj/$f.o & fi
 done
 wait
 # SRC_OVERRIDE=<path>: compile that file in place of $CS/$SRC (an older or patched version of the same module)
