@@ -1,6 +1,6 @@
-// Shared by csrc/diffnet.hip (diffnet_boundary_x2_kernel: the step boundary as a launch of its own) and csrc/diffnet_x3.hip (the whole-loop
-// kernel, where the step boundary is a task of the persistent queue): Philox4x32-10 + Box-Muller, and the two-piece fp16 GEMM of the step
-// boundary (skip projection, output head, next step's input projection; diffnet.py:118-120,128-131, spec_denoiser.py:86-101).
+// Shared by csrc/boundary.hip (the step-boundary kernels of the reverse loop) and csrc/diffusion_ops.hip (set_randn, set_posterior_step):
+// Philox4x32-10 + Box-Muller, and the two-piece fp16 GEMM of the step boundary (skip projection, output head, next step's input projection;
+// diffnet.py:118-120,128-131, spec_denoiser.py:86-101).
 #pragma once
 #include "common.h"
 

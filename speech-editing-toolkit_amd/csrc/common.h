@@ -77,7 +77,7 @@ static inline hipError_t set_cu_count(int *n_cu) {
     return hipSuccess;
 }
 
-const uint64_t *set_seed_delta_ptr();  // the device word of set_rng_seed_delta (csrc/diffnet.hip), NULL when unset
+const uint64_t *set_seed_delta_ptr();  // the device word of set_rng_seed_delta (csrc/diffusion_ops.hip), NULL when unset
 // Clear `words` 32-bit words with a KERNEL.  Not hipMemsetAsync: as a memset node of a captured graph (training.GraphedTrainStep) a clear
 // was not ordered against eager work enqueued between two replays (ROCm 7.2) -- buffers came out as uninitialised memory.
 static __global__ void __launch_bounds__(256) set_zero_words_kernel(unsigned *p, int64_t words) {
@@ -122,6 +122,10 @@ __device__ __forceinline__ float dev_pro(float v, int pro, float p) {
 //   B operand: lane l holds B[k = l >> 5][j = l & 31]
 //   C/D      : reg r of lane l is D[row = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5)][col = l & 31]
 __device__ __forceinline__ int mfma32_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+// Accumulator register r of the 32x32 block holds row  urow16(r) + 4*(lane>>5):  the first term is wave-uniform, so a
+// global access can be  (uniform row pointer, SGPR) + (one per-lane 32-bit offset, VGPR)  -- no per-row 64-bit address
+// registers (those spilled and serialised the epilogue stores behind vmcnt(0) reloads).
+__device__ __forceinline__ int urow16(int r) { return (r & 3) + 8 * (r >> 2); }
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }

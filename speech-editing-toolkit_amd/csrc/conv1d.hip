@@ -790,3 +790,5 @@ extern "C" int set_weight_norm_fold(const float *g, const float *v, float *w, in
     hipLaunchKernelGGL(weight_norm_fold_kernel, dim3(n0), dim3(256), 0, (hipStream_t)stream, g, v, w, inner);
     return set_check_launch("set_weight_norm_fold");
 }
+
+extern "C" int64_t set_sizeof_conv1d_args(void) { return (int64_t)sizeof(SetConv1dArgs); }

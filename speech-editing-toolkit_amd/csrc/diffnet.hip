@@ -1,12 +1,15 @@
-// DiffNet (FluentSpeech denoiser) kernels and the reverse-diffusion loop for gfx950.
+// DiffNet (FluentSpeech denoiser) layer kernels on the fp32 MFMA pipe for gfx950: one residual layer per launch (diffnet_layer_kernel),
+// the persistent layer-stack kernels (diffnet_stack_kernel: direct; diffnet_stack_wino_kernel: Winograd F(2,3); diffnet_stack_split_kernel:
+// row split for small batches), the kernels that pack their weight images, and the launcher of the stack kernels
+// (set_launch_diffnet_stack_f32: which one runs is decided by plan_stack, csrc/diffusion_loop.hip).
 //
-// Hot kernel: diffnet_layer_kernel -- ONE launch per residual layer (diffnet.py:60-81), fusing
+// A layer (diffnet.py:60-81) fuses
 //   x+d  ->  k=3 dilated conv (implicit GEMM, 512x768)  -> +bias +hoisted conditioner projection
 //        ->  sigmoid*tanh gate  ->  1x1 conv (GEMM 512x256)  ->  residual/sqrt(2) + skip accumulate.
 // fp32 end to end on v_mfma_f32_32x32x2_f32 (exact fp32 FMA chain): the parity bar is |dmel| < 1e-4
 // against the fp32 reference, which a bf16 path cannot meet.
 //
-// Work decomposition (64-wide waves, 256 CUs):
+// Work decomposition of diffnet_layer_kernel (64-wide waves, 256 CUs):
 //   grid  = (ceil(T/64), B); block = 256 threads = 4 waves; block tile = all 512 rows x 64 frames.
 //   wave w owns gate rows [64w,64w+64) and the matching filter rows [256+64w, 256+64w+64) so the
 //   gate is lane-local in the accumulator layout; same split for residual/skip rows of GEMM 2.
@@ -19,7 +22,7 @@
 #include <stdlib.h>
 
 #include "common.h"
-#include "boundary_x2.h"
+#include "diffnet_host.h"
 #include "stack_queue.h"
 
 namespace {
@@ -28,11 +31,6 @@ constexpr int DC = 256;       // residual_channels this kernel is specialised fo
 constexpr int NT = 64;        // frames per block tile
 constexpr int KS1 = 3 * DC / 2;  // 384 k-steps (K=768) of GEMM 1
 constexpr int KS2 = DC / 2;      // 128 k-steps (K=256) of GEMM 2
-
-// Accumulator register r of the 32x32 block holds row  urow(r) + 4*(lane>>5):  the first term is wave-uniform, so
-// every global access below is  (uniform row pointer, SGPR) + (one per-lane 32-bit offset, VGPR)  -- no per-row
-// 64-bit address registers (those spilled and serialised the epilogue stores behind vmcnt(0) reloads).
-__device__ __forceinline__ int urow16(int r) { return (r & 3) + 8 * (r >> 2); }
 
 __device__ __forceinline__ int layer_row(int w, int rb, int i) {
     // rb 0,1 -> first half rows (gate / residual); rb 2,3 -> second half (filter / skip)
@@ -271,7 +269,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_layer_kernel(SetDiffnetLayerAr
 // ds_read_b64 + 4 VALU per k-step); the filter transform is folded into the packed weights; bias + conditioner
 // projection are folded into the M1 / M4 accumulator init.  GEMM 2 and the epilogue are as in layer_tile<2>.
 constexpr int WN_NT = 64;
-constexpr int WN_MAXD = 8;             // largest dilation (dilation_cycle_length <= 4)
+constexpr int WN_MAXD = STACK_WINO_MAX_DIL;  // largest dilation (dilation_cycle_length <= 4)
 constexpr int WN_XW = WN_NT + 2 * WN_MAXD;  // 64 frames + a halo of d on each side (d = 1: + the 2-column boundary gap)
 constexpr int WN_KS = DC / 2;  // 128 k-steps (2 channels each) for every GEMM here
 constexpr int WN_GS = 2;       // k-steps per operand group of GEMM 1
@@ -1043,99 +1041,27 @@ extern "C" int set_debug_split_phase_buffer(uint64_t *buf) {
 }
 
 extern "C" int64_t set_sizeof_diffnet_stack_args(void) { return (int64_t)sizeof(SetDiffnetStackArgs); }
+extern "C" int64_t set_sizeof_diffnet_layer_args(void) { return (int64_t)sizeof(SetDiffnetLayerArgs); }
 
-// read at every call (tests set the environment between launches): SET_AMD_SPLIT_F32 != 0 pins the row-split kernel to the fp32 pipe
-static bool split_f32_pinned() {
-    const char *e = getenv("SET_AMD_SPLIT_F32");
-    return e && atoi(e) != 0;
-}
-static int x3_mode_of_images(int images) { return (images & 4) ? 3 : ((images & 8) ? 2 : 0); }  // split-operand mode of an `images` mask (set_amd.h)
-
-// 0 = direct kernel, 64-frame tiles; 1 = direct kernel, 32-frame tiles; 2 = Winograd F(2,3) kernel (64-frame tiles,
-// 8-wave blocks, needs its packed images, dilation_cycle_length <= 4 and at least ~0.68 tiles per CU to be worth it);
-// 3 = row-split kernel for small batches (4 blocks per 32-frame tile, needs its images and the z workspace);
-// 4 / 5 = split-operand kernel (fp32 = 3 bf16 pieces, six bf16 MFMAs per product / 2 fp16 pieces, three; csrc/diffnet_x3.hip)
-static int stack_variant(int B, int T, int dcl, bool have_wino, bool have_split, int x3_mode, int n_cu) {
-    const bool have_x3 = x3_mode == 2 || x3_mode == 3;
-    const int64_t tiles64 = (int64_t)B * ((T + 63) / 64);
-    // row-split kernel: 4 blocks per 32-frame tile, all co-resident (2 per CU); SET_AMD_SPLIT=0 disables, =2 forces it
-    // (when it fits); an explicit SET_AMD_WINO choice also rules it out
-    // (measured at T = 800: one utterance 75 ms per 100 steps, two 79 ms; from three utterances on two blocks would share a CU
-    // and the split-operand kernel, ~123 ms whatever the batch up to B = 16, is the faster one)
-    const int64_t split_blocks = 4 * (int64_t)B * ((T + 31) / 32);
-    // co-residency: two blocks per CU for the fp32-pipe kernel, ONE for the two-piece fp16 one (its A ring takes the whole register
-    // file of a SIMD lane group: launch bounds (256, 1)) unless SET_AMD_SPLIT_F32 pins the fp32-pipe kernel
-    const bool split_one_per_cu = have_x3 && !split_f32_pinned();
-    const bool split_fits = have_split && dcl <= 4 && split_blocks <= (split_one_per_cu ? 1 : 2) * (int64_t)n_cu;
-    const bool split_pays = split_blocks <= (int64_t)(have_x3 ? 1 : 2) * n_cu;
-    int split_env = 1;
-    if (const char *e = getenv("SET_AMD_SPLIT")) split_env = atoi(e);
-    if (split_fits && (split_env == 2 || (split_env == 1 && !getenv("SET_AMD_WINO") && split_pays))) return 3;
-    // split-operand kernel: every batch the row-split kernel does not take (a task is 61 us against 77 us for a 32-frame
-    // task of the direct fp32 kernel, so it wins even when the chip is far from full; tiny inputs stay on the fp32 kernels);
-    // SET_AMD_X3=0 disables, =2 forces it at any size; an explicit SET_AMD_WINO choice also rules it out
-    int x3_env = 1;
-    if (const char *e = getenv("SET_AMD_X3")) x3_env = atoi(e);
-    if (have_x3 && dcl <= 4 && (x3_env == 2 || (x3_env == 1 && !getenv("SET_AMD_WINO") && tiles64 >= 8)))
-        return x3_mode == 3 ? 4 : 5;
-    int ncb = tiles64 < 3 * n_cu ? 1 : 2;
-    if (const char *e = getenv("SET_AMD_STACK_NCB")) ncb = atoi(e) == 2 ? 2 : 1;
-    const bool wino_ok = have_wino && (1 << (dcl - 1)) <= WN_MAXD;
-    bool wino = wino_ok && 25 * tiles64 >= 17 * n_cu;  // measured crossover vs the direct 32-frame kernel: ~0.68 tiles per CU
-    if (const char *e = getenv("SET_AMD_WINO")) wino = wino_ok && (atoi(e) == 2 || (wino && atoi(e) != 0));  // 2 = force
-    return wino ? 2 : (ncb == 1 ? 1 : 0);
-}
-extern "C" int set_diffnet_stack_variant(int B, int T, int dilation_cycle_length, int images) {
-    int n_cu = 256;
-    (void)set_cu_count(&n_cu);  // (stays 256 when the query fails)
-    return stack_variant(B, T, dilation_cycle_length, (images & 1) != 0, (images & 2) != 0, x3_mode_of_images(images), n_cu);
-}
-
-int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, int n_cu, hipStream_t s);                 // csrc/diffnet_x3.hip
-int set_x3_winograd_selected(int x3_mode, int B, int T, int dilation_cycle_length, int n_cu);                // csrc/diffnet_x3.hip (0 / 1 / 2)
-extern "C" int set_diffnet_stack_x3_winograd(int B, int T, int dilation_cycle_length, int images) {
-    int n_cu = 256;
-    (void)set_cu_count(&n_cu);  // (stays 256 when the query fails)
-    const int x3_mode = x3_mode_of_images(images);
-    if (stack_variant(B, T, dilation_cycle_length, (images & 1) != 0, (images & 2) != 0, x3_mode, n_cu) != 5) return 0;
-    return set_x3_winograd_selected(x3_mode, B, T, dilation_cycle_length, n_cu);
-}
-int set_launch_diffnet_stack_split_x2(const SetDiffnetStackArgs &a, hipStream_t s);                       // csrc/diffnet_x3.hip
-
-extern "C" int set_diffnet_stack(const SetDiffnetStackArgs *args, void *stream) {
-    SET_REQUIRE(args != nullptr, "set_diffnet_stack");
-    const SetDiffnetStackArgs &a = *args;
-    SET_REQUIRE(a.xa && a.xb && a.skip && a.condproj && a.dstep && a.w1p_all && a.w2p_all && a.b_dil_all &&
-                    a.b_out_all && a.sync_ws,
-                "set_diffnet_stack");
-    SET_REQUIRE(a.B > 0 && a.T > 0 && a.L > 0 && a.dilation_cycle_length >= 1 && a.dilation_cycle_length <= 4,
-                "set_diffnet_stack");
-    hipStream_t s = (hipStream_t)stream;
+// the fp32-pipe stack kernels (families 0 - 3 of the plan; the row-split one here is the fp32 launch, p.split_x2 goes to csrc/diffnet_x3.hip)
+int set_launch_diffnet_stack_f32(const SetDiffnetStackArgs &a, const StackPlan &p, hipStream_t s) {
     static SetDeviceOnce lds_once;
     if (int rc = set_lds_optin(lds_once, 150 * 1024, "set_diffnet_stack(attr)", diffnet_stack_kernel<1, 8, 2>, diffnet_stack_kernel<2, 4, 2>,
                                diffnet_stack_wino_kernel<true>, diffnet_stack_wino_kernel<false>, diffnet_stack_split_kernel))
         return rc;
-    int n_cu = 0;
-    SET_HIP(set_cu_count(&n_cu), "set_diffnet_stack");
-    // Tile width: a task (l, i) needs tiles i-1..i+1 of layer l-1, so at most `tiles per layer` tasks are ever
-    // runnable.  Workers (2 per CU) must stay BELOW that or the youngest ones only wait (measured: 36 % wait time
-    // with 512 workers on 416 64-frame tiles).  Use 64-frame tiles when a layer has >= 1.5x the workers, else
-    // 32-frame tiles (B=32, T=800: 800 tiles, no tail waste); the grid is capped at 0.8x the tile count.
-    const bool plain = !a.x_all && !a.save_y && !a.save_z;
-    const int variant = stack_variant(a.B, a.T, a.dilation_cycle_length, a.w1w_all && a.w2w_all,
-                                      a.w1s_all && a.w2s_all && a.z_ws && plain, (a.wx3_all && plain) ? a.x3_mode : 0, n_cu);
-    if (variant >= 4) return set_launch_diffnet_stack_x3(a, n_cu, s);
-    if (variant == 3 && a.wx3_all && a.x3_mode == 2 && !split_f32_pinned())
-        return set_launch_diffnet_stack_split_x2(a, s);  // the same scheme on the two-piece fp16 operands
-    if (variant == 3) {
+    if (p.family == STACK_ROW_SPLIT) {
         const int tiles = (a.T + 31) / 32, nt = a.B * tiles;
         SET_HIP(set_zero_async(a.sync_ws, stack_sync_words(SQ_ROW_SPLIT, nt) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
         hipLaunchKernelGGL(diffnet_stack_split_kernel, dim3(4 * nt), dim3(256), (size_t)SP_LDS_FLOATS * sizeof(float), s, a,
                            tiles, nt, stack_fault_tile());
         return set_check_launch("set_diffnet_stack");
     }
-    const bool wino = variant == 2;
-    const int ncb = variant == 1 ? 1 : 2;
+    // Tile width: a task (l, i) needs tiles i-1..i+1 of layer l-1, so at most `tiles per layer` tasks are ever
+    // runnable.  Workers (2 per CU) must stay BELOW that or the youngest ones only wait (measured: 36 % wait time
+    // with 512 workers on 416 64-frame tiles).  Use 64-frame tiles when a layer has >= 1.5x the workers, else
+    // 32-frame tiles (B=32, T=800: 800 tiles, no tail waste); the grid is capped at 0.8x the tile count.
+    const bool wino = p.family == STACK_WINO;
+    const int ncb = p.family == STACK_DIRECT32 ? 1 : 2;
     const int ntt = 32 * ncb;
     int tiles_per_utt = (a.T + ntt - 1) / ntt;
     int ntiles = a.B * tiles_per_utt;
@@ -1156,7 +1082,7 @@ extern "C" int set_diffnet_stack(const SetDiffnetStackArgs *args, void *stream) 
             "set_diffnet_stack(memset)");
     const int wps = wino ? 1 : 2;  // resident blocks per CU (three 168-VGPR blocks per CU measured slower: see DESIGN.md)
     // capped at 0.8x the tile count (see above), but a block on every CU while there are tiles for them
-    const int grid = stack_grid(wps * n_cu, ntiles, ntasks64, true, n_cu);
+    const int grid = stack_grid(wps * p.n_cu, ntiles, ntasks64, true, p.n_cu);
     const int fault_tile = stack_fault_tile();
     if (wino) {
         if (a.dilation_cycle_length == 1)
@@ -1175,807 +1101,3 @@ extern "C" int set_diffnet_stack(const SetDiffnetStackArgs *args, void *stream) 
                            (int)ntasks64, task_slot);
     return set_check_launch("set_diffnet_stack");
 }
-
-// ----------------------------------------------------------------------------------------------------------
-// unfused pieces (any residual_channels; also the device-side cross-check of the fused kernel)
-// ----------------------------------------------------------------------------------------------------------
-namespace {
-__global__ void __launch_bounds__(256) gate_kernel(const float *y, float *z, int B, int C, int T) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * C * T) return;
-    const int64_t ct = i % ((int64_t)C * T);
-    const int64_t b = i / ((int64_t)C * T);
-    const float *yb = y + b * 2 * C * T;
-    z[i] = dev_sigmoid(yb[ct]) * tanhf(yb[(int64_t)C * T + ct]);
-}
-__global__ void __launch_bounds__(256) res_skip_kernel(const float *x_in, const float *o, float *x_out, float *skip,
-                                                       int B, int C, int T, int first) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * C * T) return;
-    const int64_t ct = i % ((int64_t)C * T);
-    const int64_t b = i / ((int64_t)C * T);
-    const float *ob = o + b * 2 * C * T;
-    x_out[i] = (x_in[i] + ob[ct]) / 1.41421356237309504880f;
-    const float s = ob[(int64_t)C * T + ct];
-    skip[i] = first ? s : skip[i] + s;
-}
-__global__ void __launch_bounds__(256) sinusoid_kernel(const float *t, float *out, int dim, int n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)dim * n) return;
-    const int j = (int)(i / n), k = (int)(i % n);
-    const int half = dim / 2;
-    const int jj = j < half ? j : j - half;
-    // emb = exp(arange(half) * -(ln(1e4)/(half-1)))   (diffnet.py:42-43, all fp32 tensor ops)
-    const float e = (float)(9.210340371976184 / (double)(half - 1));  // python float -> fp32 scalar
-    const float freq = expf((float)jj * -e);
-    const float ang = t[k] * freq;
-    out[i] = j < half ? sinf(ang) : cosf(ang);
-}
-
-// (Philox4x32-10 + Box-Muller: csrc/boundary_x2.h, shared with the whole-loop kernel of csrc/diffnet_x3.hip)
-
-// seed_delta (set_rng_seed_delta, may be NULL): a device word ADDED to the seed argument -- a captured graph carries the seed of the
-// step it was captured at; the replay of step k stores (seed_k - seed_captured) there and draws exactly the eager step's numbers
-__global__ void __launch_bounds__(256) randn_kernel(float *out, int64_t n, uint64_t seed, uint64_t offset, const uint64_t *seed_delta) {
-    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;  // quad index
-    if (q * 4 >= n) return;
-    if (seed_delta) seed += *seed_delta;
-    float z[4];
-    randn4(seed, offset + (uint64_t)q, z);
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (q * 4 + k < n) out[q * 4 + k] = z[k];
-}
-
-// x_prev = c1*x0 + c2*x_t + nonzero*exp(0.5*logvar)*eps      (spec_denoiser.py:86-101)
-__global__ void __launch_bounds__(256) posterior_kernel(const float *x0, const float *x_t, const float *eps,
-                                                        const float *coef4, int64_t coef_bs, float *x_prev,
-                                                        int64_t per_batch, int64_t n, uint64_t seed,
-                                                        uint64_t offset, const uint64_t *seed_delta) {
-    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (q * 4 >= n) return;
-    if (seed_delta) seed += *seed_delta;
-    float z[4];
-    if (!eps) randn4(seed, offset + (uint64_t)q, z);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t i = q * 4 + k;
-        if (i >= n) break;
-        const float *cf = coef4 + (i / per_batch) * coef_bs;
-        const float mean = cf[0] * x0[i] + cf[1] * x_t[i];
-        const float e = eps ? eps[i] : z[k];
-        x_prev[i] = mean + cf[3] * expf(0.5f * cf[2]) * e;
-    }
-}
-
-__global__ void __launch_bounds__(256) q_sample_kernel(const float *x_start, const float *eps, const float *ab2,
-                                                       const float *nonpad, float *x_t, int B, int M, int T) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * M * T) return;
-    const int t = (int)(i % T);
-    const int b = (int)(i / ((int64_t)M * T));
-    float v = ab2[2 * b] * x_start[i] + ab2[2 * b + 1] * eps[i];
-    if (nonpad) v *= nonpad[(int64_t)b * T + t];
-    x_t[i] = v;
-}
-
-// ---- MFMA layout self test ----------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) selftest_mfma_kernel(float *max_err) {
-    constexpr int K = 8;
-    const int lane = threadIdx.x;
-    auto Af = [](int i, int k) { return 0.25f * (float)((i * 7 + k * 3) % 11) - 1.0f; };
-    auto Bf = [](int k, int j) { return 0.125f * (float)((k * 5 + j * 13) % 17) - 0.75f; };
-    f32x16 acc = {0};
-    for (int k0 = 0; k0 < K; k0 += 2) {
-        const int k = k0 + (lane >> 5);
-        acc = mfma32(Af(lane & 31, k), Bf(k, lane & 31), acc);
-    }
-    float err = 0.0f;
-    for (int r = 0; r < 16; ++r) {
-        const int row = mfma32_row(r, lane), col = lane & 31;
-        float ref = 0.0f;
-        for (int k = 0; k < K; ++k) ref = fmaf(Af(row, k), Bf(k, col), ref);
-        err = fmaxf(err, fabsf(ref - acc[r]));
-    }
-    for (int off = 32; off > 0; off >>= 1) err = fmaxf(err, __shfl_xor(err, off));
-    if (lane == 0) *max_err = err;
-}
-}  // namespace
-
-extern "C" int set_gate(const float *y, float *z, int32_t B, int32_t C, int32_t T, void *stream) {
-    SET_REQUIRE(y && z && B > 0 && C > 0 && T > 0, "set_gate");
-    hipLaunchKernelGGL(gate_kernel, dim3(set_blocks((int64_t)B * C * T, 256)), dim3(256), 0, (hipStream_t)stream, y, z,
-                       B, C, T);
-    return set_check_launch("set_gate");
-}
-extern "C" int set_res_skip(const float *x_in, const float *o, float *x_out, float *skip, int32_t B, int32_t C,
-                            int32_t T, int32_t first, void *stream) {
-    SET_REQUIRE(x_in && o && x_out && skip && B > 0 && C > 0 && T > 0, "set_res_skip");
-    hipLaunchKernelGGL(res_skip_kernel, dim3(set_blocks((int64_t)B * C * T, 256)), dim3(256), 0, (hipStream_t)stream,
-                       x_in, o, x_out, skip, B, C, T, first);
-    return set_check_launch("set_res_skip");
-}
-extern "C" int set_sinusoid_embed(const float *t, float *out, int32_t dim, int32_t n, void *stream) {
-    SET_REQUIRE(t && out && dim >= 4 && (dim % 2) == 0 && n > 0, "set_sinusoid_embed");
-    hipLaunchKernelGGL(sinusoid_kernel, dim3(set_blocks((int64_t)dim * n, 256)), dim3(256), 0, (hipStream_t)stream, t,
-                       out, dim, n);
-    return set_check_launch("set_sinusoid_embed");
-}
-static const uint64_t *g_seed_delta = nullptr;
-const uint64_t *set_seed_delta_ptr() { return g_seed_delta; }
-extern "C" int set_rng_seed_delta(const uint64_t *dev_word) {
-    g_seed_delta = dev_word;
-    return SET_OK;
-}
-
-extern "C" int set_randn(float *out, int64_t n, uint64_t seed, uint64_t offset, void *stream) {
-    SET_REQUIRE(out && n > 0, "set_randn");
-    hipLaunchKernelGGL(randn_kernel, dim3(set_blocks((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, out, n,
-                       seed, offset, g_seed_delta);
-    return set_check_launch("set_randn");
-}
-extern "C" int set_posterior_step(const float *x0, const float *x_t, const float *eps, const float *coef4,
-                                  int64_t coef_bs, float *x_prev, int32_t B, int64_t per_batch, uint64_t seed,
-                                  uint64_t offset, void *stream) {
-    SET_REQUIRE(x0 && x_t && coef4 && x_prev && B > 0 && per_batch > 0, "set_posterior_step");
-    const int64_t n = (int64_t)B * per_batch;
-    hipLaunchKernelGGL(posterior_kernel, dim3(set_blocks((n + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, x0,
-                       x_t, eps, coef4, coef_bs, x_prev, per_batch, n, seed, offset, g_seed_delta);
-    return set_check_launch("set_posterior_step");
-}
-extern "C" int set_q_sample(const float *x_start, const float *eps, const float *ab2, const float *nonpad, float *x_t,
-                            int32_t B, int32_t M, int32_t T, void *stream) {
-    SET_REQUIRE(x_start && eps && ab2 && x_t && B > 0 && M > 0 && T > 0, "set_q_sample");
-    hipLaunchKernelGGL(q_sample_kernel, dim3(set_blocks((int64_t)B * M * T, 256)), dim3(256), 0, (hipStream_t)stream,
-                       x_start, eps, ab2, nonpad, x_t, B, M, T);
-    return set_check_launch("set_q_sample");
-}
-extern "C" int set_selftest_mfma(float *max_err_host, void *stream) {
-    SET_REQUIRE(max_err_host != nullptr, "set_selftest_mfma");
-    float *d = nullptr;
-    SET_HIP(hipMalloc(&d, sizeof(float)), "set_selftest_mfma");
-    hipLaunchKernelGGL(selftest_mfma_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d);
-    int rc = set_check_launch("set_selftest_mfma");
-    if (rc == SET_OK) {
-        hipError_t e = hipMemcpyAsync(max_err_host, d, sizeof(float), hipMemcpyDeviceToHost, (hipStream_t)stream);
-        if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-        if (e != hipSuccess) rc = set_fail(SET_E_LAUNCH, "set_selftest_mfma", hipGetErrorString(e));
-    }
-    (void)hipFree(d);
-    return rc;
-}
-
-// ----------------------------------------------------------------------------------------------------------
-// the reverse loop: enqueue steps x (in-proj, L fused layers, skip-proj, out-proj, posterior)
-// ----------------------------------------------------------------------------------------------------------
-// ----------------------------------------------------------------------------------------------------------
-// Step boundary: everything between the layer stack of step k and the layer stack of step k+1 in ONE launch:
-//   h   = ReLU(W_skip * (skip / sqrt(L)) + b_skip)            (diffnet.py:128-130)
-//   x0  = W_out * h + b_out                                    (diffnet.py:131)
-//   x'  = c1 x0 + c2 x_t + nonzero * exp(logvar/2) * eps       (spec_denoiser.py:86-101, eps explicit or Philox)
-//   xin = ReLU(W_in * x' + b_in)                               (diffnet.py:118-120, input of the next step)
-// One block = one utterance x 64 frames, 4 waves, everything stays in LDS/registers between the three GEMMs.  The
-// four separate launches this replaces were latency-bound (31 + 75 + 51 + 14 us at B=32, T=800).  Weights are the
-// ordinary packed conv images (set_pack_conv_weight); arithmetic order (prologue divide, bias after the sum, Philox
-// quad = 4 consecutive frames of one row) equals the unfused kernels, so results are bit-identical to them.
-// Needs T % 4 == 0 (quad alignment), 256 residual channels, M <= 96 mel bins.
-// ----------------------------------------------------------------------------------------------------------
-struct BoundaryArgs {
-    const float *skip;      // [B][256][T]
-    float *x;               // [B][M][T]  in: x_t, out: x_{t-1}
-    const float *eps;       // [B][M][T] or NULL
-    const float *coef4;     // {c1, c2, logvar, nonzero} of this step (device)
-    const float *w_skip_p, *b_skip, *w_outp_p, *b_outp, *w_in_p, *b_in;
-    float *xin_next;        // [B][256][T] or NULL (last step)
-    float inv_div;          // unused (division by sqrt(L) is done exactly as the conv prologue does: x / p)
-    float div;
-    uint64_t seed, quad_offset;
-    int T, M, MP;           // MP = M rounded up to 16 (rows of the x' tile in LDS, K of the head GEMM)
-};
-constexpr int BD_LD = 64;
-
-__global__ void __launch_bounds__(256, 2) diffnet_boundary_kernel(BoundaryArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];  // [256][64]: skip tile -> h tile -> x' tile
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5, l31 = lane & 31;
-    const int b = blockIdx.y, t0 = blockIdx.x * 64, T = a.T, M = a.M;
-    // ---- phase 1: skip tile / sqrt(L) -> LDS (wave w: rows 64w .. 64w+63, lanes along t; unconditional clamped loads)
-    {
-        const rsrc_t rs = make_rsrc(a.skip + (int64_t)b * DC * T);
-        const unsigned vo = 4u * (unsigned)min(t0 + lane, T - 1);
-        const bool tv = t0 + lane < T;
-        for (int r0 = 0; r0 < 64; r0 += 16) {
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = buf_load(rs, vo, 4u * (unsigned)(64 * w + r0 + u) * (unsigned)T);
-#pragma unroll
-            for (int u = 0; u < 16; ++u) smem[(64 * w + r0 + u) * BD_LD + lane] = tv ? v[u] / a.div : 0.0f;
-        }
-    }
-    __syncthreads();
-    // ---- phase 2: h = ReLU(W_skip * s + b): wave w owns rows [64w, 64w+64) = row blocks 2w, 2w+1
-    f32x16 acc[2][1][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        acc[i][0][0] = (f32x16){0};
-        acc[i][0][1] = (f32x16){0};
-        const float *wp = a.w_skip_p + (int64_t)(2 * w + i) * (DC / 2) * 64 + lane;
-        const float *bp = smem + half * BD_LD + l31;
-        gemm_groups<1, 2, 8>(acc[i], wp, bp, 2 * BD_LD, (DC / 2) / 8, [&](int) {
-            wp += 8 * 64;
-            bp += 8 * 2 * BD_LD;
-        });
-    }
-    __syncthreads();  // every wave is done reading the skip tile
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = 32 * (2 * w + i) + mfma32_row(r, lane);
-            const float bias = a.b_skip[row];
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) smem[row * BD_LD + 32 * cb + l31] = fmaxf(acc[i][0][cb][r] + bias, 0.0f);
-        }
-    __syncthreads();
-    // ---- phase 3: x0 = W_out * h + b: row blocks 0..ceil(M/32)-1 on waves 0..2
-    const int rbn = (M + 31) / 32;
-    f32x16 xo[1][2];
-    xo[0][0] = (f32x16){0};
-    xo[0][1] = (f32x16){0};
-    if (w < rbn) {
-        const float *wp = a.w_outp_p + (int64_t)w * (DC / 2) * 64 + lane;
-        const float *bp = smem + half * BD_LD + l31;
-        gemm_groups<1, 2, 8>(xo, wp, bp, 2 * BD_LD, (DC / 2) / 8, [&](int) {
-            wp += 8 * 64;
-            bp += 8 * 2 * BD_LD;
-        });
-    }
-    __syncthreads();  // h tile consumed
-    if (w < rbn) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = 32 * w + mfma32_row(r, lane);
-            const float bias = a.b_outp[min(row, M - 1)];
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) smem[row * BD_LD + 32 * cb + l31] = row < M ? xo[0][cb][r] + bias : 0.0f;
-        }
-    }
-    __syncthreads();
-    // ---- phase 4: posterior update on quads of 4 consecutive frames (T % 4 == 0: a quad never straddles rows)
-    {
-        const float c1 = a.coef4[0], c2 = a.coef4[1], sig = a.coef4[3] * expf(0.5f * a.coef4[2]);
-        float *xb = a.x + (int64_t)b * M * T;
-        const float *eb = a.eps ? a.eps + (int64_t)b * M * T : nullptr;
-        for (int qi = tid; qi < a.MP * 16; qi += 256) {
-            const int m = qi >> 4, tq = qi & 15, t = t0 + 4 * tq;
-            float *cell = smem + m * BD_LD + 4 * tq;
-            if (m < M && t < T) {
-                const int64_t i = (int64_t)m * T + t;
-                const f32x4 xt = *reinterpret_cast<const f32x4 *>(xb + i);
-                float z[4];
-                if (eb) {
-                    const f32x4 e4 = *reinterpret_cast<const f32x4 *>(eb + i);
-                    z[0] = e4[0]; z[1] = e4[1]; z[2] = e4[2]; z[3] = e4[3];
-                } else {
-                    randn4(a.seed, a.quad_offset + (uint64_t)(((int64_t)b * M * T + i) >> 2), z);
-                }
-                f32x4 o;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float mean = c1 * cell[k] + c2 * xt[k];
-                    o[k] = mean + sig * z[k];
-                }
-                *reinterpret_cast<f32x4 *>(xb + i) = o;
-                *reinterpret_cast<f32x4 *>(cell) = o;
-            } else {
-                *reinterpret_cast<f32x4 *>(cell) = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};  // K padding rows / frames >= T
-            }
-        }
-    }
-    if (!a.xin_next) return;
-    __syncthreads();
-    // ---- phase 5: next step's input projection xin = ReLU(W_in * x' + b_in), K = MP
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        acc[i][0][0] = (f32x16){0};
-        acc[i][0][1] = (f32x16){0};
-        const float *wp = a.w_in_p + (int64_t)(2 * w + i) * (a.MP / 2) * 64 + lane;
-        const float *bp = smem + half * BD_LD + l31;
-        gemm_groups<1, 2, 4>(acc[i], wp, bp, 2 * BD_LD, (a.MP / 2) / 4, [&](int) {
-            wp += 4 * 64;
-            bp += 4 * 2 * BD_LD;
-        });
-    }
-    const rsrc_t ro = make_rsrc(a.xin_next + (int64_t)b * DC * T);
-    // all 32 bias values first: a bias load placed between the stores cannot be moved across them (b_in may alias
-    // xin_next as far as the compiler knows), which serialises one L2 round trip per store
-    float bin[2][16];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) bin[i][r] = (a.b_in + 32 * (2 * w + i) + urow16(r))[4 * half];
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-        if (t0 + 32 * cb + l31 < T) {
-            const unsigned so = 4u * (unsigned)(4 * half * T + t0 + 32 * cb + l31);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int ur = 32 * (2 * w + i) + urow16(r);  // wave-uniform; + 4*half rows in the lane offset
-                    buf_store(fmaxf(acc[i][0][cb][r] + bin[i][r], 0.0f), ro, so, 4u * (unsigned)ur * (unsigned)T);
-                }
-        }
-    }
-}
-
-// ---- the same step boundary on the two-piece fp16 operands (csrc/diffnet_x3.hip, csrc/conv_x2.hip: fp32 operands as two
-// fp16 pieces, three fp16 MFMAs per product, fp32 accumulate).  The fp32 kernel above is bound by its three small GEMMs on
-// the fp32 MFMA pipe (23 us of pipe time per 64-frame tile); here they take a fifth of that.  Same tile, same five phases;
-// the operand tiles live in LDS as [piece][frame][channel] fp16 (rows padded by 16 B), the weights come from the images of
-// set_pack_conv_weight_x2 (A-fragment order, straight from global memory), x0 / x' pass through an fp32 tile for the
-// posterior update exactly as above.  Used by the reverse loop whenever the layer stack runs on two-piece fp16 operands.
-// (operand types, bx_split / bx_mma / bx_gemm and the tile constants: csrc/boundary_x2.h)
-struct BoundaryX2Args {
-    BoundaryArgs g;
-    const unsigned short *w_skip_x2, *w_outp_x2, *w_in_x2;
-    int32_t *err_flag;
-};
-
-__global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2Args ax) {
-    const BoundaryArgs &a = ax.g;
-    extern __shared__ __attribute__((aligned(16))) unsigned char bl[];  // [2][64][BX_XR]: s -> h pieces; x0 / x' (fp32) and x' pieces overlay
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int half = lane >> 5, l31 = lane & 31;
-    const int b = blockIdx.y, t0 = blockIdx.x * 64, T = a.T, M = a.M;
-    const unsigned lane16 = 16u * (unsigned)lane;
-    const unsigned T4 = 4u * (unsigned)T;
-    float amax = 0.0f;
-    // ---- phase 1: skip tile / sqrt(L), split -> LDS [piece][frame][256]: thread (frame f, 64 channels cg)
-    {
-        const int f = lane, cg = w;
-        const rsrc_t rs = make_rsrc(a.skip + (int64_t)b * DC * T);
-        const unsigned vo = 4u * (unsigned)min(t0 + f, T - 1);
-        const bool tv = t0 + f < T;
-        for (int c0 = 0; c0 < 64; c0 += 16) {
-            float v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = buf_load(rs, vo, (unsigned)(64 * cg + c0 + u) * T4);
-#pragma unroll
-            for (int q8 = 0; q8 < 2; ++q8) {
-                bx_u32x4 u0, u1;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    unsigned short p0[2], p1[2];
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const float sv = v[8 * q8 + 2 * e + k] / a.div;
-                        const float x = tv ? sv : 0.0f;
-                        amax = fmaxf(amax, fabsf(x));
-                        bx_split(x, p0[k], p1[k]);
-                    }
-                    u0[e] = (unsigned)p0[0] | ((unsigned)p0[1] << 16);
-                    u1[e] = (unsigned)p1[0] | ((unsigned)p1[1] << 16);
-                }
-                *reinterpret_cast<bx_u32x4 *>(bl + f * BX_XR + (64 * cg + c0 + 8 * q8) * 2) = u0;
-                *reinterpret_cast<bx_u32x4 *>(bl + BX_PIECE + f * BX_XR + (64 * cg + c0 + 8 * q8) * 2) = u1;
-            }
-        }
-    }
-    __syncthreads();
-    auto bfrag256 = [&](int ks, int cb) { return (unsigned)((cb * 32 + l31) * BX_XR + (ks * 16 + half * 8) * 2); };
-    // ---- phase 2: h = ReLU(W_skip s + b): wave w owns rows [64w, 64w+64)
-    {
-        const rsrc_t rw = make_rsrc(ax.w_skip_x2);
-        const float inv = reinterpret_cast<const float *>(ax.w_skip_x2 + (DC / 32) * (DC / 16) * 1024)[1];
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) acc[i][cb] = (f32x16){0};
-        bx_gemm<2>(acc, rw, lane16, 2 * w, DC / 16, DC / 16, bl, BX_PIECE, bfrag256);
-        __syncthreads();  // every wave is done reading the s tile
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    unsigned short p0[4], p1[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int row = 32 * (2 * w + i) + 8 * g + 4 * half + e;
-                        const float h = fmaxf(acc[i][cb][4 * g + e] * inv + a.b_skip[row], 0.0f);
-                        amax = fmaxf(amax, h);
-                        bx_split(h, p0[e], p1[e]);
-                    }
-                    const unsigned off = (unsigned)((cb * 32 + l31) * BX_XR + (32 * (2 * w + i) + 8 * g + 4 * half) * 2);
-                    bx_u32x2 u;
-                    u[0] = (unsigned)p0[0] | ((unsigned)p0[1] << 16); u[1] = (unsigned)p0[2] | ((unsigned)p0[3] << 16);
-                    *reinterpret_cast<bx_u32x2 *>(bl + off) = u;
-                    u[0] = (unsigned)p1[0] | ((unsigned)p1[1] << 16); u[1] = (unsigned)p1[2] | ((unsigned)p1[3] << 16);
-                    *reinterpret_cast<bx_u32x2 *>(bl + BX_PIECE + off) = u;
-                }
-    }
-    __syncthreads();
-    // ---- phase 3: x0 = W_out h + b: row blocks 0 .. ceil(M/32)-1 on waves 0..2; x0 -> fp32 tile xs[96][64] (over piece 0)
-    float *xs = reinterpret_cast<float *>(bl);
-    {
-        const int rbn = (M + 31) / 32;
-        f32x16 xo[1][2];
-        xo[0][0] = (f32x16){0};
-        xo[0][1] = (f32x16){0};
-        const float inv = reinterpret_cast<const float *>(ax.w_outp_x2 + ((M + 31) / 32) * (DC / 16) * 1024)[1];
-        if (w < rbn) bx_gemm<1>(xo, make_rsrc(ax.w_outp_x2), lane16, w, DC / 16, DC / 16, bl, BX_PIECE, bfrag256);
-        __syncthreads();  // h tile consumed
-        if (w < 3) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = 32 * w + mfma32_row(r, lane);
-                const float bias = a.b_outp[min(row, M - 1)];
-#pragma unroll
-                for (int cb = 0; cb < 2; ++cb) xs[row * 64 + 32 * cb + l31] = (w < rbn && row < M) ? xo[0][cb][r] * inv + bias : 0.0f;
-            }
-        }
-    }
-    __syncthreads();
-    // ---- phase 4: posterior update on quads of 4 consecutive frames (T % 4 == 0), as in the fp32 kernel
-    {
-        const float c1 = a.coef4[0], c2 = a.coef4[1], sig = a.coef4[3] * expf(0.5f * a.coef4[2]);
-        float *xb = a.x + (int64_t)b * M * T;
-        const float *eb = a.eps ? a.eps + (int64_t)b * M * T : nullptr;
-        for (int qi = tid; qi < 96 * 16; qi += 256) {
-            const int m = qi >> 4, tq = qi & 15, t = t0 + 4 * tq;
-            float *cell = xs + m * 64 + 4 * tq;
-            if (m < M && t < T) {
-                const int64_t i = (int64_t)m * T + t;
-                const f32x4 xt = *reinterpret_cast<const f32x4 *>(xb + i);
-                float z[4];
-                if (eb) {
-                    const f32x4 e4 = *reinterpret_cast<const f32x4 *>(eb + i);
-                    z[0] = e4[0]; z[1] = e4[1]; z[2] = e4[2]; z[3] = e4[3];
-                } else {
-                    randn4(a.seed, a.quad_offset + (uint64_t)(((int64_t)b * M * T + i) >> 2), z);
-                }
-                f32x4 o;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float mean = c1 * cell[k] + c2 * xt[k];
-                    o[k] = mean + sig * z[k];
-                }
-                *reinterpret_cast<f32x4 *>(xb + i) = o;
-                *reinterpret_cast<f32x4 *>(cell) = o;
-            } else {
-                *reinterpret_cast<f32x4 *>(cell) = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};  // K padding rows / frames >= T
-            }
-        }
-    }
-    if (!a.xin_next) {
-        if (!(amax < 32768.0f) && ax.err_flag) __hip_atomic_store(ax.err_flag, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    __syncthreads();
-    // ---- x' (fp32 [96][64]) -> two fp16 pieces [frame][96] in the piece-1 region: thread (frame f, 24 channels cg)
-    unsigned char *xp = bl + BX_PIECE;
-    constexpr unsigned XP_PIECE = 64 * BX_PR;
-    {
-        const int f = lane, cg = w;
-#pragma unroll
-        for (int q8 = 0; q8 < 3; ++q8) {
-            bx_u32x4 u0, u1;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                unsigned short p0[2], p1[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const float x = xs[(24 * cg + 8 * q8 + 2 * e + k) * 64 + f];
-                    amax = fmaxf(amax, fabsf(x));
-                    bx_split(x, p0[k], p1[k]);
-                }
-                u0[e] = (unsigned)p0[0] | ((unsigned)p0[1] << 16);
-                u1[e] = (unsigned)p1[0] | ((unsigned)p1[1] << 16);
-            }
-            *reinterpret_cast<bx_u32x4 *>(xp + f * BX_PR + (24 * cg + 8 * q8) * 2) = u0;
-            *reinterpret_cast<bx_u32x4 *>(xp + XP_PIECE + f * BX_PR + (24 * cg + 8 * q8) * 2) = u1;
-        }
-    }
-    if (!(amax < 32768.0f) && ax.err_flag) __hip_atomic_store(ax.err_flag, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    // ---- phase 5: next step's input projection xin = ReLU(W_in x' + b_in), K = M rounded up to 32 (zero padded)
-    {
-        const int ngin = ((M + 31) / 32) * 2;  // 16-channel groups of the image (Cin = M rounded up to 32, zero padded)
-        const float inv = reinterpret_cast<const float *>(ax.w_in_x2 + (DC / 32) * ngin * 1024)[1];
-        f32x16 acc[2][2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) acc[i][cb] = (f32x16){0};
-        bx_gemm<2>(acc, make_rsrc(ax.w_in_x2), lane16, 2 * w, ngin, ngin, xp, XP_PIECE,
-                   [&](int ks, int cb) { return (unsigned)((cb * 32 + l31) * BX_PR + (ks * 16 + half * 8) * 2); });
-        const rsrc_t ro = make_rsrc(a.xin_next + (int64_t)b * DC * T);
-        float bin[2][16];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) bin[i][r] = (a.b_in + 32 * (2 * w + i) + urow16(r))[4 * half];
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-            if (t0 + 32 * cb + l31 < T) {
-                const unsigned so = 4u * (unsigned)(4 * half * T + t0 + 32 * cb + l31);
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int ur = 32 * (2 * w + i) + urow16(r);
-                        buf_store(fmaxf(acc[i][cb][r] * inv + bin[i][r], 0.0f), ro, so, 4u * (unsigned)ur * (unsigned)T);
-                    }
-            }
-        }
-    }
-}
-
-static bool boundary_fusable(const SetDiffLoopArgs &a) {
-    if (const char *e = getenv("SET_AMD_FUSED_BOUNDARY"))
-        if (atoi(e) == 0) return false;
-    return a.T % 4 == 0 && a.M <= 96 && a.M >= 2 && ((a.M + 15) / 16 * 16 / 2) % 8 == 0;
-}
-
-static int launch_boundary(const SetDiffLoopArgs &a, int Bg, const float *skip, float *x, const float *eps, int sid,
-                           uint64_t quad_offset, float *xin_next, bool x2, hipStream_t s) {
-    static SetDeviceOnce lds_once;
-    if (int rc = set_lds_optin(lds_once, 80 * 1024, "boundary(attr)", diffnet_boundary_kernel, diffnet_boundary_x2_kernel)) return rc;
-    BoundaryArgs g = {};
-    g.skip = skip; g.x = x; g.eps = eps; g.coef4 = a.coef4 + 4 * sid;
-    g.w_skip_p = a.w_skip_p; g.b_skip = a.b_skip; g.w_outp_p = a.w_outp_p; g.b_outp = a.b_outp;
-    g.w_in_p = a.w_in_p; g.b_in = a.b_in; g.xin_next = xin_next;
-    g.div = sqrtf((float)a.L); g.seed = a.seed; g.quad_offset = quad_offset;
-    g.T = a.T; g.M = a.M; g.MP = (a.M + 15) / 16 * 16;
-    if (x2) {
-        BoundaryX2Args gx = {};
-        gx.g = g;
-        gx.w_skip_x2 = reinterpret_cast<const unsigned short *>(a.w_skip_x2);
-        gx.w_outp_x2 = reinterpret_cast<const unsigned short *>(a.w_outp_x2);
-        gx.w_in_x2 = reinterpret_cast<const unsigned short *>(a.w_in_x2);
-        gx.err_flag = a.err_flag;
-        hipLaunchKernelGGL(diffnet_boundary_x2_kernel, dim3((a.T + 63) / 64, Bg), dim3(256), (size_t)2 * BX_PIECE, s, gx);
-    } else {
-        hipLaunchKernelGGL(diffnet_boundary_kernel, dim3((a.T + 63) / 64, Bg), dim3(256), (size_t)DC * BD_LD * sizeof(float), s, g);
-    }
-    return set_check_launch("set_diffusion_loop(boundary)");
-}
-
-static SetConv1dArgs conv1x1_args(const float *in, const float *wp, const float *bias, float *out, int B, int Cin,
-                                  int Cout, int T) {
-    SetConv1dArgs c = {};
-    c.in = in; c.w = wp; c.bias = bias; c.out = out;
-    c.in_bs = (int64_t)Cin * T; c.in_cs = T; c.out_bs = (int64_t)Cout * T; c.out_cs = T;
-    c.B = B; c.Cin = Cin; c.Cout = Cout; c.K = 1; c.dil = 1; c.pad = 0;
-    c.T_in = T; c.T_iter = T; c.T_out = T; c.out_stride = 1; c.out_off = 0;
-    c.alpha = 1.0f; c.impl = SET_IMPL_MFMA;
-    return c;
-}
-
-// auxiliary streams for utterance groups (created once, never destroyed)
-static hipStream_t g_aux_streams[8] = {nullptr};
-static int aux_stream(int i, hipStream_t *out) {
-    if (!g_aux_streams[i]) SET_HIP(hipStreamCreateWithFlags(&g_aux_streams[i], hipStreamNonBlocking), "aux stream");
-    *out = g_aux_streams[i];
-    return SET_OK;
-}
-
-// enqueue the chain of one utterance group [b0, b0+Bg) on stream s
-static int diffusion_chain(const SetDiffLoopArgs &a, int g, int b0, int Bg, hipStream_t s, hipEvent_t *ev) {
-    const int T = a.T, M = a.M, L = a.L;
-    const int64_t per_batch = (int64_t)M * T;
-    float *x = a.x + (int64_t)b0 * per_batch;
-    float *ws_x0 = a.ws_x0 + (int64_t)b0 * DC * T, *ws_x1 = a.ws_x1 + (int64_t)b0 * DC * T;
-    float *ws_skip = a.ws_skip + (int64_t)b0 * DC * T, *ws_h = a.ws_h + (int64_t)b0 * DC * T;
-    float *ws_x0pred = a.ws_x0pred + (int64_t)b0 * per_batch;
-    const float *condproj = a.condproj ? a.condproj + (int64_t)b0 * L * 512 * T : nullptr;
-    const int tiles_per_utt = (T + NT - 1) / NT;
-    int32_t *sync_ws = a.sync_ws ? a.sync_ws + SQ_GROUP_WORDS * (int64_t)g + 2 * (int64_t)b0 * ((T + 31) / 32) : nullptr;  // per-group slice
-    const uint64_t quads_before = (uint64_t)((int64_t)b0 * per_batch / 4);
-    const uint64_t quads_total = (uint64_t)(((int64_t)a.B * per_batch + 3) / 4);
-    int rc = SET_OK;
-    const bool fused_boundary = boundary_fusable(a);
-    const bool bf16_loop = a.img16_all != nullptr;
-    int n_cu = 0;
-    SET_HIP(set_cu_count(&n_cu), "set_diffusion_loop");
-    // the step boundary on two-piece fp16 operands whenever the layer stack runs on them (same splitting, same range guard)
-    bool boundary_x2 = false;
-    if (a.persistent && !bf16_loop && fused_boundary && a.w_skip_x2 && a.w_outp_x2 && a.w_in_x2 && a.wx3_all && a.x3_mode == 2 &&
-        a.M <= 96) {
-        const int v = stack_variant(Bg, T, a.dilation_cycle_length, a.w1w_all && a.w2w_all, a.w1s_all && a.w2s_all && a.z_ws,
-                                    a.x3_mode, n_cu);
-        boundary_x2 = v == 5 || (v == 3 && !split_f32_pinned());
-    }
-    // the bf16-operand loop takes the split-operand boundary whenever its images are given (round 4: 85 -> 37 us per step at B = 32,
-    // T = 800; it is the fp32-equivalent one, and it raises the same range word, which the caller must read)
-    if (bf16_loop && fused_boundary && a.w_skip_x2 && a.w_outp_x2 && a.w_in_x2 && a.M <= 96) boundary_x2 = true;
-    if (const char *e = getenv("SET_AMD_BOUNDARY_X2")) boundary_x2 = boundary_x2 && atoi(e) != 0;
-    for (int k = 0; k < a.steps && rc == SET_OK; ++k) {
-        const int sid = a.steps - 1 - k;  // diffusion step id t = steps-1 .. 0 (spec_denoiser.py:181)
-        // input projection + ReLU (diffnet.py:118-120); with the fused boundary it is part of the previous step's
-        // boundary launch
-        if (!fused_boundary || k == 0) {
-            SetConv1dArgs cin = conv1x1_args(x, a.w_in_p, a.b_in, ws_x0, Bg, M, DC, T);
-            cin.act = SET_ACT_RELU;
-            rc = set_conv1d(&cin, s);
-            if (rc != SET_OK) break;
-        }
-        float *cur = ws_x0, *nxt = ws_x1;
-        if (ev) (void)hipEventRecord(ev[2 * k], s);
-        if (a.persistent && !bf16_loop) {
-            SetDiffnetStackArgs sa = {};
-            sa.xa = ws_x0; sa.xb = ws_x1; sa.skip = ws_skip;
-            sa.condproj = condproj; sa.cp_bs = (int64_t)L * 512 * T; sa.cp_ls = (int64_t)512 * T;
-            sa.dstep = a.dstep + sid; sa.d_bs = 0; sa.d_cs = a.steps; sa.d_ls = (int64_t)DC * a.steps;
-            sa.w1p_all = a.w1p_all; sa.w2p_all = a.w2p_all; sa.b_dil_all = a.b_dil_all; sa.b_out_all = a.b_out_all;
-            sa.w1w_all = a.w1w_all; sa.w2w_all = a.w2w_all;
-            sa.w1s_all = a.w1s_all; sa.w2s_all = a.w2s_all; sa.wx3_all = a.wx3_all; sa.x3_mode = a.x3_mode;
-            sa.z_ws = a.z_ws ? a.z_ws + (int64_t)b0 * DC * 32 * ((T + 31) / 32) : nullptr;
-            sa.err_flag = a.err_flag;
-            sa.sync_ws = sync_ws;
-            sa.B = Bg; sa.T = T; sa.L = L; sa.dilation_cycle_length = a.dilation_cycle_length;
-            rc = set_diffnet_stack(&sa, s);
-        }
-        // opt-in bf16-operand layers, `fuse` per launch when the workspace is there (csrc/diffnet_bf16.hip: the tile stays on chip
-        // between the layers of a group)
-        int fuse = 1;
-        if (bf16_loop && a.bf16_ws && a.dilation_cycle_length <= 2) {
-            fuse = set_diffnet_layers_bf16_plan(Bg, T, L, a.dilation_cycle_length);  // 10 (128-frame tiles fill the chip) or 5
-            if (const char *e = getenv("SET_AMD_BF16_FUSE")) fuse = atoi(e) < 1 ? 1 : (atoi(e) > 16 ? 16 : atoi(e));
-            if (fuse > 1 && a.bf16_ws_floats < set_diffnet_layers_bf16_scratch_floats(a.B, T, 0, fuse, a.dilation_cycle_length)) fuse = 1;
-        }
-        for (int l = 0; l < L && rc == SET_OK && bf16_loop && fuse > 1; l += fuse) {
-            SetDiffnetLayersBf16Args fa = {};
-            fa.x_in = cur; fa.x_out = nxt; fa.skip = ws_skip;
-            fa.cond = a.cond + (int64_t)b0 * 192 * T;
-            fa.dstep = a.dstep + sid; fa.d_bs = 0; fa.d_cs = a.steps; fa.d_ls = (int64_t)DC * a.steps;
-            fa.img = reinterpret_cast<const uint16_t *>(a.img16_all) + (int64_t)l * set_diffnet_layer_bf16_image_size();
-            fa.b_dil = a.b_dil_all + (int64_t)l * 512; fa.b_cond = a.b_cond_all + (int64_t)l * 512; fa.b_out = a.b_out_all + (int64_t)l * 512;
-            // utterance groups (n_groups > 1) run concurrently on their own streams and the 128-frame kernel indexes its private skip
-            // rows by (blockIdx.y, blockIdx.x) of its own launch: every group gets its own slice (per-utterance floats do not depend on B)
-            const int64_t per_utt = set_diffnet_layers_bf16_scratch_floats(1, T, 0, fuse, a.dilation_cycle_length);
-            fa.scratch = a.bf16_ws + (int64_t)b0 * per_utt; fa.scratch_floats = (int64_t)Bg * per_utt;
-            fa.B = Bg; fa.T = T; fa.l0 = l; fa.nl = L - l < fuse ? L - l : fuse; fa.dilation_cycle_length = a.dilation_cycle_length;
-            fa.first = (l == 0);
-            rc = set_diffnet_layers_fwd_bf16(&fa, s);
-            float *tmp = cur; cur = nxt; nxt = tmp;
-        }
-        for (int l = 0; l < L && rc == SET_OK && bf16_loop && fuse == 1; ++l) {
-            // one launch per layer: conditioner projection inside the layer GEMM
-            SetDiffnetLayerBf16Args la = {};
-            la.x_in = cur; la.x_out = nxt; la.skip = ws_skip;
-            la.cond = a.cond + (int64_t)b0 * 192 * T;
-            la.dstep = a.dstep + (int64_t)l * DC * a.steps + sid;
-            la.d_bs = 0; la.d_cs = a.steps;
-            la.img = reinterpret_cast<const uint16_t *>(a.img16_all) + (int64_t)l * set_diffnet_layer_bf16_image_size();
-            la.b_dil = a.b_dil_all + (int64_t)l * 512; la.b_cond = a.b_cond_all + (int64_t)l * 512;
-            la.b_out = a.b_out_all + (int64_t)l * 512;
-            la.B = Bg; la.T = T; la.dil = 1 << (l % a.dilation_cycle_length); la.first = (l == 0);
-            rc = set_diffnet_layer_fwd_bf16(&la, s);
-            float *tmp = cur; cur = nxt; nxt = tmp;
-        }
-        for (int l = 0; l < L && rc == SET_OK && !a.persistent && !bf16_loop; ++l) {
-            SetDiffnetLayerArgs la = {};
-            la.x_in = cur; la.x_out = nxt; la.skip = ws_skip;
-            la.condproj = condproj + (int64_t)l * 512 * T;
-            la.cp_bs = (int64_t)L * 512 * T;
-            la.dstep = a.dstep + (int64_t)l * DC * a.steps + sid;
-            la.d_bs = 0; la.d_cs = a.steps;
-            la.w1p = a.w1p_all + (int64_t)l * (512 * 768); la.b_dil = a.b_dil_all + (int64_t)l * 512;
-            la.w2p = a.w2p_all + (int64_t)l * (512 * 256); la.b_out = a.b_out_all + (int64_t)l * 512;
-            la.B = Bg; la.T = T; la.dil = 1 << (l % a.dilation_cycle_length); la.first = (l == 0);
-            rc = set_diffnet_layer(&la, s);
-            float *tmp = cur; cur = nxt; nxt = tmp;
-        }
-        if (ev) (void)hipEventRecord(ev[2 * k + 1], s);
-        if (rc != SET_OK) break;
-        const float *eps = a.noise ? a.noise + (int64_t)k * a.B * per_batch + (int64_t)b0 * per_batch : nullptr;
-        if (fused_boundary) {
-            // only the skip sum feeds the output head (diffnet.py:128); the next step's stack input buffer is ws_x0
-            rc = launch_boundary(a, Bg, ws_skip, x, eps, sid, (uint64_t)(k + 1) * quads_total + quads_before,
-                                 k + 1 < a.steps ? ws_x0 : nullptr, boundary_x2, s);
-            continue;
-        }
-        // skip sum / sqrt(L) -> skip_projection -> ReLU -> output_projection (diffnet.py:128-131)
-        SetConv1dArgs cs = conv1x1_args(ws_skip, a.w_skip_p, a.b_skip, ws_h, Bg, DC, DC, T);
-        cs.pro = SET_PRO_DIV; cs.pro_param = sqrtf((float)L); cs.act = SET_ACT_RELU;
-        rc = set_conv1d(&cs, s);
-        if (rc != SET_OK) break;
-        SetConv1dArgs co = conv1x1_args(ws_h, a.w_outp_p, a.b_outp, ws_x0pred, Bg, DC, M, T);
-        rc = set_conv1d(&co, s);
-        if (rc != SET_OK) break;
-        // Philox counters are global element quads, so the noise does not depend on the grouping
-        rc = set_posterior_step(ws_x0pred, x, eps, a.coef4 + 4 * sid, 0, x, Bg, per_batch, a.seed,
-                                (uint64_t)(k + 1) * quads_total + quads_before, s);
-    }
-    return rc;
-}
-
-extern "C" int set_diffusion_loop(const SetDiffLoopArgs *args, void *stream) {
-    SET_REQUIRE(args != nullptr, "set_diffusion_loop");
-    const SetDiffLoopArgs &a = *args;
-    SET_REQUIRE(a.B > 0 && a.T > 0 && a.M > 0 && a.L > 0 && a.steps > 0 && a.dilation_cycle_length >= 1,
-                "set_diffusion_loop");
-    SET_REQUIRE(a.x && a.dstep && a.coef4 && a.w_in_p && a.b_in && a.b_dil_all && a.b_out_all && a.w_skip_p && a.b_skip &&
-                    a.w_outp_p && a.b_outp, "set_diffusion_loop");
-    if (a.img16_all) {
-        SET_REQUIRE(a.cond && a.b_cond_all, "set_diffusion_loop(bf16 loop needs cond and b_cond_all)");
-    } else {
-        SET_REQUIRE(a.condproj && a.w1p_all && a.w2p_all, "set_diffusion_loop");
-        SET_REQUIRE(!a.persistent || a.sync_ws, "set_diffusion_loop(persistent needs sync_ws)");
-    }
-    SET_REQUIRE(a.ws_x0 && a.ws_x1 && a.ws_skip && a.ws_h && a.ws_x0pred, "set_diffusion_loop");
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t per_batch = (int64_t)a.M * a.T;
-    int G = a.n_groups < 1 ? 1 : (a.n_groups > 8 ? 8 : a.n_groups);
-    if (G > a.B) G = a.B;
-    if (per_batch % 4 != 0) G = 1;  // group slices must start on a Philox quad boundary
-    const bool timing = a.layer_span_ms != nullptr;
-    hipEvent_t *ev = nullptr;
-    if (timing) {
-        ev = new hipEvent_t[(size_t)2 * a.steps * G];
-        for (int i = 0; i < 2 * a.steps * G; ++i) SET_HIP(hipEventCreate(&ev[i]), "set_diffusion_loop(event)");
-    }
-    hipEvent_t loop_ev[2] = {nullptr, nullptr};
-    if (a.loop_ms) {
-        SET_HIP(hipEventCreate(&loop_ev[0]), "set_diffusion_loop(event)");
-        SET_HIP(hipEventCreate(&loop_ev[1]), "set_diffusion_loop(event)");
-        (void)hipEventRecord(loop_ev[0], s);
-    }
-    int rc = SET_OK;
-    if (G == 1) {
-        rc = diffusion_chain(a, 0, 0, a.B, s, ev);
-    } else {
-        hipEvent_t fork = nullptr, join[8] = {nullptr};
-        SET_HIP(hipEventCreateWithFlags(&fork, hipEventDisableTiming), "set_diffusion_loop(fork)");
-        SET_HIP(hipEventRecord(fork, s), "set_diffusion_loop(fork)");
-        for (int g = 0; g < G && rc == SET_OK; ++g) {
-            const int b0 = (int)((int64_t)a.B * g / G), b1 = (int)((int64_t)a.B * (g + 1) / G);
-            hipStream_t sg;
-            rc = aux_stream(g, &sg);
-            if (rc != SET_OK) break;
-            SET_HIP(hipStreamWaitEvent(sg, fork, 0), "set_diffusion_loop(fork wait)");
-            rc = diffusion_chain(a, g, b0, b1 - b0, sg, ev ? ev + (size_t)2 * a.steps * g : nullptr);
-            SET_HIP(hipEventCreateWithFlags(&join[g], hipEventDisableTiming), "set_diffusion_loop(join)");
-            SET_HIP(hipEventRecord(join[g], sg), "set_diffusion_loop(join)");
-            SET_HIP(hipStreamWaitEvent(s, join[g], 0), "set_diffusion_loop(join wait)");
-        }
-        (void)hipEventDestroy(fork);
-        for (int g = 0; g < G; ++g)
-            if (join[g]) (void)hipEventDestroy(join[g]);
-    }
-    if (a.loop_ms) (void)hipEventRecord(loop_ev[1], s);
-    if (timing || a.loop_ms) {
-        if (rc == SET_OK) {
-            hipError_t e = hipStreamSynchronize(s);
-            if (e != hipSuccess) rc = set_fail(SET_E_LAUNCH, "set_diffusion_loop(sync)", hipGetErrorString(e));
-        }
-        if (rc == SET_OK && timing) {
-            for (int k = 0; k < a.steps; ++k) {
-                float acc_ms = 0.0f;
-                for (int g = 0; g < G; ++g) {
-                    float ms = 0.0f;
-                    (void)hipEventElapsedTime(&ms, ev[(size_t)2 * a.steps * g + 2 * k], ev[(size_t)2 * a.steps * g + 2 * k + 1]);
-                    acc_ms += ms;
-                }
-                a.layer_span_ms[k] = acc_ms / (float)G;
-            }
-        }
-        if (rc == SET_OK && a.loop_ms) (void)hipEventElapsedTime(a.loop_ms, loop_ev[0], loop_ev[1]);
-    }
-    if (ev) {
-        for (int i = 0; i < 2 * a.steps * G; ++i) (void)hipEventDestroy(ev[i]);
-        delete[] ev;
-    }
-    if (loop_ev[0]) { (void)hipEventDestroy(loop_ev[0]); (void)hipEventDestroy(loop_ev[1]); }
-    return rc;
-}
-
-extern "C" int64_t set_sizeof_conv1d_args(void) { return (int64_t)sizeof(SetConv1dArgs); }
-extern "C" int64_t set_sizeof_diffnet_layer_args(void) { return (int64_t)sizeof(SetDiffnetLayerArgs); }
-extern "C" int64_t set_sizeof_diff_loop_args(void) { return (int64_t)sizeof(SetDiffLoopArgs); }

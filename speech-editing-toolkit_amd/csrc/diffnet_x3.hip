@@ -35,6 +35,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "diffnet_host.h"
 #include "stack_queue.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
@@ -1539,8 +1540,8 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
 
 }  // namespace
 
-// called by set_diffnet_stack (csrc/diffnet.hip) for the row-split variant when two-piece fp16 images are given
-int set_launch_diffnet_stack_split_x2(const SetDiffnetStackArgs &a, hipStream_t s) {
+// the row-split family of the plan on two-piece fp16 operands (p.split_x2)
+int set_launch_diffnet_stack_split_x2(const SetDiffnetStackArgs &a, const StackPlan &p, hipStream_t s) {
     static SetDeviceOnce lds_once;
     if (int rc = set_lds_optin(lds_once, 80 * 1024, "set_diffnet_stack(split x2 attr)", diffnet_stack_split_x2_kernel)) return rc;
     const int tiles = (a.T + 31) / 32, nt = a.B * tiles;
@@ -1549,9 +1550,7 @@ int set_launch_diffnet_stack_split_x2(const SetDiffnetStackArgs &a, hipStream_t 
     const size_t ldsz = (size_t)2 * piece_bytes + (64 * 32 + XC) * sizeof(float) + 16;
     SET_HIP(set_zero_async(a.sync_ws, stack_sync_words(SQ_ROW_SPLIT, nt) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
     // 8 L2-warmer blocks (one per XCD) when the chip has CUs to spare and the block -> XCD round-robin lines them up with the parts
-    int n_cu = 0;
-    (void)set_cu_count(&n_cu);  // (stays 0 when the query fails: no warmers)
-    const int extra = (4 * nt + 8 <= n_cu && a.L > 1) ? 8 : 0;  // (block q: XCD q % 8, part q & 3 = (q % 8) & 3 -- consistent)
+    const int extra = (4 * nt + 8 <= p.n_cu && a.L > 1) ? 8 : 0;  // (block q: XCD q % 8, part q & 3 = (q % 8) & 3 -- consistent)
     // agent-scope loads for the tiles other blocks produced instead of an acquire fence after each wait (measured in round 3 against
     // the fences: 62.7 -> 61.4 ms per 100 steps at B = 1, 66.9 -> 62.3 at B = 2 (T = 800), bit-identical either way).  A run-time
     // argument on purpose: folded into the kernel as a constant it changes the register allocation and measured ~7 % slower at B = 1
@@ -1585,46 +1584,18 @@ extern "C" int set_pack_diffnet_layer_x3(const float *w_dil, const float *w_out,
     return set_check_launch("set_pack_diffnet_layer_x3");
 }
 
-// does set_launch_diffnet_stack_x3 take the Winograd form (diffnet_stack_x3v_kernel) for this shape?  Returns the column blocks per tile:
-// 0 = direct form, 2 = 64-frame tiles, 3 = 96-frame tiles.  SET_AMD_X3_WINO=0 pins the direct form, =2 / =3 the tile width.
-int set_x3_winograd_selected(int x3_mode, int B, int T, int dilation_cycle_length, int n_cu) {
-    if (x3_mode != 2 || dilation_cycle_length != 1 || T % 2 != 0) return 0;
-    const int64_t tiles64 = (int64_t)B * ((T + 63) / 64);
-    bool narrow = 5 * tiles64 < 3 * (int64_t)n_cu;
-    if (const char *e = getenv("SET_AMD_X3_TILE")) narrow = atoi(e) == 32;
-    if (narrow) return 0;
-    if (const char *e = getenv("SET_AMD_X3_WINO")) {
-        const int v = atoi(e);
-        if (v <= 0) return 0;
-        if (v == 2 || v == 3) return v;
-    }
-    // 96-frame tiles once every CU has a tile chain of them (B = 32, T = 800: 267 chains for 256 CUs; below that the workers wait for each
-    // other: B = 24 123 k frames/s on 96-frame tiles against 149 k on 64-frame ones, profiles/r06_x3v_nb2_ab.log)
-    const int64_t tiles96 = ((int64_t)B * ((T + 31) / 32) + 2) / 3;
-    return tiles96 >= (int64_t)n_cu ? 3 : 2;
-}
-
-// called by set_diffnet_stack (csrc/diffnet.hip) once it has picked this kernel
-int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, int n_cu, hipStream_t s) {
-    SET_REQUIRE(a.x3_mode == 2 || a.x3_mode == 3, "set_diffnet_stack(x3_mode must be 2 = f16x2 or 3 = bf16x3)");
-    // tile width: 64 frames from ~0.6 tiles per CU on; below that 32-frame tiles (twice the tasks, each about half as long:
-    // the time of a layer is the time of one task while the chip is not full).  SET_AMD_X3_TILE=32|64 overrides.
-    const int64_t tiles64 = (int64_t)a.B * ((a.T + 63) / 64);
-    bool narrow = 5 * tiles64 < 3 * (int64_t)n_cu;
-    if (const char *e = getenv("SET_AMD_X3_TILE")) narrow = atoi(e) == 32;
-    // block shape: one 8-wave block per CU.  (Round 3 also shipped two 4-wave blocks per CU behind SET_AMD_X3_WAVES=4 -- bit-identical,
-    // never faster: B = 32 1.78 ms per 20 layers (8 waves) vs 1.94 - 2.38 ms, B = 64 3.65 vs 3.69 ms with the clock dropping from 1.88
-    // to 1.63 GHz; profiles/r03_x3_pair_probe.log -- but its 64-frame instantiation spilled registers, which confounded the
-    // comparison; round 4 measured the power limit directly instead (profiles/r04_power.log, r04_mfma_ceiling.log) and removed the
-    // variant from the library.  The NU template parameter of the kernel stays for tools/build_exp.sh experiments.)
-    // round 6: Winograd F(2,3) form of GEMM 1 on 64- / 96-frame tiles (dilation 1, even T; SET_AMD_X3_WINO=0 keeps the direct form) -- see
-    // diffnet_stack_x3v_kernel (its 8-byte loads of frame pairs need 8-byte aligned tensors and even strides; anything else takes the direct form)
-    const bool al8 = ((reinterpret_cast<uintptr_t>(a.condproj) | reinterpret_cast<uintptr_t>(a.xa) | reinterpret_cast<uintptr_t>(a.xb)) & 7) == 0 &&
-                     ((a.cp_bs | a.cp_ls) & 1) == 0;
-    const int wino = al8 ? set_x3_winograd_selected(a.x3_mode, a.B, a.T, a.dilation_cycle_length, n_cu) : 0;
-    if (wino == 3) return launch_x3v<3>(a, n_cu, s);
-    if (wino == 2) return launch_x3v<2>(a, n_cu, s);
-    if (a.x3_mode == 2)
-        return narrow ? launch_x3<SplitF16x2, 1, 1>(a, n_cu, s) : launch_x3<SplitF16x2, 1, 2>(a, n_cu, s);
-    return narrow ? launch_x3<SplitBf16x3, 1, 1>(a, n_cu, s) : launch_x3<SplitBf16x3, 1, 2>(a, n_cu, s);
+// the split-operand kernels (families 4 and 5 of the plan), in the form the plan picked:
+//   tile width: 64 frames from ~0.6 tiles per CU on; below that 32-frame tiles (twice the tasks, each about half as long: the time of a layer
+//   is the time of one task while the chip is not full).
+//   block shape: one 8-wave block per CU.  (Round 3 also shipped two 4-wave blocks per CU behind SET_AMD_X3_WAVES=4 -- bit-identical,
+//   never faster: B = 32 1.78 ms per 20 layers (8 waves) vs 1.94 - 2.38 ms, B = 64 3.65 vs 3.69 ms with the clock dropping from 1.88
+//   to 1.63 GHz; profiles/r03_x3_pair_probe.log -- but its 64-frame instantiation spilled registers, which confounded the
+//   comparison; round 4 measured the power limit directly instead (profiles/r04_power.log, r04_mfma_ceiling.log) and removed the
+//   variant from the library.  The NU template parameter of the kernel stays for tools/build_exp.sh experiments.)
+//   round 6: Winograd F(2,3) form of GEMM 1 on 64- / 96-frame tiles (two-piece fp16, dilation 1, even T) -- see diffnet_stack_x3v_kernel
+int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, const StackPlan &p, hipStream_t s) {
+    if (p.x3_wino) return p.x3_ncb == 3 ? launch_x3v<3>(a, p.n_cu, s) : launch_x3v<2>(a, p.n_cu, s);
+    if (p.family == STACK_X3_F16)
+        return p.x3_ncb == 1 ? launch_x3<SplitF16x2, 1, 1>(a, p.n_cu, s) : launch_x3<SplitF16x2, 1, 2>(a, p.n_cu, s);
+    return p.x3_ncb == 1 ? launch_x3<SplitBf16x3, 1, 1>(a, p.n_cu, s) : launch_x3<SplitBf16x3, 1, 2>(a, p.n_cu, s);
 }

@@ -38,7 +38,7 @@ def compiled():
 
 HOT = {  # file -> kernel-name fragments whose MFMAs must not sit behind a drained ring
     "diffnet_x3.hip": ("diffnet_stack_x3_kernel", "diffnet_stack_x3v_kernel", "diffnet_stack_split_x2_kernel"),
-    "diffnet.hip": ("diffnet_boundary_x2_kernel",),
+    "boundary.hip": ("diffnet_boundary_x2_kernel",),
     "diffnet_bf16.hip": ("diffnet_layers_t128_bf16_kernel", "diffnet_layers_reg_bf16_kernel", "diffnet_layer_fwd_bf16_kernel", "diffnet_layer_bwd_bf16_kernel"),
 }
 
