@@ -371,8 +371,9 @@ int set_q_sample(const float *x_start, const float *eps, const float *ab2, const
                  int32_t B, int32_t M, int32_t T, void *stream);
 /* fill with N(0,1): Philox4x32-10 + Box-Muller (throughput runs; spec_denoiser.py:180) */
 int set_randn(float *out, int64_t n, uint64_t seed, uint64_t offset, void *stream);
-/* Graph capture of a training step: every Philox kernel launched through set_randn / set_posterior_step / set_dropout adds the device
- * word *dev_word to its seed argument (NULL = off, the default).  A captured step carries the seeds of the step it was captured at; the
+/* Graph capture of a training step: every Philox kernel launched through set_randn / set_posterior_step / set_dropout, and the fused
+ * step boundary of set_diffusion_loop (which replaces set_posterior_step there), adds the device word *dev_word to its seed argument
+ * (NULL = off, the default).  A captured step carries the seeds of the step it was captured at; the
  * replay of step k stores (seed_k - seed_captured) in the word before it launches the graph and draws exactly the numbers the eager
  * step k draws.  Process-wide; the word must stay allocated while it is set. */
 int set_rng_seed_delta(const uint64_t *dev_word);

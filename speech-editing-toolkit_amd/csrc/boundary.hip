@@ -9,7 +9,8 @@
 // One block = one utterance x 64 frames, 4 waves, everything stays in LDS/registers between the three GEMMs.  The
 // four separate launches this replaces were latency-bound (31 + 75 + 51 + 14 us at B=32, T=800).  Weights are the
 // ordinary packed conv images (set_pack_conv_weight); arithmetic order (prologue divide, bias after the sum, Philox
-// quad = 4 consecutive frames of one row) equals the unfused kernels, so results are bit-identical to them.
+// quad = 4 consecutive frames of one row, the device word of set_rng_seed_delta added to the seed) equals the unfused kernels, so
+// results are bit-identical to them.
 // Needs T % 4 == 0 (quad alignment), 256 residual channels, M <= 96 mel bins.
 // ----------------------------------------------------------------------------------------------------------
 #include <stdlib.h>
@@ -32,6 +33,7 @@ struct BoundaryArgs {
     float inv_div;          // unused (division by sqrt(L) is done exactly as the conv prologue does: x / p)
     float div;
     uint64_t seed, quad_offset;
+    const uint64_t *seed_delta;  // set_rng_seed_delta (may be NULL): added to the seed, as set_posterior_step does
     int T, M, MP;           // MP = M rounded up to 16 (rows of the x' tile in LDS, K of the head GEMM)
 };
 constexpr int BD_LD = 64;
@@ -107,6 +109,8 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_kernel(BoundaryArgs a
     // ---- phase 4: posterior update on quads of 4 consecutive frames (T % 4 == 0: a quad never straddles rows)
     {
         const float c1 = a.coef4[0], c2 = a.coef4[1], sig = a.coef4[3] * expf(0.5f * a.coef4[2]);
+        uint64_t seed = a.seed;
+        if (a.seed_delta) seed += *a.seed_delta;  // set_rng_seed_delta: see randn_kernel (one wave-uniform load)
         float *xb = a.x + (int64_t)b * M * T;
         const float *eb = a.eps ? a.eps + (int64_t)b * M * T : nullptr;
         for (int qi = tid; qi < a.MP * 16; qi += 256) {
@@ -120,7 +124,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_kernel(BoundaryArgs a
                     const f32x4 e4 = *reinterpret_cast<const f32x4 *>(eb + i);
                     z[0] = e4[0]; z[1] = e4[1]; z[2] = e4[2]; z[3] = e4[3];
                 } else {
-                    randn4(a.seed, a.quad_offset + (uint64_t)(((int64_t)b * M * T + i) >> 2), z);
+                    randn4(seed, a.quad_offset + (uint64_t)(((int64_t)b * M * T + i) >> 2), z);
                 }
                 f32x4 o;
 #pragma unroll
@@ -286,6 +290,8 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2A
     // ---- phase 4: posterior update on quads of 4 consecutive frames (T % 4 == 0), as in the fp32 kernel
     {
         const float c1 = a.coef4[0], c2 = a.coef4[1], sig = a.coef4[3] * expf(0.5f * a.coef4[2]);
+        uint64_t seed = a.seed;
+        if (a.seed_delta) seed += *a.seed_delta;  // set_rng_seed_delta: see randn_kernel (one wave-uniform load)
         float *xb = a.x + (int64_t)b * M * T;
         const float *eb = a.eps ? a.eps + (int64_t)b * M * T : nullptr;
         for (int qi = tid; qi < 96 * 16; qi += 256) {
@@ -299,7 +305,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2A
                     const f32x4 e4 = *reinterpret_cast<const f32x4 *>(eb + i);
                     z[0] = e4[0]; z[1] = e4[1]; z[2] = e4[2]; z[3] = e4[3];
                 } else {
-                    randn4(a.seed, a.quad_offset + (uint64_t)(((int64_t)b * M * T + i) >> 2), z);
+                    randn4(seed, a.quad_offset + (uint64_t)(((int64_t)b * M * T + i) >> 2), z);
                 }
                 f32x4 o;
 #pragma unroll
@@ -392,7 +398,7 @@ int launch_boundary(const SetDiffLoopArgs &a, int Bg, const float *skip, float *
     g.skip = skip; g.x = x; g.eps = eps; g.coef4 = a.coef4 + 4 * sid;
     g.w_skip_p = a.w_skip_p; g.b_skip = a.b_skip; g.w_outp_p = a.w_outp_p; g.b_outp = a.b_outp;
     g.w_in_p = a.w_in_p; g.b_in = a.b_in; g.xin_next = xin_next;
-    g.div = sqrtf((float)a.L); g.seed = a.seed; g.quad_offset = quad_offset;
+    g.div = sqrtf((float)a.L); g.seed = a.seed; g.quad_offset = quad_offset; g.seed_delta = set_seed_delta_ptr();
     g.T = a.T; g.M = a.M; g.MP = (a.M + 15) / 16 * 16;
     if (x2) {
         BoundaryX2Args gx = {};
