@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SET_AMD_ABI_VERSION 2
+#define SET_AMD_ABI_VERSION 3
 
 /* error codes */
 #define SET_OK 0
@@ -607,10 +607,8 @@ int set_partial_rows_sum(const float *part, float *out, int32_t groups, int32_t 
 int set_step_proj_fwd(const float *h, const float *w, int64_t w_ls, const float *b, int64_t b_ls, float *out, int32_t L, int32_t C,
                       int32_t N, void *stream);
 int64_t set_step_proj_bwd_scratch_floats(int32_t L, int32_t C, int32_t N);
-int set_step_proj_bwd(const float *h, const float *g, const float *w, int64_t w_ls, float *dh, float *dw, int64_t dw_ls, float *db,
-                      int64_t db_ls, float *scratch, int32_t L, int32_t C, int32_t N, void *stream);
-/* its two halves on their own (set_step_proj_bwd = _dh then _dw): dh feeds the backward chain, dW / db are parameter gradients
- * the host side may launch on its second stream */
+/* the backward in two entry points: dh feeds the backward chain, dW / db are parameter gradients the host side may launch on its
+ * second stream */
 int set_step_proj_bwd_dh(const float *g, const float *w, int64_t w_ls, float *dh, float *scratch, int32_t L, int32_t C, int32_t N,
                          void *stream);
 int set_step_proj_bwd_dw(const float *h, const float *g, float *dw, int64_t dw_ls, float *db, int64_t db_ls, int32_t L, int32_t C,
@@ -645,16 +643,20 @@ typedef struct SetPackF32Desc {
 int64_t set_sizeof_pack_f32_desc(void);
 int64_t set_fill_pack_f32_desc(SetPackF32Desc *d, int32_t kind, int32_t dil);
 int set_pack_conv_weights_f32_batch(const SetPackF32Desc *descs_dev, int32_t n, int64_t total, void *stream);
-/* out[c] += sum_{b,t} x[b][c][t]   (bias gradients) */
-int set_channel_sum(const float *x, float *out, int32_t B, int32_t C, int32_t T, void *stream);
 
-/* Deterministic reductions of the training path.  The entry points above that accumulate with fp32 atomics
- * (set_channel_sum, set_weighted_sum, set_sumsq, the `sums` pass of set_dur_loss / set_pitch_loss, set_embedding_bwd,
- * set_expand_states_bwd) give results whose last bits depend on the arrival order of the blocks.  The *_det variants
- * below write one partial result per block / slice into `scratch` and combine them in a fixed order: bit-identical from
- * run to run (what makes a resumed training run repeat the uninterrupted one exactly).  `scratch` may be reused by the
- * next call on the same stream.  Sizes (floats): channel_sum 2048 + C; weighted_sum 1024; sumsq 2048; dur 4 B;
- * pitch 4 ceil(B T / 256); scatter_rows B * set_scatter_rows_segments(T) * n_rows * C. */
+/* Reductions of the training path.  Every sum that feeds a loss or a gradient is ordered: the entry points below write one
+ * partial result per block / slice into `scratch` and combine them in a fixed order, so the result is bit-identical from
+ * run to run (what makes a resumed training run repeat the uninterrupted one exactly).  There is no form that accumulates
+ * with fp32 atomics, whose last bits would depend on the arrival order of the blocks; the one exception is the split-K
+ * branch of set_conv1d_wgrad (SET_IMPL_MFMA), which the training path does not take (it uses set_conv1d_wgrad_det).
+ * `scratch` is required; it may be reused by the next call on the same stream.  Sizes (floats): channel_sum 2048 + C;
+ * weighted_sum 1024; sumsq 2048; dur 4 B; pitch 4 ceil(B T / 256); scatter_rows B * set_scatter_rows_segments(T) * n_rows * C.
+ *   set_channel_sum_det:  out[c] += sum_{b,t} x[b][c][t]   (bias gradients)
+ *   set_weighted_sum_det: out[0] += sum_i x[i] * (w ? w[i/inner] : 1)
+ *   set_sumsq_det:        out[0] += sum g[i]^2
+ *   set_dur_loss_sums_det (speech_editing_base.py:58-90):    sums[0..3] += {sum nonpad*d^2, sum nonpad, sum wordmask*dw^2, sum wordmask}
+ *   set_pitch_loss_sums_det (speech_editing_base.py:92-108): sums[0..3] += {sum nonpad*bce, sum nonpad, sum nv*|df0|, sum nv}
+ *                         on channel-major pitch_pred [B][2][T] (row 0 f0, row 1 uv logit) */
 int set_channel_sum_det(const float *x, float *out, int32_t B, int32_t C, int32_t T, float *scratch, void *stream);
 int set_weighted_sum_det(const float *x, const float *w, float *out, int64_t n, int64_t inner, float *scratch, void *stream);
 int set_sumsq_det(const float *g, float *out, int64_t n, float *scratch, void *stream);
@@ -685,9 +687,9 @@ int set_gate_bwd(const float *y, const float *dz, float *dy, int32_t B, int32_t 
 /* backward of set_res_skip: dx = dx_out/sqrt2 ; d_o[:, :C] = dx_out/sqrt2 ; d_o[:, C:] = dskip */
 int set_res_skip_bwd(const float *dx_out, const float *dskip, float *dx, float *d_o, int32_t B, int32_t C, int32_t T,
                      void *stream);
-/* backward of set_layernorm_ch; dgamma/dbeta are accumulated (+=).  `partial`: scratch of
- * set_layernorm_ch_bwd_scratch(B, C, T) floats (contents irrelevant) for a contention-free two-pass reduction of
- * dgamma/dbeta; NULL falls back to one atomic per (block, channel), which serialises across XCDs. */
+/* backward of set_layernorm_ch; dgamma/dbeta are accumulated (+=).  `partial` is required: scratch of
+ * set_layernorm_ch_bwd_scratch(B, C, T) floats (contents irrelevant) that takes one row of dgamma/dbeta partial sums per
+ * block; a second launch adds the rows in block order (NULL: SET_E_INVALID). */
 int64_t set_layernorm_ch_bwd_scratch(int32_t B, int32_t C, int32_t T);
 int set_layernorm_ch_bwd(const float *x, const float *gamma, const float *mask, const float *dy, float *dx,
                          float *dgamma, float *dbeta, float *partial, int32_t B, int32_t C, int32_t T, float eps,
@@ -695,13 +697,6 @@ int set_layernorm_ch_bwd(const float *x, const float *gamma, const float *mask, 
 /* the same with dx = (LayerNorm gradient) + add [B][C][T]: the residual branch of a pre-LN sub-block joins inside the launch */
 int set_layernorm_ch_bwd_add(const float *x, const float *gamma, const float *mask, const float *dy, const float *add, float *dx,
                              float *dgamma, float *dbeta, float *partial, int32_t B, int32_t C, int32_t T, float eps, void *stream);
-/* dtable[idx[b][t]][c] += scale * dout[b][c][t], except for row `padding_idx` (-1: none), whose gradient stays 0
- * as with nn.Embedding(padding_idx=...) (modules/commons/layers.py:45-50) */
-int set_embedding_bwd(const int64_t *idx, const float *dout, float *dtable, int32_t B, int32_t T, int32_t C,
-                      int32_t n_rows, float scale, int32_t padding_idx, void *stream);
-/* denc[b][c][mel2ph[b][t]-1] += dout[b][c][t] */
-int set_expand_states_bwd(const int64_t *mel2ph, const float *dout, float *denc, int32_t B, int32_t C, int32_t T_txt,
-                          int32_t T, void *stream);
 /* inverted dropout with a Philox keep-mask keyed by (seed, offset + i/4): y = keep ? x/(1-p) : 0.  Calling it on the
  * output gradient with the same (seed, offset) is the backward (nar_tts_modules.py:20,86 predictor dropout). */
 int set_dropout(const float *x, float *y, int64_t n, float p, uint64_t seed, uint64_t offset, void *stream);
@@ -726,8 +721,6 @@ int set_stutter_head_loss_bwd(const float *h, const float *w, const float *logit
 int set_stutter_head_bwd_reduce(const float *scratch, float *dw, float *db, int32_t B, int32_t C, int32_t T, void *stream);
 /* w[f] = (sum_m |target[f][m]|) != 0    (weights_nonzero_speech, utils/nn/seq_utils.py:33-37) */
 int set_frame_weight(const float *target, float *w, int64_t frames, int32_t M, void *stream);
-/* out[0] += sum_i x[i] * (w ? w[i/inner] : 1) */
-int set_weighted_sum(const float *x, const float *w, float *out, int64_t n, int64_t inner, void *stream);
 /* absd = |pred - target|, sgn = sign(pred - target)  (either may be NULL)   (l1_loss, speech_base.py:223-229) */
 int set_l1_elem(const float *pred, const float *target, float *absd, float *sgn, int64_t n, void *stream);
 /* out[i] = a[i] * (w ? w[i/inner] : 1) * (scale_dev ? scale_dev[0] : 1) * scale */
@@ -743,29 +736,19 @@ int set_ssim_map(const float *mu1, const float *mu2, const float *s11, const flo
                  float *one_minus, float *d_mu1, float *d_s11, float *d_s12, int64_t n, void *stream);
 int set_ssim_bwd(const float *img1, const float *img2, float bias, const float *gm, const float *g11, const float *g12,
                  float *dimg1, int32_t B, int32_t H, int32_t W, void *stream);
-/* duration losses (speech_editing_base.py:58-90).  Pass 1 (ddur NULL): sums[0..3] += {sum nonpad*d^2, sum nonpad,
- * sum wordmask*dw^2, sum wordmask}.  Pass 2 (ddur set): ddur = gscale * d(lam_p*s0/s1 + lam_w*s2/s3)/d dur_pred. */
-int set_dur_loss(const float *dur_pred, const int64_t *mel2ph, const int64_t *txt, const int64_t *word_id, float *sums,
-                 const float *final_sums, float *ddur, int32_t B, int32_t T, int32_t T_txt, int32_t n_words,
-                 float lam_p, float lam_w, float gscale, void *stream);
-/* pitch losses (speech_editing_base.py:92-108) on channel-major pitch_pred [B][2][T] (row 0 f0, row 1 uv logit).
- * Pass 1: sums += {sum nonpad*bce, sum nonpad, sum nv*|df0|, sum nv};  pass 2: dpp = gradient. */
-int set_pitch_loss(const float *pp, const float *f0, const float *uv, const int64_t *mel2ph, float *sums,
-                   const float *final_sums, float *dpp, int32_t B, int32_t T, float lam_uv, float lam_f0, float gscale,
-                   void *stream);
-/* out[0] += sum g[i]^2 */
-int set_sumsq(const float *g, float *out, int64_t n, void *stream);
+/* Gradients of the duration and pitch losses.  `final_sums` (required): the four sums of set_dur_loss_sums_det /
+ * set_pitch_loss_sums_det.  ddur = gscale * d(lam_p*s0/s1 + lam_w*s2/s3)/d dur_pred;  dpp [B][2][T] = gscale * d(lam_f0*s2/s3 +
+ * lam_uv*s0/s1)/d pitch_pred. */
+int set_dur_loss(const float *dur_pred, const int64_t *mel2ph, const int64_t *txt, const int64_t *word_id,
+                 const float *final_sums, float *ddur, int32_t B, int32_t T, int32_t T_txt, int32_t n_words, float lam_p,
+                 float lam_w, float gscale, void *stream);
+int set_pitch_loss(const float *pp, const float *f0, const float *uv, const int64_t *mel2ph, const float *final_sums,
+                   float *dpp, int32_t B, int32_t T, float lam_uv, float lam_f0, float gscale, void *stream);
 /* torch.optim.AdamW step (speech_base.py:163-170) over flat buffers on the gradient g*grad_scale (grad_scale =
  * 1/world after a SUM all-reduce), with clip_grad_norm_ folded in (base_task.py:129-133): the gradient is further
  * scaled by min(1, max_norm / (sqrt(sumsq[0])*grad_scale + 1e-6)) when sumsq != NULL (sumsq = sum g^2). */
 int set_adamw(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2, float eps,
               float weight_decay, int32_t step, const float *sumsq, float max_norm, float grad_scale, void *stream);
-/* The same update with lr and the bias corrections 1 - beta^step read from device memory hyper = [lr, bc1, bc2] (a captured training
- * step is replayed for every update: its kernel arguments are frozen).  set_adamw_hyper computes bc1, bc2 on the host exactly as
- * set_adamw does (out2[0], out2[1]). */
-int set_adamw_hyper(float beta1, float beta2, int32_t step, float *out2);
-int set_adamw_dev(float *p, const float *g, float *m, float *v, int64_t n, const float *hyper, float beta1, float beta2, float eps,
-                  float weight_decay, const float *sumsq, float max_norm, float grad_scale, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Attention building blocks (CampNet rows; modules/speech_editing/commons/transformer.py)

@@ -303,12 +303,10 @@ SIGNATURES = {
     "set_partial_rows_sum": (C.c_int, [_V, _V, _I32, _I32, _I32, _I32, _F, _V]),
     "set_step_proj_fwd": (C.c_int, [_V, _V, _I64, _V, _I64, _V, _I32, _I32, _I32, _V]),
     "set_step_proj_bwd_scratch_floats": (_I64, [_I32, _I32, _I32]),
-    "set_step_proj_bwd": (C.c_int, [_V, _V, _V, _I64, _V, _V, _I64, _V, _I64, _V, _I32, _I32, _I32, _V]),
     "set_step_proj_bwd_dh": (C.c_int, [_V, _V, _I64, _V, _V, _I32, _I32, _I32, _V]),
     "set_step_proj_bwd_dw": (C.c_int, [_V, _V, _V, _I64, _V, _I64, _I32, _I32, _I32, _V]),
     "set_diffnet_layer_bwd_reduce": (C.c_int, [_V, _V, _V, _I32, _I32, _V, _V, _V, _V, _I64, _V]),
     "set_diffnet_layers_bwd_reduce": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _V, _I64, _V, _I64, _V, _I64, _V, _I64, _I64, _V]),
-    "set_channel_sum": (C.c_int, [_V, _V, _I32, _I32, _I32, _V]),
     "set_row_sum": (C.c_int, [_V, _V, _I64, _I32, _F, _V]),
     "set_conv_epilogue_bwd": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _I32, _F, _V]),
     "set_act_fwd": (C.c_int, [_V, _V, _I64, _I32, _F, _V]),
@@ -319,8 +317,6 @@ SIGNATURES = {
     "set_layernorm_ch_bwd": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _F, _V]),
     "set_layernorm_ch_bwd_add": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _F, _V]),
     "set_layernorm_ch_bwd_scratch": (C.c_int64, [_I32, _I32, _I32]),
-    "set_embedding_bwd": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _I32, _F, _I32, _V]),
-    "set_expand_states_bwd": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _I32, _V]),
     "set_dropout": (C.c_int, [_V, _V, _I64, _F, _U64, _U64, _V]),
     "set_residual_dropout": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _F, _U64, _U64, _V]),
     "set_conv_epilogue_bwd_dropout": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _F, _U64, _U64, _V]),
@@ -329,18 +325,14 @@ SIGNATURES = {
     "set_stutter_head_loss_bwd": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _V]),
     "set_stutter_head_bwd_reduce": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _V]),
     "set_frame_weight": (C.c_int, [_V, _V, _I64, _I32, _V]),
-    "set_weighted_sum": (C.c_int, [_V, _V, _V, _I64, _I64, _V]),
     "set_l1_elem": (C.c_int, [_V, _V, _V, _V, _I64, _V]),
     "set_scale_bcast": (C.c_int, [_V, _V, _V, _I64, _I64, _V, _F, _V]),
     "set_ssim_filter": (C.c_int, [_V, _V, _F, _V, _V, _V, _V, _V, _I32, _I32, _I32, _V]),
     "set_ssim_map": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _I64, _V]),
     "set_ssim_bwd": (C.c_int, [_V, _V, _F, _V, _V, _V, _V, _I32, _I32, _I32, _V]),
-    "set_dur_loss": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _F, _F, _F, _V]),
-    "set_pitch_loss": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _I32, _I32, _F, _F, _F, _V]),
-    "set_sumsq": (C.c_int, [_V, _V, _I64, _V]),
+    "set_dur_loss": (C.c_int, [_V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _F, _F, _F, _V]),
+    "set_pitch_loss": (C.c_int, [_V, _V, _V, _V, _V, _V, _I32, _I32, _F, _F, _F, _V]),
     "set_adamw": (C.c_int, [_V, _V, _V, _V, _I64, _F, _F, _F, _F, _F, _I32, _V, _F, _F, _V]),
-    "set_adamw_hyper": (C.c_int, [_F, _F, _I32, C.POINTER(C.c_float)]),
-    "set_adamw_dev": (C.c_int, [_V, _V, _V, _V, _I64, _V, _F, _F, _F, _F, _V, _F, _F, _V]),
     "set_sizeof_conv1d_args": (_I64, []),
     "set_sizeof_diffnet_layer_args": (_I64, []),
     "set_sizeof_diff_loop_args": (_I64, []),

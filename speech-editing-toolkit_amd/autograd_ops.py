@@ -6,13 +6,14 @@ from ops.py unchanged.
 """
 import collections
 import ctypes as C
+import functools
 import os
 
 import torch
 
 from . import _lib, ops
 from ._lib import SetAmdError  # noqa: E402
-from ._lib import ACT, PRO, IMPL_MFMA, IMPL_NAIVE, check
+from ._lib import ACT, PRO, IMPL_NAIVE, check
 from .ops import _p, _stream, _uniform_stride, ConvWeight
 
 # no-gradient ops: identical to the inference path
@@ -303,11 +304,8 @@ def _tape_tgt(param, dev, cw=None):
     return tmp, tmp
 
 
-def _wgrad_impl(T):
-    return IMPL_MFMA if T >= 16 else IMPL_NAIVE
-
-
 _DET_SCRATCH = {}  # (device, stream) -> per-block / per-slice partial results of the ordered reductions (reused: stream-ordered)
+_WG_SCRATCH = {}  # (device, stream) -> slice-partial buffer of the ordered weight-gradient path (reused: stream-ordered)
 
 
 def _stream_key(device):
@@ -323,26 +321,20 @@ def _leaf_keep(buf):
                 _leaf_hold(st, buf)
 
 
-def _det_scratch(device, n_floats):
+def _scratch(pool, slack, device, n_floats):
+    """The current stream's buffer of `pool`, regrown (x 1.25 + slack) when it is smaller than n_floats."""
     key = _stream_key(device)
-    buf = _DET_SCRATCH.get(key)
+    buf = pool.get(key)
     if buf is None or buf.numel() < n_floats:
         if buf is not None:
             _leaf_keep(buf)
-        buf = torch.empty(int(n_floats * 1.25) + 4096, dtype=torch.float32, device=device)
-        _DET_SCRATCH[key] = buf
+        buf = torch.empty(int(n_floats * 1.25) + slack, dtype=torch.float32, device=device)
+        pool[key] = buf
     return buf
 
 
-def _wg_scratch(device, need):
-    key = _stream_key(device)
-    buf = _WG_SCRATCH.get(key)
-    if buf is None or buf.numel() < need:
-        if buf is not None:
-            _leaf_keep(buf)
-        buf = torch.empty(int(need * 1.25) + 1024, dtype=torch.float32, device=device)
-        _WG_SCRATCH[key] = buf
-    return buf
+_det_scratch = functools.partial(_scratch, _DET_SCRATCH, 4096)  # (device, n_floats)
+_wg_scratch = functools.partial(_scratch, _WG_SCRATCH, 1024)
 
 
 def channel_sum_(x, out, B, Cc, T):
@@ -350,18 +342,14 @@ def channel_sum_(x, out, B, Cc, T):
     check(L().set_channel_sum_det(_p(x), _p(out), B, Cc, T, _p(_det_scratch(x.device, 2048 + Cc)), _stream()), "set_channel_sum_det")
 
 
-_WG_SCRATCH = {}  # (device, stream) -> slice-partial buffer of the deterministic weight-gradient path (reused: stream-ordered)
-DETERMINISTIC_WGRAD = True  # False: the round-1 split-K kernel with fp32 atomics (order-dependent bits)
-
-
 def conv_wgrad(g, x, chan_add, dw, B, Cin, Cout, K, dil, pad, T, T_in, pro=0, pro_param=0.0, dw_ptr=None, dtype=None):
     """dW[co][ci][tap] += sum_{b,t} G[b][co][t] * P(X[b][ci][t + tap*dil - pad] + chan_add[b][ci]).  MFMA shapes go
     through set_conv1d_wgrad_det (per-slice partial sums reduced in slice order: bit-stable, no atomics) with bf16 or
     fp32 operands according to ops.compute_dtype(); tiny T uses the one-thread-per-weight kernel."""
     ptr = C.c_void_p(dw.data_ptr() if dw_ptr is None else dw_ptr)
-    if T < 16 or not DETERMINISTIC_WGRAD:
+    if T < 16:
         check(L().set_conv1d_wgrad(_p(g), _p(x), _p(chan_add), ptr, B, Cin, Cout, K, dil, pad, T, T_in, pro,
-                                   float(pro_param), _wgrad_impl(T), _stream()), "set_conv1d_wgrad")
+                                   float(pro_param), IMPL_NAIVE, _stream()), "set_conv1d_wgrad")
         return
     if dtype is not None:
         dt = dtype  # bf16 operands already in HBM (fused layer kernels)
@@ -949,7 +937,6 @@ class _DiffNetStackFn(torch.autograd.Function):
         dd = torch.empty(B, L_ * C_, dtype=torch.float32, device=dev)
         dx = _gzeros((B, C_, T), dev)  # the last layer's x output feeds nothing
         grads = []
-        impl_w = _wgrad_impl(T)
         for l in range(L_ - 1, -1, -1):
             layer = layers[l]
             dil = layer.dilation
@@ -1669,7 +1656,7 @@ class _DurLossFn(torch.autograd.Function):
         d = torch.empty_like(dur_pred)
         out = None
         for lam_a, lam_b, gg in ((lam_p, 0.0, gp), (0.0, lam_w, gw)):
-            check(L().set_dur_loss(_p(dur_pred), _p(mel2ph), _p(txt), _p(word_id), None, _p(sums), _p(d), B, mel2ph.shape[1],
+            check(L().set_dur_loss(_p(dur_pred), _p(mel2ph), _p(txt), _p(word_id), _p(sums), _p(d), B, mel2ph.shape[1],
                                    T_txt, n_words, float(lam_a), float(lam_b), 1.0, _stream()), "set_dur_loss")
             term = torch.empty_like(d)
             check(L().set_scale_bcast(_p(d), None, _p(term), d.numel(), 1, _p(gg.reshape(1).contiguous()), 1.0, _stream()),
@@ -1703,7 +1690,7 @@ class _PitchLossFn(torch.autograd.Function):
         lam_uv, lam_f0 = ctx.cfg
         B, _, T = pp.shape
         d = torch.empty_like(pp)
-        check(L().set_pitch_loss(_p(pp), _p(f0), _p(uv), _p(mel2ph), None, _p(sums), _p(d), B, T, float(lam_uv),
+        check(L().set_pitch_loss(_p(pp), _p(f0), _p(uv), _p(mel2ph), _p(sums), _p(d), B, T, float(lam_uv),
                                  float(lam_f0), 1.0, _stream()), "set_pitch_loss")
         # rows carry independent upstream gradients: row 0 (f0) * g_f0, row 1 (uv) * g_uv
         gsc = torch.stack([g_f0.reshape(()), g_uv.reshape(())]).reshape(1, 2, 1).expand(B, 2, 1).contiguous().reshape(-1)

@@ -164,9 +164,9 @@ __global__ void __launch_bounds__(256) conv1d_wgrad_naive_kernel(WgradArgs a) {
     a.dw[idx] += s;
 }
 
-// out[c] += sum_{b,t} x[b][c][t]  (bias grads): grid (C, slices over the batch), wave-shuffle + LDS reduce, one atomic per
-// block.  (One block per channel left C <= 512 blocks to stream 50 MB: 27 us at B=32, T=800.)
-__global__ void __launch_bounds__(256) channel_sum_kernel(const float *x, float *out, int B, int C, int T, float *part = nullptr) {
+// part[slice][c] = sum_{b in slice,t} x[b][c][t]  (bias grads): grid (C, slices over the batch), wave-shuffle + LDS reduce, one
+// partial per block.  (One block per channel left C <= 512 blocks to stream 50 MB: 27 us at B=32, T=800.)
+__global__ void __launch_bounds__(256) channel_sum_kernel(const float *x, int B, int C, int T, float *part) {
     __shared__ float red[4];
     const int c = blockIdx.x;
     float s = 0.0f;
@@ -177,10 +177,7 @@ __global__ void __launch_bounds__(256) channel_sum_kernel(const float *x, float 
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const float v = red[0] + red[1] + red[2] + red[3];
-        if (part) part[(int64_t)blockIdx.y * C + c] = v; else atomicAdd(&out[c], v);
-    }
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * C + c] = red[0] + red[1] + red[2] + red[3];
 }
 // out[b][c] = sum_t x[b][c][t] (* 1/div); one wave per (b,c)
 __global__ void __launch_bounds__(256) row_sum_kernel(const float *x, float *out, int64_t rows, int T, float scale) {
@@ -360,10 +357,9 @@ __global__ void __launch_bounds__(256) res_skip_bwd_vec4_kernel(const float *dx_
 // ---- LayerNorm over channels, backward: block = 32 frames x 8 channel groups (as the forward kernel), column sums
 //      through LDS; x and dy of the thread's <= 32 channels are fetched once as two batches and stay in registers for
 //      all four passes (C <= 256; wider inputs re-read).  dgamma/dbeta: reduce over the 32 frames of the group inside
-//      the wave, then one row of per-block partial sums (`partial[blk][2][C]`, reduced by lnb_partial_sum_kernel) --
-//      or, without scratch, one atomic per (block, channel): every block hits the same 2C addresses, and same-address
-//      device-scope atomics from different XCDs serialise at ~0.7 us each (measured: 416 blocks -> 280 us for 80 MB
-//      of traffic), hence the scratch path.
+//      the wave, then one row of per-block partial sums (`partial[blk][2][C]`, reduced by lnb_partial_sum_kernel).
+//      (One atomic per (block, channel) instead: every block hits the same 2C addresses, and same-address device-scope
+//      atomics from different XCDs serialise at ~0.7 us each -- measured: 416 blocks -> 280 us for 80 MB of traffic.)
 // Three block shapes (template FT frames x CG channel groups, RC channels per thread in registers): 32 x 8 (C > 256), 16 x 16 in 256 threads
 // and 32 x 16 in 512 threads (C <= 256; the launch function picks by grid size).  Round 5: the 16-group shapes (twice the blocks of the
 // 32 x 8 one, which left CampNet's B = 16, T = 800 at 400 blocks = two rounds on 256 CUs), the residual gradient `add` fetched with x and dy
@@ -381,32 +377,26 @@ __device__ __forceinline__ float lnb_block_sum(float v, float (*red)[FT], int cg
     return s;
 }
 template <int FT>
-__device__ __forceinline__ void lnb_emit(float dg, float db, int c, int tl, float *dgamma, float *dbeta, float *partial,
-                                         int C) {
+__device__ __forceinline__ void lnb_emit(float dg, float db, int c, int tl, float *partial, int C) {
     // sum over the FT frames of this channel group (FT consecutive lanes: xor offsets stay inside the group)
 #pragma unroll
     for (int off = FT / 2; off > 0; off >>= 1) { dg += __shfl_xor(dg, off); db += __shfl_xor(db, off); }
     if (tl == 0) {
-        if (partial) {
-            float *row = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * C;
-            row[c] = dg;
-            row[C + c] = db;
-        } else {
-            atomicAdd(&dgamma[c], dg);
-            atomicAdd(&dbeta[c], db);
-        }
+        partial[c] = dg;
+        partial[C + c] = db;
     }
 }
 
 // add != NULL: dx = (LayerNorm gradient) + add -- the residual branch of a pre-LN sub-block joins here instead of in a separate launch
 template <int FT, int CG, int RC>
 __global__ void __launch_bounds__(FT * CG) layernorm_ch_bwd_kernel(const float *x, const float *gamma, const float *mask,
-                                                               const float *dy, float *dx, float *dgamma, float *dbeta,
-                                                               float *partial, int B, int C, int T, float eps, const float *add) {
+                                                               const float *dy, float *dx, float *partial, int B, int C, int T,
+                                                               float eps, const float *add) {
     static_assert(FT * CG == 256 || FT * CG == 512, "one thread per (frame, channel group)");
     __shared__ float red[CG][FT];
     const int tl = threadIdx.x % FT, cg = threadIdx.x / FT;
     const int b = blockIdx.y, t = blockIdx.x * FT + tl;
+    partial += ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 2 * C;
     const bool valid = t < T;
     const int tc = valid ? t : T - 1;
     const int cq = (C + CG - 1) / CG, c0 = cg * cq, c1 = min(C, c0 + cq);
@@ -463,7 +453,7 @@ __global__ void __launch_bounds__(FT * CG) layernorm_ch_bwd_kernel(const float *
                 if constexpr (PREF) o = add ? gx + av[i] : gx;
                 else o = add ? gx + buf_load(radd, valid ? vb : BUF_OOB, (unsigned)i * T4) : gx;
                 buf_store(o, rdx, valid ? vb : BUF_OOB, (unsigned)i * T4);  // frames beyond T: offset out of range, dropped
-                lnb_emit<FT>(gv[i] * xv[i], gv[i], c0 + i, tl, dgamma, dbeta, partial, C);
+                lnb_emit<FT>(gv[i] * xv[i], gv[i], c0 + i, tl, partial, C);
             }
         }
         return;
@@ -490,7 +480,7 @@ __global__ void __launch_bounds__(FT * CG) layernorm_ch_bwd_kernel(const float *
             const float gx = rstd * (dyc * gamma[c] - s1 - xh * s2);
             op[(int64_t)c * T] = ap ? gx + ap[(int64_t)c * T] : gx;
         }
-        lnb_emit<FT>(dyc * xh, dyc, c, tl, dgamma, dbeta, partial, C);
+        lnb_emit<FT>(dyc * xh, dyc, c, tl, partial, C);
     }
 }
 // out[j] += sum_r partial[r][j], j < n (= 2C: dgamma then dbeta); block = 64 columns x ROWS_RG row groups (rows_sum.h)
@@ -504,42 +494,6 @@ __global__ void __launch_bounds__(64 * ROWS_RG) lnb_partial_sum_kernel(const flo
     if (rg == 0 && j < n) {
         if (j < C) dgamma[j] += s; else dbeta[j - C] += s;
     }
-}
-
-// ---- embedding / alignment gather backward (scatter-add) ------------------------------------------------------
-// one thread per (b, c) walks t and flushes one atomic per RUN of equal indices: masked regions / sorted alignments
-// map long stretches of frames to one row (e.g. every masked frame -> pitch bin 1), which serialises per-frame atomics.
-// (Tried: one wave per (b, c, 64-frame segment) with a segmented scan -- coalesced and 13x more parallel, but the frame-
-// level pitch bins give one run per frame, and 5 M atomics issued at once on 58 k addresses cost 2.7 ms more per step
-// than this slow walk, which spreads them out.  The way forward is an LDS-privatised table per block, not more threads.)
-__global__ void __launch_bounds__(256) embedding_bwd_kernel(const int64_t *idx, const float *dout, float *dtable, int B,
-                                                            int T, int C, int n_rows, float scale, int padding_idx) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * C) return;
-    const int c = (int)(i % C), b = (int)(i / C);
-    const int64_t *ib = idx + (int64_t)b * T;
-    const float *dp = dout + ((int64_t)b * C + c) * T;
-    int64_t cur = -1;
-    float acc = 0.0f;
-    for (int t = 0; t < T; ++t) {
-        int64_t row = ib[t];
-        row = row < 0 ? 0 : (row >= n_rows ? n_rows - 1 : row);
-        if (row != cur) {
-            if (cur >= 0 && cur != padding_idx) atomicAdd(&dtable[cur * C + c], acc);
-            cur = row;
-            acc = 0.0f;
-        }
-        acc = fmaf(scale, dp[t], acc);
-    }
-    if (cur >= 0 && cur != padding_idx) atomicAdd(&dtable[cur * C + c], acc);  // nn.Embedding(padding_idx) row stays 0
-}
-__global__ void __launch_bounds__(256) expand_states_bwd_kernel(const int64_t *mel2ph, const float *dout, float *denc,
-                                                                int B, int C, int T_txt, int T) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * C * T) return;
-    const int t = (int)(i % T), c = (int)((i / T) % C), b = (int)(i / ((int64_t)T * C));
-    const int64_t m = mel2ph[(int64_t)b * T + t];
-    if (m > 0 && m <= T_txt) atomicAdd(&denc[((int64_t)b * C + c) * T_txt + (m - 1)], dout[i]);
 }
 
 // ---- dropout: keep mask from Philox(seed, offset + i/4); same kernel for forward and backward ------------------
@@ -624,9 +578,8 @@ __global__ void __launch_bounds__(256) frame_weight_kernel(const float *target, 
     for (int m = 0; m < M; ++m) s += fabsf(target[i * M + m]);
     w[i] = s != 0.0f ? 1.0f : 0.0f;
 }
-// sum-reduce helper: out[0] += sum x[i] (* w[i / inner])
-__global__ void __launch_bounds__(256) weighted_sum_kernel(const float *x, const float *w, float *out, int64_t n,
-                                                           int64_t inner, float *part = nullptr) {
+// sum-reduce helper: part[block] = the block's share of sum x[i] (* w[i / inner])
+__global__ void __launch_bounds__(256) weighted_sum_kernel(const float *x, const float *w, int64_t n, int64_t inner, float *part) {
     __shared__ float red[256];
     float s = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
@@ -637,7 +590,7 @@ __global__ void __launch_bounds__(256) weighted_sum_kernel(const float *x, const
         if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
         __syncthreads();
     }
-    if (threadIdx.x == 0) { if (part) part[blockIdx.x] = red[0]; else atomicAdd(out, red[0]); }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
 // |pred - target| (forward) / sign(pred - target) (backward), [n]
 __global__ void __launch_bounds__(256) l1_elem_kernel(const float *pred, const float *target, float *absd, float *sgn,
@@ -759,12 +712,13 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(const float *img1, const 
 }
 
 // duration losses (speech_editing_base.py:58-90): one block per utterance.
-// out[0] += sum_j nonpad (log(dp+1) - log(dg+1))^2 ; out[1] += sum nonpad ; out[2] += sum_w wmask (..)^2 ; out[3] += sum wmask
-// ddur (optional): gradient of  lam_p * out0/out1 + lam_w * out2/out3  given the FINAL sums in `sums` (second pass).
+// ddur == NULL (first pass): part[b][0] = sum_j nonpad (log(dp+1) - log(dg+1))^2 ; part[b][1] = sum nonpad ;
+// part[b][2] = sum_w wmask (..)^2 ; part[b][3] = sum wmask  over utterance b (the caller adds the rows in order: out0 .. out3).
+// ddur != NULL (second pass): gradient of  lam_p * out0/out1 + lam_w * out2/out3  given the FINAL sums in `final_sums`.
 __global__ void __launch_bounds__(256) dur_loss_kernel(const float *dur_pred, const int64_t *mel2ph, const int64_t *txt,
-                                                       const int64_t *word_id, float *sums, const float *final_sums,
-                                                       float *ddur, int T, int T_txt, int n_words, float lam_p,
-                                                       float lam_w, float gscale, float *part = nullptr) {
+                                                       const int64_t *word_id, const float *final_sums, float *ddur, int T,
+                                                       int T_txt, int n_words, float lam_p, float lam_w, float gscale,
+                                                       float *part) {
     extern __shared__ float sh[];  // dur_gt[T_txt+1] | wp[n_words+1] | wg[n_words+1]
     float *dg = sh, *wp = sh + (T_txt + 1), *wg = wp + (n_words + 1);
     const int b = blockIdx.x;
@@ -801,7 +755,7 @@ __global__ void __launch_bounds__(256) dur_loss_kernel(const float *dur_pred, co
             const float d = logf(wp[wi] + 1.0f) - logf(wg[wi] + 1.0f);
             s2 += d * d * wm; s3 += wm;
         }
-        // block sum in a fixed order, then one slot per utterance (part) or the order-dependent atomics
+        // block sum in a fixed order, then one slot per utterance
         __shared__ float red4[4][256];
         red4[0][threadIdx.x] = s0; red4[1][threadIdx.x] = s1; red4[2][threadIdx.x] = s2; red4[3][threadIdx.x] = s3;
         __syncthreads();
@@ -810,10 +764,7 @@ __global__ void __launch_bounds__(256) dur_loss_kernel(const float *dur_pred, co
                 for (int k = 0; k < 4; ++k) red4[k][threadIdx.x] += red4[k][threadIdx.x + st];
             __syncthreads();
         }
-        if (threadIdx.x < 4) {
-            if (part) part[(int64_t)b * 4 + threadIdx.x] = red4[threadIdx.x][0];
-            else atomicAdd(&sums[threadIdx.x], red4[threadIdx.x][0]);
-        }
+        if (threadIdx.x < 4) part[(int64_t)b * 4 + threadIdx.x] = red4[threadIdx.x][0];
     } else {
         for (int j = threadIdx.x; j < T_txt; j += 256) {
             const float np = txt[(int64_t)b * T_txt + j] != 0 ? 1.0f : 0.0f;
@@ -828,12 +779,12 @@ __global__ void __launch_bounds__(256) dur_loss_kernel(const float *dur_pred, co
 }
 
 // pitch losses (speech_editing_base.py:92-108) on channel-major pitch_pred [B][2][T]:
-// sums[0] += sum nonpad * bce(logit, uv) ; sums[1] += sum nonpad ; sums[2] += sum nv |f0p - f0| ; sums[3] += sum nv
-// second pass (dpp != NULL): dpp[b][0][t] = lam_f0 * nv * sign / sums[3] ; dpp[b][1][t] = lam_uv * nonpad * (sigmoid - uv) / sums[1]
+// first pass (dpp == NULL), per block blk: part[blk][0] = sum nonpad * bce(logit, uv) ; part[blk][1] = sum nonpad ;
+// part[blk][2] = sum nv |f0p - f0| ; part[blk][3] = sum nv  (the caller adds the rows in order: sums[0..3])
+// second pass (dpp != NULL): dpp[b][0][t] = lam_f0 * nv * sign / final_sums[3] ; dpp[b][1][t] = lam_uv * nonpad * (sigmoid - uv) / final_sums[1]
 __global__ void __launch_bounds__(256) pitch_loss_kernel(const float *pp, const float *f0, const float *uv,
-                                                         const int64_t *mel2ph, float *sums, const float *final_sums,
-                                                         float *dpp, int B, int T, float lam_uv, float lam_f0,
-                                                         float gscale, float *part = nullptr) {
+                                                         const int64_t *mel2ph, const float *final_sums, float *dpp, int B,
+                                                         int T, float lam_uv, float lam_f0, float gscale, float *part) {
     __shared__ float wsum[4][4];
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     float s0 = 0, s1 = 0, s2 = 0, s3 = 0;
@@ -859,18 +810,15 @@ __global__ void __launch_bounds__(256) pitch_loss_kernel(const float *pp, const 
         for (int off = 32; off > 0; off >>= 1) {
             s0 += __shfl_xor(s0, off); s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); s3 += __shfl_xor(s3, off);
         }
-        if (part) {  // one slot per block, waves combined in wave order
-            if ((threadIdx.x & 63) == 0) {
-                const int wv = threadIdx.x >> 6;
-                wsum[0][wv] = s0; wsum[1][wv] = s1; wsum[2][wv] = s2; wsum[3][wv] = s3;
-            }
-            __syncthreads();
-            if (threadIdx.x < 4)
-                part[(int64_t)blockIdx.x * 4 + threadIdx.x] =
-                    ((wsum[threadIdx.x][0] + wsum[threadIdx.x][1]) + wsum[threadIdx.x][2]) + wsum[threadIdx.x][3];
-        } else if ((threadIdx.x & 63) == 0) {
-            atomicAdd(&sums[0], s0); atomicAdd(&sums[1], s1); atomicAdd(&sums[2], s2); atomicAdd(&sums[3], s3);
+        // one slot per block, waves combined in wave order
+        if ((threadIdx.x & 63) == 0) {
+            const int wv = threadIdx.x >> 6;
+            wsum[0][wv] = s0; wsum[1][wv] = s1; wsum[2][wv] = s2; wsum[3][wv] = s3;
         }
+        __syncthreads();
+        if (threadIdx.x < 4)
+            part[(int64_t)blockIdx.x * 4 + threadIdx.x] =
+                ((wsum[threadIdx.x][0] + wsum[threadIdx.x][1]) + wsum[threadIdx.x][2]) + wsum[threadIdx.x][3];
     }
 }
 
@@ -950,8 +898,8 @@ __global__ void __launch_bounds__(256) scatter_reduce_kernel(const float *part, 
 }
 
 // ---- optimizer ---------------------------------------------------------------------------------------------------
-// sum of squares of a flat buffer -> out[0] (atomic)
-__global__ void __launch_bounds__(256) sumsq_kernel(const float *g, float *out, int64_t n, float *part = nullptr) {
+// sum of squares of a flat buffer: part[block] = the block's share
+__global__ void __launch_bounds__(256) sumsq_kernel(const float *g, int64_t n, float *part) {
     __shared__ float red[256];
     float s = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s = fmaf(g[i], g[i], s);
@@ -961,18 +909,15 @@ __global__ void __launch_bounds__(256) sumsq_kernel(const float *g, float *out, 
         if ((int)threadIdx.x < st) red[threadIdx.x] += red[threadIdx.x + st];
         __syncthreads();
     }
-    if (threadIdx.x == 0) { if (part) part[blockIdx.x] = red[0]; else atomicAdd(out, red[0]); }
+    if (threadIdx.x == 0) part[blockIdx.x] = red[0];
 }
 // AdamW (torch.optim.AdamW semantics, amsgrad off) over a flat buffer; grads are first scaled by
 // clip = min(1, max_norm / (sqrt(sumsq[0]) + 1e-6))  (torch.nn.utils.clip_grad_norm_), sumsq optional.
-// hyper != NULL (set_adamw_dev): lr and the two bias corrections come from device memory [lr, bc1, bc2] -- the step of a captured
-// graph, whose kernel arguments are frozen, reads the values of the update it is replayed for
 __global__ void __launch_bounds__(256) adamw_kernel(float *p, const float *g, float *m, float *v, int64_t n, float lr,
                                                     float beta1, float beta2, float eps, float wd, float bc1, float bc2,
-                                                    const float *sumsq, float max_norm, float grad_scale, const float *hyper) {
+                                                    const float *sumsq, float max_norm, float grad_scale) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2 = hyper[2]; }
     float clip = 1.0f;
     if (sumsq && max_norm > 0.0f) {
         const float c = max_norm / (sqrtf(sumsq[0]) * grad_scale + 1e-6f);
@@ -1145,14 +1090,6 @@ int launch_wgrad_f32_partial(const float *g, const float *x, const float *chan_a
     return set_check_launch("set_conv1d_wgrad_det(f32)");
 }
 
-extern "C" int set_channel_sum(const float *x, float *out, int32_t B, int32_t C, int32_t T, void *stream) {
-    SET_REQUIRE(x && out && B > 0 && C > 0 && T > 0, "set_channel_sum");
-    int slices = (2048 + C - 1) / C;  // ~2048 blocks in total
-    if (slices > B) slices = B;
-    if (slices < 1) slices = 1;
-    hipLaunchKernelGGL(channel_sum_kernel, dim3(C, slices), dim3(256), 0, (hipStream_t)stream, x, out, B, C, T);
-    return set_check_launch("set_channel_sum");
-}
 extern "C" int set_partial_rows_sum(const float *part, float *out, int32_t groups, int32_t rows, int32_t cols, int32_t accumulate,
                                     float scale, void *stream);  // diffnet_bf16.hip
 
@@ -1170,8 +1107,8 @@ extern "C" int set_step_proj_fwd(const float *h, const float *w, int64_t w_ls, c
 
 extern "C" int64_t set_step_proj_bwd_scratch_floats(int32_t L, int32_t C, int32_t N) { return (int64_t)L * (C / 64) * C * N; }
 
-// the two halves of set_step_proj_bwd as entry points of their own: the input gradient feeds the chain of backward kernels, the weight /
-// bias gradients are parameter gradients nothing reads before the optimizer -- the host side launches them on its second stream
+// the backward in two entry points: the input gradient feeds the chain of backward kernels, the weight / bias gradients are parameter
+// gradients nothing reads before the optimizer -- the host side launches them on its second stream
 extern "C" int set_step_proj_bwd_dh(const float *g, const float *w, int64_t w_ls, float *dh, float *scratch, int32_t L, int32_t C, int32_t N,
                                     void *stream) {
     SET_REQUIRE(g && w && dh && scratch && L > 0 && C > 0 && N > 0, "set_step_proj_bwd_dh");
@@ -1189,20 +1126,14 @@ extern "C" int set_step_proj_bwd_dw(const float *h, const float *g, float *dw, i
     else hipLaunchKernelGGL(step_proj_bwd_dw_kernel<64>, dim3(L, C / 16), dim3(256), 0, s, h, g, dw, dw_ls, db, db_ls, L, C, N);
     return set_check_launch("set_step_proj_bwd_dw");
 }
-extern "C" int set_step_proj_bwd(const float *h, const float *g, const float *w, int64_t w_ls, float *dh, float *dw, int64_t dw_ls,
-                                 float *db, int64_t db_ls, float *scratch, int32_t L, int32_t C, int32_t N, void *stream) {
-    SET_REQUIRE(h && g && w && dh && dw && db && scratch && L > 0 && C > 0 && N > 0, "set_step_proj_bwd");
-    const int rc = set_step_proj_bwd_dh(g, w, w_ls, dh, scratch, L, C, N, stream);
-    return rc ? rc : set_step_proj_bwd_dw(h, g, dw, dw_ls, db, db_ls, L, C, N, stream);
-}
 
-// Deterministic variants: per-block partial results in `scratch`, combined in block order by set_partial_rows_sum.
+// Reductions: per-block partial results in `scratch`, combined in block order by set_partial_rows_sum.
 extern "C" int set_channel_sum_det(const float *x, float *out, int32_t B, int32_t C, int32_t T, float *scratch, void *stream) {
     SET_REQUIRE(x && out && scratch && B > 0 && C > 0 && T > 0, "set_channel_sum_det");
     int slices = (2048 + C - 1) / C;
     if (slices > B) slices = B;
     if (slices < 1) slices = 1;  // scratch: slices * C <= 2048 + C floats
-    hipLaunchKernelGGL(channel_sum_kernel, dim3(C, slices), dim3(256), 0, (hipStream_t)stream, x, out, B, C, T, scratch);
+    hipLaunchKernelGGL(channel_sum_kernel, dim3(C, slices), dim3(256), 0, (hipStream_t)stream, x, B, C, T, scratch);
     const int rc = set_check_launch("set_channel_sum_det");
     return rc ? rc : set_partial_rows_sum(scratch, out, 1, slices, C, 1, 1.0f, stream);
 }
@@ -1211,7 +1142,7 @@ extern "C" int set_weighted_sum_det(const float *x, const float *w, float *out, 
     SET_REQUIRE(x && out && scratch && n > 0 && inner > 0, "set_weighted_sum_det");
     int64_t blocks = (n + 255) / 256;
     if (blocks > 1024) blocks = 1024;  // scratch: <= 1024 floats
-    hipLaunchKernelGGL(weighted_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, w, out, n, inner, scratch);
+    hipLaunchKernelGGL(weighted_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, w, n, inner, scratch);
     const int rc = set_check_launch("set_weighted_sum_det");
     return rc ? rc : set_partial_rows_sum(scratch, out, 1, (int)blocks, 1, 1, 1.0f, stream);
 }
@@ -1219,7 +1150,7 @@ extern "C" int set_sumsq_det(const float *g, float *out, int64_t n, float *scrat
     SET_REQUIRE(g && out && scratch && n > 0, "set_sumsq_det");
     int64_t blocks = (n + 255) / 256;
     if (blocks > 2048) blocks = 2048;  // scratch: <= 2048 floats
-    hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, out, n, scratch);
+    hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, n, scratch);
     const int rc = set_check_launch("set_sumsq_det");
     return rc ? rc : set_partial_rows_sum(scratch, out, 1, (int)blocks, 1, 1, 1.0f, stream);
 }
@@ -1231,7 +1162,7 @@ extern "C" int set_dur_loss_sums_det(const float *dur_pred, const int64_t *mel2p
                 "set_dur_loss_sums_det");
     const size_t lds = (size_t)(T_txt + 1 + 2 * (n_words + 1)) * sizeof(float);
     SET_REQUIRE(lds < 56000, "set_dur_loss_sums_det(T_txt too large)");
-    hipLaunchKernelGGL(dur_loss_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, dur_pred, mel2ph, txt, word_id, sums,
+    hipLaunchKernelGGL(dur_loss_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, dur_pred, mel2ph, txt, word_id,
                        (const float *)nullptr, (float *)nullptr, T, T_txt, n_words, 0.0f, 0.0f, 1.0f, scratch);
     const int rc = set_check_launch("set_dur_loss_sums_det");
     return rc ? rc : set_partial_rows_sum(scratch, sums, 1, B, 4, 1, 1.0f, stream);
@@ -1240,7 +1171,7 @@ extern "C" int set_pitch_loss_sums_det(const float *pp, const float *f0, const f
                                        int32_t B, int32_t T, float *scratch, void *stream) {
     SET_REQUIRE(pp && f0 && uv && mel2ph && sums && scratch && B > 0 && T > 0, "set_pitch_loss_sums_det");
     const unsigned nb = set_blocks((int64_t)B * T, 256);
-    hipLaunchKernelGGL(pitch_loss_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, pp, f0, uv, mel2ph, sums,
+    hipLaunchKernelGGL(pitch_loss_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, pp, f0, uv, mel2ph,
                        (const float *)nullptr, (float *)nullptr, B, T, 0.0f, 0.0f, 1.0f, scratch);
     const int rc = set_check_launch("set_pitch_loss_sums_det");
     return rc ? rc : set_partial_rows_sum(scratch, sums, 1, (int)nb, 4, 1, 1.0f, stream);
@@ -1361,7 +1292,7 @@ extern "C" int set_layernorm_ch_bwd_add(const float *x, const float *gamma, cons
 }
 static int layernorm_ch_bwd_launch(const float *x, const float *gamma, const float *mask, const float *dy, float *dx, float *dgamma,
                                    float *dbeta, float *partial, int32_t B, int32_t C, int32_t T, float eps, const float *add, void *stream) {
-    SET_REQUIRE(x && gamma && dy && dx && dgamma && dbeta && B > 0 && C > 0 && T > 0, "set_layernorm_ch_bwd");
+    SET_REQUIRE(x && gamma && dy && dx && dgamma && dbeta && partial && B > 0 && C > 0 && T > 0, "set_layernorm_ch_bwd");
     SET_REQUIRE(B <= 65535, "set_layernorm_ch_bwd(B)");
     SET_REQUIRE((int64_t)(C + 32) * T * 4 < ((int64_t)1 << 31), "set_layernorm_ch_bwd (one utterance exceeds the 2 GiB of a buffer offset)");
     // C <= 256: 16 channel groups (<= 16 channels per thread in registers).  32-frame tiles in 512-thread blocks (128-byte row segments, two
@@ -1377,34 +1308,18 @@ static int layernorm_ch_bwd_launch(const float *x, const float *gamma, const flo
     const int tiles = (groups16 && !big) ? (T + 15) / 16 : t32;
     if (big)
         hipLaunchKernelGGL((layernorm_ch_bwd_kernel<32, 16, 16>), dim3(tiles, B), dim3(512), 0, (hipStream_t)stream,
-                           x, gamma, mask, dy, dx, dgamma, dbeta, partial, B, C, T, eps, add);
+                           x, gamma, mask, dy, dx, partial, B, C, T, eps, add);
     else if (groups16)
         hipLaunchKernelGGL((layernorm_ch_bwd_kernel<16, 16, 16>), dim3(tiles, B), dim3(256), 0, (hipStream_t)stream,
-                           x, gamma, mask, dy, dx, dgamma, dbeta, partial, B, C, T, eps, add);
+                           x, gamma, mask, dy, dx, partial, B, C, T, eps, add);
     else
         hipLaunchKernelGGL((layernorm_ch_bwd_kernel<32, 8, 32>), dim3(tiles, B), dim3(256), 0, (hipStream_t)stream,
-                           x, gamma, mask, dy, dx, dgamma, dbeta, partial, B, C, T, eps, add);
-    if (partial) {
-        const int rc = set_check_launch("set_layernorm_ch_bwd");
-        if (rc) return rc;
-        hipLaunchKernelGGL(lnb_partial_sum_kernel, dim3((2 * C + 63) / 64), dim3(64 * ROWS_RG), 0, (hipStream_t)stream,
-                           partial, dgamma, dbeta, tiles * B, C);
-    }
+                           x, gamma, mask, dy, dx, partial, B, C, T, eps, add);
+    const int rc = set_check_launch("set_layernorm_ch_bwd");
+    if (rc) return rc;
+    hipLaunchKernelGGL(lnb_partial_sum_kernel, dim3((2 * C + 63) / 64), dim3(64 * ROWS_RG), 0, (hipStream_t)stream,
+                       partial, dgamma, dbeta, tiles * B, C);
     return set_check_launch("set_layernorm_ch_bwd");
-}
-extern "C" int set_embedding_bwd(const int64_t *idx, const float *dout, float *dtable, int32_t B, int32_t T, int32_t C,
-                                 int32_t n_rows, float scale, int32_t padding_idx, void *stream) {
-    SET_REQUIRE(idx && dout && dtable && B > 0 && T > 0 && C > 0 && n_rows > 0, "set_embedding_bwd");
-    hipLaunchKernelGGL(embedding_bwd_kernel, dim3(set_blocks((int64_t)B * C, 256)), dim3(256), 0, (hipStream_t)stream,
-                       idx, dout, dtable, B, T, C, n_rows, scale, padding_idx);
-    return set_check_launch("set_embedding_bwd");
-}
-extern "C" int set_expand_states_bwd(const int64_t *mel2ph, const float *dout, float *denc, int32_t B, int32_t C,
-                                     int32_t T_txt, int32_t T, void *stream) {
-    SET_REQUIRE(mel2ph && dout && denc && B > 0 && C > 0 && T_txt > 0 && T > 0, "set_expand_states_bwd");
-    hipLaunchKernelGGL(expand_states_bwd_kernel, dim3(set_blocks((int64_t)B * C * T, 256)), dim3(256), 0,
-                       (hipStream_t)stream, mel2ph, dout, denc, B, C, T_txt, T);
-    return set_check_launch("set_expand_states_bwd");
 }
 extern "C" int set_dropout(const float *x, float *y, int64_t n, float p, uint64_t seed, uint64_t offset, void *stream) {
     SET_REQUIRE(x && y && n > 0 && p >= 0.0f && p < 1.0f, "set_dropout");
@@ -1433,13 +1348,6 @@ extern "C" int set_frame_weight(const float *target, float *w, int64_t frames, i
     hipLaunchKernelGGL(frame_weight_kernel, dim3(set_blocks(frames, 256)), dim3(256), 0, (hipStream_t)stream, target, w,
                        frames, M);
     return set_check_launch("set_frame_weight");
-}
-extern "C" int set_weighted_sum(const float *x, const float *w, float *out, int64_t n, int64_t inner, void *stream) {
-    SET_REQUIRE(x && out && n > 0 && inner > 0, "set_weighted_sum");
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(weighted_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, w, out, n, inner);
-    return set_check_launch("set_weighted_sum");
 }
 extern "C" int set_l1_elem(const float *pred, const float *target, float *absd, float *sgn, int64_t n, void *stream) {
     SET_REQUIRE(pred && target && (absd || sgn) && n > 0, "set_l1_elem");
@@ -1492,32 +1400,23 @@ extern "C" int set_ssim_bwd(const float *img1, const float *img2, float bias, co
                        img2, gm, g11, g12, dimg1, B, H, W, bias);
     return set_check_launch("set_ssim_bwd");
 }
+// gradient passes of the two losses; `final_sums` holds the four sums of set_dur_loss_sums_det / set_pitch_loss_sums_det
 extern "C" int set_dur_loss(const float *dur_pred, const int64_t *mel2ph, const int64_t *txt, const int64_t *word_id,
-                            float *sums, const float *final_sums, float *ddur, int32_t B, int32_t T, int32_t T_txt,
-                            int32_t n_words, float lam_p, float lam_w, float gscale, void *stream) {
-    SET_REQUIRE(dur_pred && mel2ph && txt && word_id && B > 0 && T > 0 && T_txt > 0 && n_words >= 0, "set_dur_loss");
-    SET_REQUIRE((ddur && final_sums) || (!ddur && sums), "set_dur_loss");
+                            const float *final_sums, float *ddur, int32_t B, int32_t T, int32_t T_txt, int32_t n_words,
+                            float lam_p, float lam_w, float gscale, void *stream) {
+    SET_REQUIRE(dur_pred && mel2ph && txt && word_id && final_sums && ddur && B > 0 && T > 0 && T_txt > 0 && n_words >= 0, "set_dur_loss");
     const size_t lds = (size_t)(T_txt + 1 + 2 * (n_words + 1)) * sizeof(float);
     SET_REQUIRE(lds < 60000, "set_dur_loss(T_txt too large)");
-    hipLaunchKernelGGL(dur_loss_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, dur_pred, mel2ph, txt, word_id, sums,
-                       final_sums, ddur, T, T_txt, n_words, lam_p, lam_w, gscale);
+    hipLaunchKernelGGL(dur_loss_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, dur_pred, mel2ph, txt, word_id,
+                       final_sums, ddur, T, T_txt, n_words, lam_p, lam_w, gscale, (float *)nullptr);
     return set_check_launch("set_dur_loss");
 }
-extern "C" int set_pitch_loss(const float *pp, const float *f0, const float *uv, const int64_t *mel2ph, float *sums,
-                              const float *final_sums, float *dpp, int32_t B, int32_t T, float lam_uv, float lam_f0,
-                              float gscale, void *stream) {
-    SET_REQUIRE(pp && f0 && uv && mel2ph && B > 0 && T > 0, "set_pitch_loss");
-    SET_REQUIRE((dpp && final_sums) || (!dpp && sums), "set_pitch_loss");
+extern "C" int set_pitch_loss(const float *pp, const float *f0, const float *uv, const int64_t *mel2ph, const float *final_sums,
+                              float *dpp, int32_t B, int32_t T, float lam_uv, float lam_f0, float gscale, void *stream) {
+    SET_REQUIRE(pp && f0 && uv && mel2ph && final_sums && dpp && B > 0 && T > 0, "set_pitch_loss");
     hipLaunchKernelGGL(pitch_loss_kernel, dim3(set_blocks((int64_t)B * T, 256)), dim3(256), 0, (hipStream_t)stream, pp, f0,
-                       uv, mel2ph, sums, final_sums, dpp, B, T, lam_uv, lam_f0, gscale);
+                       uv, mel2ph, final_sums, dpp, B, T, lam_uv, lam_f0, gscale, (float *)nullptr);
     return set_check_launch("set_pitch_loss");
-}
-extern "C" int set_sumsq(const float *g, float *out, int64_t n, void *stream) {
-    SET_REQUIRE(g && out && n > 0, "set_sumsq");
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, out, n);
-    return set_check_launch("set_sumsq");
 }
 extern "C" int set_adamw(float *p, const float *g, float *m, float *v, int64_t n, float lr, float beta1, float beta2,
                          float eps, float weight_decay, int32_t step, const float *sumsq, float max_norm,
@@ -1525,19 +1424,6 @@ extern "C" int set_adamw(float *p, const float *g, float *m, float *v, int64_t n
     SET_REQUIRE(p && g && m && v && n > 0 && step >= 1, "set_adamw");
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
     hipLaunchKernelGGL(adamw_kernel, dim3(set_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1,
-                       beta2, eps, weight_decay, bc1, bc2, sumsq, max_norm, grad_scale, (const float *)nullptr);
+                       beta2, eps, weight_decay, bc1, bc2, sumsq, max_norm, grad_scale);
     return set_check_launch("set_adamw");
-}
-extern "C" int set_adamw_hyper(float beta1, float beta2, int32_t step, float *out2) {
-    SET_REQUIRE(out2 && step >= 1, "set_adamw_hyper");
-    out2[0] = 1.0f - powf(beta1, (float)step);  // exactly what set_adamw computes on the host
-    out2[1] = 1.0f - powf(beta2, (float)step);
-    return SET_OK;
-}
-extern "C" int set_adamw_dev(float *p, const float *g, float *m, float *v, int64_t n, const float *hyper, float beta1, float beta2,
-                             float eps, float weight_decay, const float *sumsq, float max_norm, float grad_scale, void *stream) {
-    SET_REQUIRE(p && g && m && v && n > 0 && hyper, "set_adamw_dev");
-    hipLaunchKernelGGL(adamw_kernel, dim3(set_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, 0.0f, beta1,
-                       beta2, eps, weight_decay, 1.0f, 1.0f, sumsq, max_norm, grad_scale, hyper);
-    return set_check_launch("set_adamw_dev");
 }

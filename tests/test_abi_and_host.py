@@ -24,7 +24,7 @@ def test_header_symbols_exported(built_lib):
     assert names == set(_lib.SIGNATURES), names ^ set(_lib.SIGNATURES)
     for n in names:
         assert hasattr(built_lib, n), n
-    assert built_lib.set_abi_version() == 2
+    assert built_lib.set_abi_version() == 3
 
 
 def test_struct_mirror_sizes(built_lib):
@@ -47,6 +47,24 @@ def test_error_codes_without_gpu(built_lib):
     assert built_lib.set_diffnet_layer(None, None) == _lib.E_INVALID
     assert built_lib.set_diffusion_loop(None, None) == _lib.E_INVALID
     assert built_lib.set_layernorm_ch(None, None, None, None, None, 1, 1, 1, C.c_float(1e-5), None) == _lib.E_INVALID
+
+
+def test_ordered_reductions_require_their_scratch_and_sums(built_lib):
+    """The training path has no atomic fallback: LayerNorm backward without `partial`, and the loss gradients without the final sums
+    of set_*_loss_sums_det, are refused with E_INVALID before any device call (the other arguments look valid: non-null, sizes > 0)."""
+    from set_amd import _lib
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p)
+    eps = C.c_float(1e-5)
+    assert built_lib.set_layernorm_ch_bwd(p, p, p, p, p, p, p, None, 1, 4, 8, eps, None) == _lib.E_INVALID
+    assert b"set_layernorm_ch_bwd" in built_lib.set_last_error()
+    assert built_lib.set_layernorm_ch_bwd_add(p, p, p, p, p, p, p, p, None, 1, 4, 8, eps, None) == _lib.E_INVALID
+    assert b"set_layernorm_ch_bwd" in built_lib.set_last_error()
+    one = C.c_float(1.0)
+    assert built_lib.set_dur_loss(p, p, p, p, None, p, 1, 8, 4, 2, one, one, one, None) == _lib.E_INVALID
+    assert b"set_dur_loss" in built_lib.set_last_error()
+    assert built_lib.set_pitch_loss(p, p, p, p, None, p, 1, 8, one, one, one, None) == _lib.E_INVALID
+    assert b"set_pitch_loss" in built_lib.set_last_error()
 
 
 def test_product_path_refuses_cpu(built_lib):
@@ -103,6 +121,43 @@ def test_dropped_experiment_switches_stay_out_of_csrc():
                 found[pat].append(fn)
     assert defined == ["stack_queue.h"], defined
     assert all(fns == ["stack_queue.h"] for fns in found.values()), found
+
+
+REMOVED_ENTRIES = ("set_channel_sum", "set_weighted_sum", "set_sumsq", "set_embedding_bwd", "set_expand_states_bwd", "set_adamw_dev",
+                   "set_adamw_hyper", "set_step_proj_bwd")
+
+
+def _strip_comments(src, python=False):
+    if python:
+        return re.sub(r"#[^\n]*", "", src)
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+
+
+def test_training_reductions_have_no_atomic_twin():
+    """csrc/train.hip keeps only the ordered form of every reduction: per-block partials in scratch, combined in a fixed order.  The two
+    kernels that still hold an atomicAdd are the split-K branch of the fp32 weight-gradient kernel (not on the training path) and the
+    integer-valued LDS frame counts of dur_loss_kernel (exact in any order).  No kernel has an optional pointer that selects another
+    path, and the retired entry points are named nowhere in the sources, the header or the package."""
+    pkg = os.path.join(ROOT, "speech-editing-toolkit_amd")
+    src = _strip_comments(open(os.path.join(pkg, "csrc", "train.hip")).read())
+    heads = list(re.finditer(r"__global__\s+void\s+(?:__launch_bounds__\([^)]*\)\s*)?(\w+)\s*\(([^)]*)\)\s*\{", src))
+    assert len(heads) == src.count("__global__") and len(heads) >= 30  # every kernel's signature was parsed
+    atomic = set()
+    for m, nxt in zip(heads, heads[1:] + [None]):
+        assert "nullptr" not in m.group(2), m.group(1)  # no defaulted pointer parameter
+        body = src[m.end():nxt.start() if nxt else len(src)]
+        if "atomicAdd" in body:
+            atomic.add(m.group(1))
+    assert atomic == {"conv1d_wgrad_mfma_kernel", "dur_loss_kernel"}, atomic
+    removed = re.compile(r"\b(%s)\b" % "|".join(REMOVED_ENTRIES))
+    files = [os.path.join(ROOT, "include", "set_amd.h")]
+    files += [os.path.join(pkg, "csrc", f) for f in sorted(os.listdir(os.path.join(pkg, "csrc"))) if f.endswith((".hip", ".h"))]
+    files += [os.path.join(pkg, f) for f in sorted(os.listdir(pkg)) if f.endswith(".py")]
+    for fn in files:
+        code = _strip_comments(open(fn).read(), python=fn.endswith(".py"))
+        assert not removed.search(code), (fn, removed.findall(code))
+    from set_amd import autograd_ops
+    assert not hasattr(autograd_ops, "DETERMINISTIC_WGRAD")
 
 
 INSTRUMENT_BUILDS = (("diffnet_x3.hip", "-DSET_X3_PROBE=1"), ("diffnet_x3.hip", "-DSET_X3_PROBE=2"), ("diffnet.hip", "-DSET_WINO_PHASES"),

@@ -77,22 +77,22 @@ def _rows_sum_depth(rows):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# LayerNorm over channels: backward (three block shapes, with / without `add`, with / without the partial-row scratch) and
+# LayerNorm over channels: backward (three block shapes, with / without `add`; the partial-row scratch is required) and
 # forward (register / loop path)
 # ------------------------------------------------------------------------------------------------------------------------
 LN_BWD = [
-    # B, C, T, add, partial
-    (3, 80, 70, False, True),     # 16x16 / 256 threads: C <= 256 && B * ceil(T/32) = 9 < 256
-    (3, 192, 70, True, True),     # 16x16 / 256 threads, `add` (pre-LN residual)
-    (2, 256, 45, True, False),    # 16x16 / 256 threads, C = 256 = 16 groups x RC 16 (cq <= RC), partial = NULL: per-block atomics
-    (16, 80, 509, False, True),   # 32x16 / 512 threads: C <= 256 && B * ceil(T/32) = 16 * 16 = 256 >= n_cu
-    (32, 192, 250, True, True),   # 32x16 / 512 threads: 32 * 8 = 256 >= n_cu, `add`
-    (32, 192, 250, False, False), # 32x16 / 512 threads, partial = NULL: atomics
-    (16, 256, 509, True, True),   # 32x16 / 512 threads at C = 256 (cq = 16 = RC)
-    (2, 257, 70, False, True),    # 32x8 loop: C > 256 -> 8 groups, cq = 33 > RC 32 (the register path of <32, 8, 32> never runs)
-    (3, 384, 45, True, True),     # 32x8 loop, `add`, cq = 48
-    (2, 384, 33, False, False),   # 32x8 loop, partial = NULL: atomics
-    (16, 384, 509, True, True),   # 32x8 loop at a grid that would take the 512-thread shape if C <= 256
+    # B, C, T, add
+    (3, 80, 70, False),     # 16x16 / 256 threads: C <= 256 && B * ceil(T/32) = 9 < 256
+    (3, 192, 70, True),     # 16x16 / 256 threads, `add` (pre-LN residual)
+    (2, 256, 45, True),     # 16x16 / 256 threads, C = 256 = 16 groups x RC 16 (cq <= RC)
+    (16, 80, 509, False),   # 32x16 / 512 threads: C <= 256 && B * ceil(T/32) = 16 * 16 = 256 >= n_cu
+    (32, 192, 250, True),   # 32x16 / 512 threads: 32 * 8 = 256 >= n_cu, `add`
+    (32, 192, 250, False),  # 32x16 / 512 threads without `add`
+    (16, 256, 509, True),   # 32x16 / 512 threads at C = 256 (cq = 16 = RC)
+    (2, 257, 70, False),    # 32x8 loop: C > 256 -> 8 groups, cq = 33 > RC 32 (the register path of <32, 8, 32> never runs)
+    (3, 384, 45, True),     # 32x8 loop, `add`, cq = 48
+    (2, 384, 33, False),    # 32x8 loop, one tile and a frame (T = 33)
+    (16, 384, 509, True),   # 32x8 loop at a grid that would take the 512-thread shape if C <= 256
 ]
 
 
@@ -122,7 +122,7 @@ def _ln_ref(x, gam, mask, dy, add, eps=1e-5):
 
 @pytest.mark.parametrize("case", LN_BWD)
 def test_layernorm_ch_bwd_every_block_shape(dev, case):
-    B, C, T, with_add, with_partial = case
+    B, C, T, with_add = case
     g = torch.Generator().manual_seed(B * 1000 + C + T)
     x = torch.randn(B, C, T, generator=g) * 2.0 + 0.5
     gam = torch.randn(C, generator=g) * 0.3 + 1.0
@@ -137,11 +137,9 @@ def test_layernorm_ch_bwd_every_block_shape(dev, case):
     dg, db = dg0.to(dev), db0.to(dev)
     L = _L()
     tiles = (T + 15) // 16 if (C <= 256 and B * ((T + 31) // 32) < 256) else (T + 31) // 32
-    part = None
-    if with_partial:
-        n_part = L.set_layernorm_ch_bwd_scratch(B, C, T)
-        assert n_part >= tiles * B * 2 * C
-        part = torch.full((n_part,), float("nan"), device=dev)  # every row the partial sum reads must have been written
+    n_part = L.set_layernorm_ch_bwd_scratch(B, C, T)
+    assert n_part >= tiles * B * 2 * C
+    part = torch.full((n_part,), float("nan"), device=dev)  # every row the partial sum reads must have been written
     if add is None:
         _check(L.set_layernorm_ch_bwd(_p(xd), _p(gd), _p(md), _p(dyd), _p(dx), _p(dg), _p(db), _p(part), B, C, T, 1e-5, _s()),
                "set_layernorm_ch_bwd")
@@ -151,12 +149,11 @@ def test_layernorm_ch_bwd_every_block_shape(dev, case):
     torch.cuda.synchronize()
     err = (dx.cpu().double() - dx_ref).abs()
     assert bool((err <= bdx + 1e-30).all()), (case, float((err / (bdx + 1e-30)).max()))
-    # dbeta: integer terms, every partial sum exact -> bit-equal to the float64 sum (also through the per-block atomics)
+    # dbeta: integer terms, every partial sum exact -> bit-equal to the float64 sum
     assert torch.equal(db.cpu().double(), db_ref + db0.double()), (case, float((db.cpu().double() - db_ref - db0.double()).abs().max()))
-    # dgamma: per-term error of x-hat (k u) plus a 5-level lane tree, the partial-row column sum (B * tiles rows) and the += ;
-    # with atomics the order varies but the depth is at most the number of blocks
+    # dgamma: per-term error of x-hat (k u) plus a 5-level lane tree, the partial-row column sum (B * tiles rows) and the +=
     rows = B * tiles
-    depth = k + 5 + (_rows_sum_depth(rows) if with_partial else rows) + 1
+    depth = k + 5 + _rows_sum_depth(rows) + 1
     bdg = _gamma(depth) * (dg_abs + dg0.double().abs()) + 1e-30
     derr = (dg.cpu().double() - dg_ref - dg0.double()).abs()
     assert bool((derr <= bdg).all()), (case, float((derr / bdg).max()))
