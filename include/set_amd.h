@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SET_AMD_ABI_VERSION 3
+#define SET_AMD_ABI_VERSION 4
 
 /* error codes */
 #define SET_OK 0
@@ -270,8 +270,9 @@ typedef struct SetDiffnetLayerArgs {
     float *skip;
     int64_t cp_bs, d_bs, d_cs;
     int32_t B, T, dil, first;
-    /* diagnostic, normally NULL: [gridDim.y*gridDim.x][8] uint64 s_memtime stamps written by wave 0 of every
-     * block at the phase boundaries (start, tile staged, GEMM1 done, gate done, z staged, GEMM2 done, end) */
+    /* diagnostic, NULL unless the library was built with -DSET_PHASE_PROBE=1 (SET_E_UNSUPPORTED otherwise):
+     * [gridDim.y*gridDim.x][8] uint64, wave 0 of every block ADDS the s_memtime ticks of its phases to words 0..5
+     * (tile staged, GEMM1, gate, barrier + z staged, GEMM2, epilogue) */
     uint64_t *dbg_clock;
 } SetDiffnetLayerArgs;
 int set_diffnet_layer(const SetDiffnetLayerArgs *args, void *stream);
@@ -555,19 +556,26 @@ int64_t set_sizeof_diffnet_layers_bf16_args(void);
 int64_t set_diffnet_layers_bf16_scratch_floats(int32_t B, int32_t T, int32_t l0, int32_t nl, int32_t dilation_cycle_length);
 int32_t set_diffnet_layers_bf16_plan(int32_t B, int32_t T, int32_t L, int32_t dilation_cycle_length);
 int set_diffnet_layers_fwd_bf16(const SetDiffnetLayersBf16Args *args, void *stream);
-/* debug: block (1,1) of the bf16 layer kernels stamps s_memtime at its phase boundaries into buf[0..7] (NULL = off) */
+/* Phase probes.  The shipped library holds no phase stamps: these setters return SET_OK for NULL and SET_E_UNSUPPORTED otherwise.  A
+ * library whose source file was built with -DSET_PHASE_PROBE=1 (tools/build_exp.sh) takes a device buffer of uint64 words; the sampled
+ * wave sums the s_memtime ticks (100 MHz) of its phases in registers and ADDS them to the buffer when the kernel ends (NULL = off).
+ * bf16: block (1,1), wave 0 of set_diffnet_layer_fwd_bf16 -> buf[0..4] = stage, GEMM 1, gate, GEMM 2, epilogue; of
+ * set_diffnet_layers_fwd_bf16, layers m >= 1 of the group -> buf[0..4] = init + barrier, GEMM 1, gate, GEMM 2, epilogue, layer count in
+ * buf[7], and the same of wave 4 in buf[8..15] */
 int set_debug_bf16_phase_buffer(uint64_t *buf);
-/* debug: lane 0 of one block (tile 1, part 1) of the row-split stack kernel ADDS the s_memtime ticks it spends in each of
- * its 8 phases (wait for the previous layer, stage, GEMM 1, gate + z publish, wait for z, z load, GEMM 2, epilogue +
- * publish), summed over the layers, to buf[0..7] (NULL = off) */
+/* wave 0 of one block (tile 1, part 1) of the fp32 row-split stack kernel, summed over the layers: buf[0..7] = wait for the previous
+ * layer, stage, GEMM 1, gate + z publish, wait for z, z load, GEMM 2, epilogue + publish */
 int set_debug_split_phase_buffer(uint64_t *buf);
-/* debug: lane 0 of block 0 of the split-operand stack kernel adds the s_memtime ticks of its phases (claim + wait, stage,
- * GEMM 1, gate, GEMM 2, epilogue + publish), summed over its tasks, to buf[0..5] and its task count to buf[7] */
+/* wave 0 of block 0 of the split-operand stack kernels, summed over its tasks: buf[0..5] = claim + wait, stage, GEMM 1, gate, GEMM 2,
+ * epilogue + publish, task count in buf[7], sub-phases in buf[8..12] (csrc/diffnet_x3.hip); the two-piece row-split kernel: the eight
+ * phases of set_debug_split_phase_buffer.  -DSET_PHASE_PROBE=2: rows of 32 dwords, the one-task timeline of tools/x3_timeline_probe.py */
 int set_debug_x3_phase_buffer(uint64_t *buf);
-/* debug: thread 0 of every 16th block of batch row 1 of the fused ResBlock-pair kernel adds the s_memtime ticks of its phases (x
- * chunk wait + split, GEMM 1 issue, GEMM 1 drain + epilogue 1, GEMM 2 issue, GEMM 2 drain + epilogue 2) to buf[0..4], block count
- * to buf[7] */
+/* wave 0 of every 16th block of batch row 1 of the fused ResBlock-pair kernel (atomic adds): buf[0..4] = x chunk wait + split, GEMM 1
+ * issue, GEMM 1 drain + epilogue 1, GEMM 2 issue, GEMM 2 drain + epilogue 2, block count in buf[7] */
 int set_debug_resblock_phase_buffer(uint64_t *buf);
+/* wave 0 of block (1,1,1) of the staged bf16 conv kernel: buf[0] = prologue, buf[1..5] = barrier 1, wait for the stage's loads + LDS
+ * writes, barrier 2, issue of the next stage's loads, fragment reads + MFMAs (summed over the stages), stage count in buf[6] */
+int set_debug_conv_phase_buffer(uint64_t *buf);
 
 typedef struct SetDiffnetLayerBf16BwdArgs {
     const float *dx_out; /* [B][256][T] gradient w.r.t. x_out; NULL = zero (the last layer's x_out feeds nothing) */

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "phase_probe.h"
 #include <type_traits>
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -186,26 +187,14 @@ __device__ __forceinline__ void conv_bf16_epilogue(const SetConv1dArgs &a, const
 // VEC (round 6): the input tile is loaded in 16-byte units (4 frames of one channel; a thread owns 4 frames x 4 channels per unit = 4
 // loads, four 8-byte LDS writes) instead of one frame per load (NPASS * KCH / 2 four-byte loads per thread and chunk): the same values
 // in the same LDS cells.  Host: T_in, the strides and Cin multiples of 4, 16-byte aligned bases, halo <= 16 (launch_conv_bf16).
-// measurement build only (tools/build_exp.sh convprobe bf16.hip -DSET_CONV_PROBE=1; tools/conv_phase_probe.py): per-stage phase times of one
-// block of conv1d_bf16_kernel (s_memtime, 100 MHz) summed in registers, written once at the end.  Not in the shipped library.
-#ifndef SET_CONV_PROBE
-#define SET_CONV_PROBE 0
-#endif
-#if SET_CONV_PROBE
-__device__ uint64_t *g_conv_phase_buf = nullptr;
-extern "C" int set_debug_conv_phase_buffer(uint64_t *buf) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_conv_phase_buf), &buf, sizeof(buf)) == hipSuccess ? 0 : 1;
-}
-#define CONV_PHASE(i) if (cprobe) { const uint64_t tn = __builtin_amdgcn_s_memtime(); cph[i] += tn - cprev; cprev = tn; }
-#else
-#define CONV_PHASE(i)
-#endif
+// probe builds (tools/build_exp.sh convprobe bf16.hip -DSET_PHASE_PROBE=1; tools/conv_phase_probe.py): wave 0 of block (1, 1, 1) of
+// conv1d_bf16_kernel sums the s_memtime ticks of its per-stage phases and adds them to buf[0..5] (0 prologue, 1 barrier 1, 2 wait for the
+// stage's loads + LDS writes, 3 barrier 2, 4 issue of the next stage's loads, 5 fragment reads + MFMAs), the stage count to buf[6]
+SET_PHASE_PROBE_BUFFER(g_conv_phase_buf, set_debug_conv_phase_buffer)
 template <int WM, int WN, int KCH, int TGM, bool HALO, bool ADD, bool VEC = false>
 __global__ void __launch_bounds__(256, 2) conv1d_bf16_kernel(SetConv1dArgs a, int lo, int halo, int CinP, int CoutP) {
-#if SET_CONV_PROBE
-    const bool cprobe = g_conv_phase_buf && blockIdx.x == 1 && blockIdx.y == 1 && blockIdx.z == 1 && threadIdx.x == 0;
-    uint64_t cph[6] = {0, 0, 0, 0, 0, 0}, cprev = __builtin_amdgcn_s_memtime();
-#endif
+    PhaseProbe<7> pp;
+    pp.start(g_conv_phase_buf && blockIdx.x == 1 && blockIdx.y == 1 && blockIdx.z == 1);
     static_assert(!VEC || KCH == 32, "16-byte input units: 32-channel stages");
     constexpr int BF_TG_MAX = TGM;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -370,11 +359,11 @@ __global__ void __launch_bounds__(256, 2) conv1d_bf16_kernel(SetConv1dArgs a, in
     stage_of(0, c0, tg0, tgn);
     issue_b(c0);
     issue_a(c0, tg0, tgn);
-    CONV_PHASE(0)  // prologue: first loads issued
+    pp.lap(0);  // prologue: first loads issued
     for (int s = 0; s < nstages; ++s) {
         stage_of(s, c0, tg0, tgn);
         __syncthreads();  // MFMAs of the previous stage are done with the tiles
-        CONV_PHASE(1)  // barrier 1
+        pp.lap(1);  // barrier 1
         if (tg0 == 0) {
             switch (a.pro) {
                 case SET_PRO_LRELU: commit_b(ic<SET_PRO_LRELU>{}, c0); break;
@@ -383,9 +372,9 @@ __global__ void __launch_bounds__(256, 2) conv1d_bf16_kernel(SetConv1dArgs a, in
             }
         }
         commit_a(c0, tgn);
-        CONV_PHASE(2)  // wait for the stage's loads + LDS writes
+        pp.lap(2);  // wait for the stage's loads + LDS writes
         __syncthreads();
-        CONV_PHASE(3)  // barrier 2
+        pp.lap(3);  // barrier 2
         auto mfma_tap = [&](int tl) {
             const int off = (tg0 + tl) * a.dil - a.pad - lo;  // >= 0: frame-row shift of this tap inside the B tile
             const unsigned char *ap = As + (tl * MB + wm * 64 + l31) * ROWB + half * 16;
@@ -408,17 +397,16 @@ __global__ void __launch_bounds__(256, 2) conv1d_bf16_kernel(SetConv1dArgs a, in
             if (tg1 == 0) issue_b(c1);
             issue_a(c1, tg1, tgn1);
         }
-        CONV_PHASE(4)  // issue of the next stage's loads
+        pp.lap(4);  // issue of the next stage's loads
         // (rolled: unrolled over the taps of a stage it ran 8 - 16 % slower, profiles/r06_conv_unroll_ab.log; the next stage's loads issued in
         // slices between the taps' MFMA groups instead of one burst behind the barrier: 5 - 10 % slower, profiles/r06_conv_sliced_issue_ab.log)
         for (int tl = 0; tl < tgn; ++tl) mfma_tap(tl);
-        CONV_PHASE(5)  // fragment reads + MFMAs of the stage
+        pp.lap(5);  // fragment reads + MFMAs of the stage
     }
 
-#if SET_CONV_PROBE
-    CONV_PHASE(5)  // (the last stage's MFMAs land here; per stage they are accounted below)
-    if (cprobe) { for (int i = 0; i < 6; ++i) g_conv_phase_buf[i] = cph[i]; g_conv_phase_buf[6] = (uint64_t)nstages; }
-#endif
+    pp.lap(5);  // (the last stage's MFMAs land here; per stage they are accounted below)
+    pp.count(6, (uint32_t)nstages);
+    pp.flush(g_conv_phase_buf);
     conv_bf16_epilogue<WM, WN>(a, acc, b, t0, r0, wm, wn, half, l31);
 }
 

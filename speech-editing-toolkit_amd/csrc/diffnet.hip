@@ -23,7 +23,13 @@
 
 #include "common.h"
 #include "diffnet_host.h"
+#include "phase_probe.h"
 #include "stack_queue.h"
+
+// probe builds (-DSET_PHASE_PROBE=1, tools/split_phase_probe.py with X2=0): wave 0 of block (tile 1, part 1) of diffnet_stack_split_kernel sums
+// the s_memtime ticks of its phases over the layers and adds them to buf[0..7] (0 wait for the previous layer, 1 stage, 2 GEMM 1, 3 gate +
+// z publish, 4 wait for z, 5 z load, 6 GEMM 2, 7 epilogue + publish)
+SET_PHASE_PROBE_BUFFER(g_split_phase_buf, set_debug_split_phase_buffer)
 
 namespace {
 
@@ -52,7 +58,7 @@ struct LayerTile {
     int64_t d_cs;
     const float *w1p, *b_dil, *w2p, *b_out;
     int T, t0, dil, first;
-    uint64_t *dbg;
+    uint64_t *dbg = nullptr;  // probe builds, diffnet_layer_kernel: the block's 8 words of SetDiffnetLayerArgs.dbg_clock
     // Winograd kernel only: tile geometry over frame offsets q = -1 .. 64 from the tile start.  Frames q >= o belong
     // to the NEXT utterance (cross-utterance tiling of the concatenated frame axis; o = 1 << 20 when the tile lies
     // inside one utterance): slab pointers above are those of the first utterance, x_bs4 / cp_bs4 the byte strides to
@@ -85,10 +91,8 @@ __device__ __forceinline__ void layer_tile(const LayerTile &a, float *smem) {
     const int XW = NTt + 2 * dil;  // tile width incl. halo
     const int T = a.T;
     const float *xin = a.xin;
-    uint64_t *dbg = a.dbg;
-#define PHASE_STAMP(i) \
-    if (dbg && tid == 0) dbg[i] = __builtin_amdgcn_s_memtime();
-    PHASE_STAMP(0)
+    PhaseProbe<6> pp;  // wave 0: 0 tile staged, 1 GEMM 1, 2 gate, 3 barrier + z staged, 4 GEMM 2, 5 epilogue
+    pp.start(a.dbg);
 
     // NB every global load below is UNCONDITIONAL on a clamped (always in-bounds) address and the validity
     // select happens afterwards: a `cond ? load : 0` makes hipcc branch around each load and drain vmcnt(0)
@@ -150,7 +154,7 @@ __device__ __forceinline__ void layer_tile(const LayerTile &a, float *smem) {
         }
     }
     __syncthreads();
-    PHASE_STAMP(1)
+    pp.lap(0);
 
     // ---- phase 1: GEMM 1  y[512 x NTt] += Wdil[512 x 768] * im2col(xs): k-step ks -> tap ks/128, channels 2*(ks%128)+{0,1}
     {
@@ -164,7 +168,7 @@ __device__ __forceinline__ void layer_tile(const LayerTile &a, float *smem) {
             if ((g % GPT) == GPT - 1) bp += dil - 128 * rstep;  // next tap: back to channel 0, shift by dil columns
         });
     }
-    PHASE_STAMP(2)
+    pp.lap(1);
 
     // ---- phase 2: gate, lane-local (acc[rb] pairs with acc[rb+2]); bias + conditioner are already inside -----
 #pragma unroll
@@ -176,7 +180,7 @@ __device__ __forceinline__ void layer_tile(const LayerTile &a, float *smem) {
                 const float z = fast_sigmoid(acc[rb][cb][r]) * fast_tanh(acc[rb + 2][cb][r]);
                 acc[rb][cb][r] = tv[cb] ? z : 0.0f;
             }
-    PHASE_STAMP(3)
+    pp.lap(2);
     __syncthreads();  // every wave is done reading xs
     // z tile zs[256][NTt] overlays the xs tile
 #pragma unroll
@@ -208,7 +212,7 @@ __device__ __forceinline__ void layer_tile(const LayerTile &a, float *smem) {
         if (rb == 1) __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();
-    PHASE_STAMP(4)
+    pp.lap(3);
 
     // ---- phase 3: GEMM 2  o[512 x NTt] += Wout[512 x 256] * zs ------------------------------------------------
     {
@@ -220,7 +224,7 @@ __device__ __forceinline__ void layer_tile(const LayerTile &a, float *smem) {
             bp += GS * rstep;
         });
     }
-    PHASE_STAMP(5)
+    pp.lap(4);
 
     // ---- phase 4: store-only epilogue: x_out = (x + o_res) * 2^-1/2 ; skip = skip + o_skip ----------------------
 #pragma unroll
@@ -238,8 +242,8 @@ __device__ __forceinline__ void layer_tile(const LayerTile &a, float *smem) {
                 }
         }
     }
-    PHASE_STAMP(6)
-#undef PHASE_STAMP
+    pp.lap(5);
+    pp.flush(a.dbg);
 }
 
 __global__ void __launch_bounds__(256, 2) diffnet_layer_kernel(SetDiffnetLayerArgs a) {
@@ -309,15 +313,10 @@ __device__ __forceinline__ void wino_init(const LayerTile &a, f32x16 (&m)[2][4])
 constexpr int WN_ZS_OFF = DC * WN_XW;
 
 template <bool UNIT_DIL>  // UNIT_DIL: every layer has dilation 1 (compile-time, keeps the shipped configuration's inner loop lean)
-__device__ __forceinline__ void wino_main(const LayerTile &a, f32x16 (&m)[2][4], float *smem, uint64_t *ph, int *s_task,
+__device__ __forceinline__ void wino_main(const LayerTile &a, f32x16 (&m)[2][4], float *smem, PhaseProbe<9> &pp, int *s_task,
                                           int claimed) {
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const int tid = threadIdx.x;
-#ifdef SET_WINO_PHASES
-#define WPH(k) { const uint64_t t_ = __builtin_amdgcn_s_memtime(); ph[k] += t_ - ph[9]; ph[9] = t_; }
-#else
-#define WPH(k)
-#endif
     const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0..7
     const int half = lane >> 5, l31 = lane & 31;
@@ -363,7 +362,7 @@ __device__ __forceinline__ void wino_main(const LayerTile &a, f32x16 (&m)[2][4],
         }
     }
     __syncthreads();
-    WPH(1)
+    pp.lap(1);
 
     // ---- GEMM 1 (Winograd): m[rf][p] += G_p[rows][c] * D_p[c][pair],  k-step = channels (2ks, 2ks+1)
     {
@@ -426,7 +425,7 @@ __device__ __forceinline__ void wino_main(const LayerTile &a, f32x16 (&m)[2][4],
         }
     }
 
-    WPH(2)
+    pp.lap(2);
     // ---- output transform + gate (lane-local): even frame y0 = M1 + M2 + M3, odd frame y1 = M2 - M3 - M4
     {
         const bool save = a.sy != nullptr;  // training forward: keep y (gate | filter rows) and z for the backward pass
@@ -494,7 +493,7 @@ __device__ __forceinline__ void wino_main(const LayerTile &a, f32x16 (&m)[2][4],
     }
     if (tid == 0) s_task[0] = claimed;  // next task of this block, read by everyone after the epilogue
     __syncthreads();
-    WPH(3)
+    pp.lap(3);
     {
         const AVec<2>::type *wp = reinterpret_cast<const AVec<2>::type *>(a.w2p) + (int64_t)w * WN_KS * 64 + lane;
         const float *bp = zs + half * WN_NT + l31;
@@ -504,7 +503,7 @@ __device__ __forceinline__ void wino_main(const LayerTile &a, f32x16 (&m)[2][4],
             bp += 8 * rstep;
         });
     }
-    WPH(4)
+    pp.lap(4);
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
         if (cb == 0 ? tv0 : tv1) {
@@ -521,8 +520,7 @@ __device__ __forceinline__ void wino_main(const LayerTile &a, f32x16 (&m)[2][4],
                 }
         }
     }
-    WPH(5)
-#undef WPH
+    pp.lap(5);
 }
 
 // ---- persistent layer stack: (layer, tile) task queue + per-tile epoch flags -----------------------------------
@@ -576,7 +574,6 @@ __global__ void __launch_bounds__(256, WPS) diffnet_stack_kernel(SetDiffnetStack
         lt.b_dil = a.b_dil_all + (int64_t)l * 512;
         lt.b_out = a.b_out_all + (int64_t)l * 512;
         lt.T = a.T; lt.t0 = j * NTt; lt.dil = 1 << (l % a.dilation_cycle_length); lt.first = (l == 0);
-        lt.dbg = nullptr;
         layer_tile<NCB, GS, true>(lt, smem);
         // publish tile i of layer l (outputs were stored agent-scope write-through: vmcnt drain = visible to every XCD)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave
@@ -651,8 +648,6 @@ __device__ __forceinline__ void split_gemm(f32x16 &acc, const float *wp, float (
     }
 }
 
-// debug: lane 0 of block (tile 1, part 1) adds the s_memtime ticks of its phases, summed over the layers, to buf[0..7]
-__device__ uint64_t *g_split_phase_buf = nullptr;
 
 __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetStackArgs a, int tiles_per_utt, int ntiles,
                                                                     int fault_tile) {
@@ -673,14 +668,8 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
     const rsrc_t rz = make_rsrc(a.z_ws + (int64_t)i * (DC * 32));
     const rsrc_t rskp = make_rsrc(a.skip + (int64_t)b * DC * T);
     const int vr = 4 * h + j;  // 32-row block of the images
-    uint64_t *dbg = (blockIdx.x == 5 && tid == 0) ? g_split_phase_buf : nullptr;
-    uint64_t tprev = dbg ? __builtin_amdgcn_s_memtime() : 0;
-#define SP_PHASE(p)                                           \
-    if (dbg) {                                                \
-        const uint64_t tn = __builtin_amdgcn_s_memtime();     \
-        dbg[p] += tn - tprev;                                 \
-        tprev = tn;                                           \
-    }
+    PhaseProbe<8> pp;
+    pp.start(g_split_phase_buf && blockIdx.x == 5);
     for (int l = 0; l < a.L; ++l) {
         const int dil = 1 << (l % a.dilation_cycle_length), XW = 32 + 2 * dil;
         const rsrc_t rxin = make_rsrc(((l & 1) ? a.xb : a.xa) + (int64_t)b * DC * T);
@@ -701,7 +690,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
         if (tid == 0) *s_ok = l == 0 ? 1 : stack_wait_parts(ready + i, ready + il, ready + ir, 4 * l, abort_flag, a.err_flag, true);
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(*s_ok) == 0) return;
-        SP_PHASE(0)
+        pp.lap(0);
         // ---- stage x + d (wave j: channels 64j .. 64j+63; zero outside [0, T): the conv pads x + d).  All 64 row loads
         //      of the wave are in flight at once: one memory round trip
         {
@@ -721,10 +710,10 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
             }
         }
         __syncthreads();
-        SP_PHASE(1)
+        pp.lap(1);
         // ---- GEMM 1: one 32-row block of  y = Wdil (*) (x + d)
         split_gemm<KS1>(acc[0][0], wp1, Ap, smem + half * XW + l31, 2 * XW, dil - 128 * 2 * XW);
-        SP_PHASE(2)
+        pp.lap(2);
         // ---- gate: the filter waves hand tanh(y_f) to the gate waves through LDS
         if (j >= 2) {
 #pragma unroll
@@ -742,7 +731,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the z rows of this wave are visible to every XCD
         __syncthreads();
         if (tid == 0) stack_publish_add(zcnt, i, l, fault_tile, false);
-        SP_PHASE(3)
+        pp.lap(3);
         // ---- GEMM 2 accumulator = b_out + x (residual rows) / + running skip sum (skip rows): these rows were written
         //      by this very wave one layer ago; the loads fly while lane 0 waits for the other parts' z rows
         {
@@ -767,7 +756,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
         if (tid == 0) *s_ok = stack_wait_parts(zcnt + i, zcnt + i, zcnt + i, 4 * (l + 1), abort_flag, a.err_flag, true);
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(*s_ok) == 0) return;
-        SP_PHASE(4)
+        pp.lap(4);
         // ---- the whole z tile [256][32] (one contiguous 32 KiB slot) -> LDS, same layout
         {
             f32x4 zv[8];
@@ -777,10 +766,10 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
             for (int k = 0; k < 8; ++k) *reinterpret_cast<f32x4 *>(smem + 4 * tid + 1024 * k) = zv[k];
         }
         __syncthreads();
-        SP_PHASE(5)
+        pp.lap(5);
         // ---- GEMM 2: one 32-row block of  o = Wout z
         split_gemm<KS2>(acc[0][0], wp2, Ap, smem + half * 32 + l31, 64, 0);
-        SP_PHASE(6)
+        pp.lap(6);
         // ---- epilogue: x' = (x + o_res) / sqrt 2 (agent scope: the neighbours' next layer reads it), skip += o_skip
         if (tv && j < 2) {
 #pragma unroll
@@ -794,9 +783,9 @@ __global__ void __launch_bounds__(256, 2) diffnet_stack_split_kernel(SetDiffnetS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // every store of the block has completed; the LDS tile is free for the next layer
         if (tid == 0) stack_publish_add(ready, i, l, fault_tile, h == 0);
-        SP_PHASE(7)
+        pp.lap(7);
     }
-#undef SP_PHASE
+    pp.flush(g_split_phase_buf);
 }
 
 // Winograd flavour of the persistent kernel: 512 threads, one block per CU, 64-frame tiles.  Same queue and flags
@@ -857,25 +846,18 @@ __global__ void __launch_bounds__(512, 2) diffnet_stack_wino_kernel(SetDiffnetSt
         lt.b_dil = a.b_dil_all + (int64_t)l * 512;
         lt.b_out = a.b_out_all + (int64_t)l * 512;
         lt.T = a.T; lt.dil = UNIT_DIL ? 1 : 1 << (l % a.dilation_cycle_length); lt.first = (l == 0);
-        lt.dbg = nullptr;
     };
-#ifdef SET_WINO_PHASES
-    // [0] init loads + vmcnt drain, [6] barrier, [8] flag/dep-wait/claim + barrier, [1] stage, [2] gemm1, [3] gate.., [4] gemm2, [5] epilogue
-    uint64_t ph[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    ph[9] = __builtin_amdgcn_s_memtime();
-#else
-    uint64_t *ph = nullptr;
-#endif
+    // probe builds (-DSET_PHASE_PROBE=1, tools/wino_probe.py with WINO_PHASES=1): wave 0 of every block adds its phase sums, in units of 1024
+    // ticks, to the 9 words behind the flags: 0 init loads + vmcnt drain, 6 barrier, 8 flag / dependency wait / claim + barrier, 1 stage,
+    // 2 GEMM 1, 3 gate.., 4 GEMM 2, 5 epilogue
+    PhaseProbe<9> pp;
+    pp.start(true);
     int i_done = -1, l_done = 0;  // finished but not yet published tile of this block
     auto publish = [&]() {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave
-#ifdef SET_WINO_PHASES
-        { const uint64_t t_ = __builtin_amdgcn_s_memtime(); ph[0] += t_ - ph[9]; ph[9] = t_; }
-#endif
+        pp.lap(0);
         __syncthreads();
-#ifdef SET_WINO_PHASES
-        { const uint64_t t_ = __builtin_amdgcn_s_memtime(); ph[6] += t_ - ph[9]; ph[9] = t_; }
-#endif
+        pp.lap(6);
         if (tid == 0 && i_done >= 0) {
             const uint64_t tf0 = __builtin_amdgcn_s_memtime();
             // no release fence: the tile's stores are agent-scope write-through (wino_main's epilogue), drained above
@@ -906,19 +888,14 @@ __global__ void __launch_bounds__(512, 2) diffnet_stack_wino_kernel(SetDiffnetSt
             i_done = -1;
             break;
         }
-#ifdef SET_WINO_PHASES
-        { const uint64_t t_ = __builtin_amdgcn_s_memtime(); ph[8] += t_ - ph[9]; ph[9] = t_; }
-#endif
-        wino_main<UNIT_DIL>(lt, m, smem, ph, s_task, claimed);
+        pp.lap(8);
+        wino_main<UNIT_DIL>(lt, m, smem, pp, s_task, claimed);
         i_done = i;
         l_done = l;
         n = __builtin_amdgcn_readfirstlane(s_task[0]);  // written by thread 0 before the barrier in front of GEMM 2
     }
     publish();
-#ifdef SET_WINO_PHASES
-    if (tid == 0)
-        for (int k = 0; k < 9; ++k) atomicAdd(a.sync_ws + sq_flags2(ntiles) + k, (int)(ph[k] >> 10));
-#endif
+    pp.flush_atomic(a.sync_ws + sq_flags2(ntiles));
     if (tid == 0) {  // units of 1024 ticks
         atomicAdd(a.sync_ws + SQ_WAIT_TICKS, (int)(wait_ticks >> 10));
         atomicAdd(a.sync_ws + SQ_FENCE_TICKS, (int)(fence_ticks >> 10));
@@ -1027,6 +1004,7 @@ extern "C" int set_diffnet_layer(const SetDiffnetLayerArgs *args, void *stream) 
     SET_REQUIRE(a.B > 0 && a.T > 0 && a.dil >= 1, "set_diffnet_layer");
     SET_REQUIRE(a.x_in != a.x_out, "set_diffnet_layer(x_in must not alias x_out)");
     if (a.dil > 8) return set_fail(SET_E_UNSUPPORTED, "set_diffnet_layer", "dilation > 8 (LDS tile > 80 KiB)");
+    if (a.dbg_clock && !SET_PHASE_PROBE) return set_fail(SET_E_UNSUPPORTED, "set_diffnet_layer(dbg_clock)", "library built without -DSET_PHASE_PROBE");
     const size_t lds = (size_t)DC * (NT + 2 * a.dil) * sizeof(float);
     static SetDeviceOnce lds_once;
     if (int rc = set_lds_optin(lds_once, 96 * 1024, "set_diffnet_layer(attr)", diffnet_layer_kernel)) return rc;
@@ -1035,10 +1013,6 @@ extern "C" int set_diffnet_layer(const SetDiffnetLayerArgs *args, void *stream) 
     return set_check_launch("set_diffnet_layer");
 }
 
-extern "C" int set_debug_split_phase_buffer(uint64_t *buf) {
-    SET_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_split_phase_buf), &buf, sizeof(buf)), "set_debug_split_phase_buffer");
-    return SET_OK;
-}
 
 extern "C" int64_t set_sizeof_diffnet_stack_args(void) { return (int64_t)sizeof(SetDiffnetStackArgs); }
 extern "C" int64_t set_sizeof_diffnet_layer_args(void) { return (int64_t)sizeof(SetDiffnetLayerArgs); }

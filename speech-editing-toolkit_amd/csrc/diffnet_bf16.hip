@@ -23,21 +23,17 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "phase_probe.h"
 #include "rows_sum.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
-// debug: phase time stamps (s_memtime) of one block of the layer kernels, see set_debug_bf16_phase_buffer
-__device__ uint64_t *g_bf16_phase_buf = nullptr;
-// (the per-layer kernels' stamps are stores through a generic pointer: compiled in only with -DSET_BF16_PROBE=1 -- tools/build_exp.sh
-// bf16probe diffnet_bf16.hip -DSET_BF16_PROBE=1 --, because one flat access makes the wait-count pass drain the weight ring with
-// vmcnt(0) at the top of every k-step group of the PRODUCTION kernel; the fused-layers kernels sum their stamps in scalar registers)
-#ifndef SET_BF16_PROBE
-#define SET_BF16_PROBE 0
-#endif
-#define BF16_PHASE(i)                                                                                    \
-    if (SET_BF16_PROBE && g_bf16_phase_buf && blockIdx.x == 1 && blockIdx.y == 1 && threadIdx.x == 0) g_bf16_phase_buf[i] = __builtin_amdgcn_s_memtime();
+// probe builds (-DSET_PHASE_PROBE=1): block (1, 1) of the layer kernels sums the s_memtime ticks of its phases and adds them to buf.
+//   diffnet_layer_fwd_bf16_kernel (tools/bf16_phase_probe.py), wave 0: buf[0..4] = stage, GEMM 1, gate, GEMM 2, epilogue
+//   diffnet_layers_reg / _t128_bf16_kernel (tools/bf16_layers_probe.py), layers m >= 1 of a group: wave 0 -> buf[0..4] = init + barrier,
+//   GEMM 1, gate, GEMM 2, epilogue, and the layer count in buf[7]; wave 4 -> buf[8..12]
+SET_PHASE_PROBE_BUFFER(g_bf16_phase_buf, set_debug_bf16_phase_buffer)
 
 namespace {
 
@@ -252,7 +248,8 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
     auto aoff1 = [&](int ks, int rb) { return (unsigned)((((RBW * w + (rb % RBW)) * KS1 + ks) * 2 + rb / RBW) * 1024); };
     auto aoff2 = [&](int ks, int rb) { return (unsigned)((((RBW * w + (rb % RBW)) * KS2 + ks) * 2 + rb / RBW) * 1024); };
 
-    BF16_PHASE(0)
+    PhaseProbe<5> pp;
+    pp.start(g_bf16_phase_buf && blockIdx.x == 1 && blockIdx.y == 1);
     // ---- stage the tiles: thread (frame row f, channel group cg).  ALL loads of the main pass (64 x + 48 cond per
     //      thread; no accumulator is live yet) are issued before the first one is consumed: one memory round trip instead
     //      of one per 32-channel batch; the per-utterance step offsets d[256] go through LDS (one load per channel per
@@ -328,7 +325,7 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
                 for (int cb = 0; cb < NCB; ++cb) acc[rb][cb][4 * g4 + e] = bv[e];
         }
     __syncthreads();
-    BF16_PHASE(1)
+    pp.lap(0);
 
     // ---- GEMM 1: y = [Wcond | Wdil tap 0 | tap 1 | tap 2] x [cond ; x+d shifted]
     gemm_bf16_a<2 * RBW, NCB>(acc, rw1, lane16, KS_C, lds, aoff1, [&](int ks, int cb) {
@@ -340,7 +337,7 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
         return (unsigned)((cb * 32 + l31 + tap * d) * XR + (c0 + half * 8) * 2);
     });
 
-    BF16_PHASE(2)
+    pp.lap(1);
     // ---- gate (lane-local: rb < RBW gate rows, rb + RBW the matching filter rows); save y and z in bf16; z tile over the x tile
     bool tv[NCB];
     unsigned vo4[NCB], vo2[NCB];
@@ -401,14 +398,14 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
                 for (int cb = 0; cb < NCB; ++cb) acc[rb][cb][4 * g4 + e] = rb < RBW ? bv[e] + xres[rb % RBW][cb][4 * g4 + e] : bv[e];
         }
     __syncthreads();
-    BF16_PHASE(3)
+    pp.lap(2);
 
     // ---- GEMM 2: o = Wout z
     gemm_bf16_a<2 * RBW, NCB>(acc, rw2, lane16, KS2, lds, aoff2, [&](int ks, int cb) {
         return (unsigned)((cb * 32 + l31) * XR + (ks * 16 + half * 8) * 2);
     });
 
-    BF16_PHASE(4)
+    pp.lap(3);
     // ---- epilogue: x' stores first (they need nothing), then the running skip sum is fetched and updated
 #pragma unroll
     for (int q = 0; q < RBW; ++q)
@@ -438,7 +435,8 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
             }
         }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    BF16_PHASE(5)
+    pp.lap(4);
+    pp.flush(g_bf16_phase_buf);
 }
 
 
@@ -675,17 +673,9 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
     const unsigned bz0 = ZS + (unsigned)(l31 * XR + half * 16);   // z tile
     const unsigned bb0 = DS + (unsigned)(a.nl * FC * 4) + (unsigned)((row_g + 4 * half) * 4);
 
-    // debug (tools/bf16_layers_probe.py): s_memtime ticks of the phases of the layers m >= 1 of block (1, 1), summed in scalar registers
-    // and written once at the end by wave 0 (buf[0..4], count in buf[7]) and wave 4 (buf[8..12]): no memory operation inside the
-    // layer loop (a flat access there made the wait-count pass drain the A ring, vmcnt(0), at the top of every k-step group)
+    // probe builds: the phases of the layers m >= 1, waves 0 and 4 of block (1, 1) (layout: at SET_PHASE_PROBE_BUFFER above)
     const bool probe = g_bf16_phase_buf && blockIdx.x == 1 && blockIdx.y == 1;
-    uint64_t tprev = 0, tph[5] = {0, 0, 0, 0, 0};
-#define LR_PHASE(i)                                                   \
-    if (probe && m >= 1) {                                            \
-        const uint64_t tn = __builtin_amdgcn_s_memtime();             \
-        tph[i] += tn - tprev;                                         \
-        tprev = tn;                                                   \
-    }
+    PhaseProbe<8> pp;
     typedef unsigned lr_u32x2 __attribute__((ext_vector_type(2)));
     // SKEW: a static priority instead of the per-k-step toggles -- waves 0-3 win every arbitration against their SIMD partners 4-7
     if (SKEW && w < 4) __builtin_amdgcn_s_setprio(1);
@@ -695,7 +685,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
         gemm_reg_prefetch<PF1>(A1, rw1, lane16, ab1);
     }
     for (int m = 0; m < a.nl; ++m) {
-        if (probe) tprev = __builtin_amdgcn_s_memtime();
+        pp.start(probe && m >= 1, w & 4);  // waves 0 and 4 sample
         const int l = a.l0 + m, d = 1 << (l % a.dilation_cycle_length);
         const bool last = m == a.nl - 1;
         const unsigned short *img = reinterpret_cast<const unsigned short *>(a.img) + (int64_t)m * N_IMG;
@@ -714,7 +704,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
                     for (int cb = 0; cb < NCB; ++cb) acc[rb][cb][4 * g4 + e] = bv[e];
             }
         lds_barrier();  // the x tile of this layer (staged above / written by the previous layer's epilogue) is complete
-        LR_PHASE(0)
+        pp.lap(0);
 
         // ---- GEMM 1: y = [Wcond | Wdil tap 0 | tap 1 | tap 2] x [cond ; x + d shifted]
         {
@@ -730,7 +720,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
             gemm_reg_run<KS1, PF1 / 4, !SKEW>(acc, A1, rw1, lane16, ab1, lds, bf1);
         }
         gemm_reg_prefetch<PF2>(A2, rw2, lane16, ab2);  // GEMM 2's first fragments travel under the gate
-        LR_PHASE(1)
+        pp.lap(1);
 
         // ---- gate -> z tile (own LDS tile: no wave has to wait for the others to leave GEMM 1)
 #pragma unroll
@@ -756,7 +746,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
                     for (int cb = 0; cb < NCB; ++cb) acc[rb][cb][4 * g4 + e] = rb == 0 ? bv[e] + xkeep[cb][4 * g4 + e] : bv[e];
             }
         lds_barrier();  // the z tile is complete (and every wave has left GEMM 1: the x tile may be overwritten)
-        LR_PHASE(2)
+        pp.lap(2);
 
         // ---- GEMM 2: o = Wout z  (z tile row j <-> frame ts + j)
         {
@@ -764,7 +754,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
             gemm_reg_run<KS2, PF2 / 4, !SKEW>(acc, A2, rw2, lane16, ab2, lds, bf2);
         }
         if (!last) gemm_reg_prefetch<PF1>(A1, make_rsrc(img + N_IMG), lane16, ab1);  // the next layer's first fragments
-        LR_PHASE(3)
+        pp.lap(3);
 
         // ---- epilogue: x' = (x + o_res) / sqrt 2 and the skip sum stay in registers; bf16(x' + d_next) -> the x tile
 #pragma unroll
@@ -800,14 +790,10 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
                 }
             }
         }
-        LR_PHASE(4)
+        pp.lap(4);
     }
-#undef LR_PHASE
-    if (probe && (tid == 0 || tid == 256)) {
-        uint64_t *pb = g_bf16_phase_buf + (tid ? 8 : 0);
-        for (int i = 0; i < 5; ++i) pb[i] += tph[i];
-        pb[7] += (uint64_t)(a.nl - 1);
-    }
+    pp.count(7, (uint32_t)(a.nl - 1));
+    pp.flush(g_bf16_phase_buf + 2 * w);  // wave 0 -> buf[0..7], wave 4 -> buf[8..15]
 }
 
 // =====================================================================================================================
@@ -1020,13 +1006,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
     const unsigned bb1 = BS + (unsigned)((row_g + 4 * half) * 4), bb2 = BS + 2048u + (unsigned)((row_g + 4 * half) * 4);
 
     const bool probe = g_bf16_phase_buf && blockIdx.x == 1 && blockIdx.y == 1;
-    uint64_t tprev = 0, tph[6] = {0, 0, 0, 0, 0, 0};
-#define LT_PHASE(i)                                                   \
-    if (probe && m >= 1) {                                            \
-        const uint64_t tn = __builtin_amdgcn_s_memtime();             \
-        tph[i] += tn - tprev;                                         \
-        tprev = tn;                                                   \
-    }
+    PhaseProbe<8> pp;
     typedef unsigned lt_u32x2 __attribute__((ext_vector_type(2)));
     if (SKEW && w < 4) __builtin_amdgcn_s_setprio(1);
     // old skip rows per column block: blocks < NSKR live in registers for the whole group, the others travel through the private copy per layer
@@ -1034,7 +1014,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
     u32x4_t A1[4 * D1][1], A2[4 * D2][1];
     gemm_t128_prefetch<1, 4 * D1>(A1, make_rsrc(reinterpret_cast<const unsigned short *>(a.img)), avo1, aoff1h(0));
     for (int m = 0; m < a.nl; ++m) {
-        if (probe) tprev = __builtin_amdgcn_s_memtime();
+        pp.start(probe && m >= 1, w & 4);  // waves 0 and 4 sample
         const int l = a.l0 + m, d = 1 << (l % a.dilation_cycle_length);
         const bool last = m == a.nl - 1;
         const unsigned short *img = reinterpret_cast<const unsigned short *>(a.img) + (int64_t)m * N_IMG;
@@ -1052,7 +1032,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
         };
         unsigned zp[2][NCB][2][2];  // packed gated z of both passes: [h][cb][g2][2 words = 4 channels]
         lds_barrier();  // B1: the x tile of this layer (staged above / written by the previous layer's epilogue) is complete
-        LT_PHASE(0)
+        pp.lap(0);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             // ---- GEMM 1, pass h: rows [16 gate ; 16 filter] x 128 frames, accumulators start at b_dil + b_cond
@@ -1106,7 +1086,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        LT_PHASE(1)
+        pp.lap(1);
         lds_barrier();  // B2: every wave has left GEMM 1: the z tile goes over the x tile
 #pragma unroll
         for (int h = 0; h < 2; ++h)
@@ -1121,7 +1101,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
         if (!last) { bsh[((m + 1) & 1) * 1024 + tid] = nb1; bsh[((m + 1) & 1) * 1024 + 512 + tid] = nb2; }
         __builtin_amdgcn_sched_barrier(0);
         lds_barrier();  // B3: the z tile is complete
-        LT_PHASE(2)
+        pp.lap(2);
 
         auto bf2 = [&](int kb, unsigned &b0, unsigned &bs) { b0 = bx0 + (unsigned)kb * 32u; bs = 32u * XR; };
         // ---- GEMM 2, skip pass: o_skip = Wout[skip rows] z + b_out; new skip rows = o_skip + old ones -> private copy / skip tensor
@@ -1175,7 +1155,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
                 for (int cb = 0; cb < NCB; ++cb) accx[0][cb][4 * g4 + e] += bv[e];
         }
         gemm_t128_run<1, KS2, D2, !SKEW, BDB2>(accx, A2, rw2, lane16, aoff2r(0), lds, bf2);
-        LT_PHASE(3)
+        pp.lap(3);
 
         // ---- epilogue: x' = (x + o_res) / sqrt 2 stays in accx; the next layer's first weight fragments; bf16(x' + d_next) packed in
         //      registers and written to the x tile once every wave has left GEMM 2
@@ -1215,14 +1195,10 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
                 }
             }
         }
-        LT_PHASE(4)
+        pp.lap(4);
     }
-#undef LT_PHASE
-    if (probe && (tid == 0 || tid == 256)) {
-        uint64_t *pb = g_bf16_phase_buf + (tid ? 8 : 0);
-        for (int i = 0; i < 5; ++i) pb[i] += tph[i];
-        pb[7] += (uint64_t)(a.nl - 1);
-    }
+    pp.count(7, (uint32_t)(a.nl - 1));
+    pp.flush(g_bf16_phase_buf + 2 * w);  // wave 0 -> buf[0..7], wave 4 -> buf[8..15]
 }
 
 // =====================================================================================================================
@@ -1682,9 +1658,3 @@ extern "C" int set_diffnet_layers_bwd_reduce(const float *part_dbo, const float 
     return set_check_launch("set_diffnet_layers_bwd_reduce");
 }
 
-// debug hook (tools/bf16_phase_probe.py): block (1, 1), thread 0 of the layer kernels stores s_memtime at its phase
-// boundaries into buf[0..7]; NULL switches it off.  Not part of the product path.
-extern "C" int set_debug_bf16_phase_buffer(uint64_t *buf) {
-    SET_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_bf16_phase_buf), &buf, sizeof(buf)), "set_debug_bf16_phase_buffer");
-    return SET_OK;
-}

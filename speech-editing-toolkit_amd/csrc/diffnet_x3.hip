@@ -36,26 +36,24 @@
 
 #include "common.h"
 #include "diffnet_host.h"
+#include "phase_probe.h"
 #include "stack_queue.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 
-// debug: lane 0 of block 0 adds the s_memtime ticks of its phases (claim + wait, stage, GEMM 1, gate, GEMM 2, epilogue +
-// publish), summed over its tasks, to buf[0..5] (+ sub-phases of the gate in buf[8..10]) and its task count to buf[7]
-__device__ uint64_t *g_x3_phase_buf = nullptr;
-// SET_X3_PROBE (default 0 since round 4; `tools/build_exp.sh probe diffnet_x3.hip -DSET_X3_PROBE=1` builds the library the phase
-// probes need).  The stamps add to counters through a generic pointer, and one flat access inside the task loop makes the wait-count
-// pass treat every outstanding load as possibly out of order (s_waitcnt vmcnt(0) at the top of every 4-k-step group of both GEMMs: the
-// weight ring drains once per group).  Without them: proper vmcnt(14) / vmcnt(12) ring waits, 1.788 -> 1.763 ms per 20-layer launch at
-// B = 32, T = 800 (the clock falls from 2.00 to 1.86 GHz at 1.40 kW: power-limited, profiles/r04_power.log).  The first build without
-// stamps faulted at 32-frame-tile shapes: the NCB = 1 instantiation staged its 256 step offsets with all 512 threads and the upper half
-// wrote past `dsh`, over the task slots behind it -- harmless only as long as the compiler kept the slot read in front of the staging,
-// which the build with stamps happened to do.  Fixed in x3_main (the bound on idx); the whole parity file passes on either build.
-#ifndef SET_X3_PROBE
-#define SET_X3_PROBE 0
-#endif
+// probe builds (-DSET_PHASE_PROBE=1): wave 0 of ONE block sums the s_memtime ticks of its phases and adds them to buf (the kernels ran
+// 1.788 -> 1.763 ms per 20-layer launch at B = 32, T = 800 once the shipped build lost its stamps, see phase_probe.h).
+//   diffnet_stack_x3_kernel (tools/x3_phase_probe.py, x3_pair_probe.py), block 0, summed over its tasks: 0 claim + wait, 1 stage, 2 GEMM 1,
+//     3 gate: tail barrier, 4 GEMM 2, 5 epilogue + publish, 7 task count, 8 gate: x residual + barrier, 9 gate: math + LDS, 10 gate: init,
+//     11 task boundary: issue, 12 task boundary: drain
+//   diffnet_stack_x3v_kernel (x3_phase_probe.py with X3_NAMES), block 0: 0 claim + accumulator start + wait, 1 first plane pair staged,
+//     2 its GEMMs, 3 E / O + second pair staged, 4 its GEMMs, 8 residual loads + gate, 9 GEMM 2, 10 epilogue issue, 5 publish, 7 task count
+//   diffnet_stack_split_x2_kernel (tools/split_phase_probe.py), block 5 = (tile 1, part 1), summed over the layers: 0 wait for the previous
+//     layer, 1 stage, 2 GEMM 1, 3 gate + z publish, 4 wait for z, 5 z load, 6 GEMM 2, 7 epilogue + publish
+// -DSET_PHASE_PROBE=2 (tools/x3_timeline_probe.py): the one-task timeline of diffnet_stack_x3v_kernel instead, rows of 32 dwords in buf
+SET_PHASE_PROBE_BUFFER(g_x3_phase_buf, set_debug_x3_phase_buffer)
 
 namespace {
 
@@ -331,15 +329,9 @@ __device__ __forceinline__ void x3_init(const X3Tile &a, f32x16 (&acc)[NU][2][NC
 }
 
 template <typename S, int NU, int NCB>
-__device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NCB], unsigned char *lds, unsigned piece_bytes, uint64_t *dbg,
-                                        uint64_t &tprev) {
-#define X3_PHASE(p)                                           \
-    if (dbg) {                                                \
-        const uint64_t tn = __builtin_amdgcn_s_memtime();     \
-        dbg[p] += tn - tprev;                                 \
-        tprev = tn;                                           \
-    }
-    X3_PHASE(0)
+__device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NCB], unsigned char *lds, unsigned piece_bytes,
+                                        PhaseProbe<13> &pp) {
+    pp.lap(0);
     constexpr int NP = S::NP;
     constexpr int NW = 8 / NU, NT = 64 * NW;  // waves / threads per block
     const int tid = threadIdx.x, lane = tid & 63;
@@ -442,14 +434,14 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[u][rb][cb][r] *= s1;
     __syncthreads();
-    X3_PHASE(1)
+    pp.lap(1);
 
     // ---- GEMM 1: y = Wdil (*) (x + d); k-step ks -> tap ks / 16 (a row shift of tap * d), channels 16 (ks % 16) ..
     gemm_x3<S, X_KS1, NU, NCB, (NU == 1 ? S::PF : S::PF2)>(
         acc, rw, lane16, (unsigned)(NU * w * X_KS1 * 2 * NP * 1024), (unsigned)(X_KS1 * 2 * NP * 1024), lds, piece_bytes, [&](int ks, int cb) {
             return (unsigned)((cb * RB + l31 + (ks >> 4) * d) * XR + ((ks & 15) * 16 + half * 8) * 2);
         });
-    X3_PHASE(2)
+    pp.lap(2);
 
     // ---- residual rows of x for GEMM 2's accumulator start: issued here, consumed after the gate
     // (NU = 2: after the gate -- no room for them next to 8 live accumulators and the gate's temporaries)
@@ -466,7 +458,7 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
     };
     if constexpr (NU == 1) load_xres();
     __syncthreads();  // every wave is done reading the x tile: the z tile overlays it (row cb * 32 + l31 <-> that block's frame)
-    X3_PHASE(8)
+    pp.lap(8);
     // ---- gate (lane-local: acc[u][0] gate rows, acc[u][1] the matching filter rows), split z, 4 consecutive channels per write
 #pragma unroll
     for (int u = 0; u < NU; ++u)
@@ -491,7 +483,7 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
                     *reinterpret_cast<u32x2_t *>(lds + q * piece_bytes + off) = uu;
                 }
             }
-    X3_PHASE(9)
+    pp.lap(9);
     if constexpr (NU != 1) load_xres();
     // ---- GEMM 2 accumulators: residual rows start at s2 (b_out + x), skip rows at s2 b_out (the running skip sum is added
     //      in the epilogue, after the x' stores are in flight)
@@ -523,15 +515,15 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
         }
     };
     if constexpr (NU == 1) load_sk();
-    X3_PHASE(10)
+    pp.lap(10);
     __syncthreads();
-    X3_PHASE(3)
+    pp.lap(3);
 
     // ---- GEMM 2: o = Wout z
     gemm_x3<S, X_KS2, NU, NCB, (NU == 1 ? S::PF : S::PF2)>(
         acc, rw, lane16, (unsigned)(x_n1<S>() * 2 + NU * w * X_KS2 * 2 * NP * 1024), (unsigned)(X_KS2 * 2 * NP * 1024), lds, piece_bytes,
         [&](int ks, int cb) { return (unsigned)((cb * 32 + l31) * XR + (ks * 16 + half * 8) * 2); });
-    X3_PHASE(4)
+    pp.lap(4);
 
     // ---- epilogue: x' (agent-scope write-through: other XCDs read it right after the publish), then the skip sum
 #pragma unroll
@@ -562,7 +554,6 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
         }
     }
 }
-#undef X3_PHASE
 
 // persistent (layer, tile) queue: the protocol of diffnet_stack_kernel (csrc/diffnet.hip)
 // NCB: 32-frame column blocks per tile (2: 64-frame tiles, the throughput shape; 1: 32-frame tiles for batches that leave
@@ -574,8 +565,8 @@ __global__ void __launch_bounds__(512 / NU, NU) diffnet_stack_x3_kernel(SetDiffn
     int *s_task = reinterpret_cast<int *>(lds + S::NP * piece_bytes + NCB * XC * sizeof(float));  // [0] next task, [1] peek result, [2] wait result
     int *counter = a.sync_ws + SQ_COUNTER, *abort_flag = a.sync_ws + SQ_ABORT, *done = a.sync_ws + SQ_FLAGS;
     const int tid = threadIdx.x;
-    uint64_t *dbg = (SET_X3_PROBE && blockIdx.x == 0 && tid == 0) ? g_x3_phase_buf : nullptr;
-    uint64_t tprev = dbg ? __builtin_amdgcn_s_memtime() : 0;
+    PhaseProbe<13> pp;
+    pp.start(g_x3_phase_buf && blockIdx.x == 0);
     // Each block claims its NEXT task while the current one runs (the result is read at the end of the task), issues the
     // next task's producer-independent loads before it drains the stores of the finished tile, and publishes that tile
     // before it waits for its own producers.  Claiming ahead is deadlock-free: a block finishes its claims in claim order,
@@ -600,9 +591,9 @@ __global__ void __launch_bounds__(512 / NU, NU) diffnet_stack_x3_kernel(SetDiffn
             if (l > 0) peek = min(ld_agent(f0), min(ld_agent(fl), ld_agent(fr)));
             claimed = atomicAdd(counter, 1);
         }
-        if (dbg) { const uint64_t tn = __builtin_amdgcn_s_memtime(); dbg[11] += tn - tprev; tprev = tn; }
+        pp.lap(11);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave: the finished tile is visible to every XCD
-        if (dbg) { const uint64_t tn = __builtin_amdgcn_s_memtime(); dbg[12] += tn - tprev; tprev = tn; }
+        pp.lap(12);
         if (tid == 0) {
             if (peek >= l) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             s_task[0] = claimed;
@@ -617,21 +608,18 @@ __global__ void __launch_bounds__(512 / NU, NU) diffnet_stack_x3_kernel(SetDiffn
             if (__builtin_amdgcn_readfirstlane(s_task[2]) == 0) break;
         }
         const int n_next = __builtin_amdgcn_readfirstlane(s_task[0]);
-        x3_main<S, NU, NCB>(lt, acc, lds, piece_bytes, dbg, tprev);
+        x3_main<S, NU, NCB>(lt, acc, lds, piece_bytes, pp);
         i_done = i;
         l_done = l;
         n = n_next;
-        if (dbg) {
-            const uint64_t tn = __builtin_amdgcn_s_memtime();
-            dbg[5] += tn - tprev;
-            dbg[7] += 1;
-            tprev = tn;
-        }
+        pp.lap(5);
+        pp.count(7);
     }
     // the last finished tile
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0 && i_done >= 0) stack_publish_store(done, i_done, l_done, fault_tile);
+    pp.flush(g_x3_phase_buf);
 }
 
 template <typename S, int NU, int NCB>
@@ -896,31 +884,10 @@ __device__ __forceinline__ void x3v_plane(f32x4 (&acc)[4][NB], u32x4_t (&A)[PFV]
     }
 }
 
-// (SET_X3_PROBE builds: lane 0 of block 0 adds its s_memtime ticks per phase to g_x3_phase_buf -- 0 claim + accumulator start + wait, 1 first
-// plane pair staged, 2 its GEMMs, 3 E / O + second pair staged, 4 its GEMMs, 8 residual loads + gate, 9 GEMM 2, 10 epilogue issue, 5 publish)
 template <int NB>
-__device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB], unsigned char *lds, uint64_t *dbg, uint64_t &tprev, uint64_t (&ts)[32]) {
-#if SET_X3_PROBE == 2  // timeline build: every wave keeps the s_memtime stamps of its task in SGPRs (ts[8 + p]), no memory access here
-#define X3V_PHASE(p)                                  \
-    {                                                 \
-        __builtin_amdgcn_sched_barrier(0);            \
-        ts[8 + (p)] = __builtin_amdgcn_s_memtime();   \
-        __builtin_amdgcn_sched_barrier(0);            \
-    }
-#else
-#define X3V_PHASE(p)                                          \
-    if (dbg) {                                                \
-        const uint64_t tn = __builtin_amdgcn_s_memtime();     \
-        dbg[p] += tn - tprev;                                 \
-        tprev = tn;                                           \
-    }
-#endif
-#if SET_X3_PROBE == 2
-#define X3V_TS(p) X3V_PHASE(p)  // stamps of the timeline build only
-#else
-#define X3V_TS(p)
-#endif
-    X3V_PHASE(0)
+__device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB], unsigned char *lds, PhaseProbe<11> &pp, PhaseTimeline<32> &tl) {
+    // phase p: a sum of the probe build and stamp 8 + p of the timeline build, which has stamps of its own besides (tl.mark alone)
+    pp.lap(0); tl.mark(8);
     typedef SplitF16x2 S;
     constexpr int PFV = XV_PF;
     int tid = threadIdx.x;
@@ -953,12 +920,12 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
         for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
             for (int q = 0; q < 2; ++q) A[p][mb][q] = buf_load_u4(rw, lane16, abase + (unsigned)(((p * 4 + mb) * 2 + q) * 1024));
-    X3V_TS(12)
+    tl.mark(20);
     __syncthreads();
-    X3V_PHASE(1)
+    pp.lap(1); tl.mark(9);
     x3v_plane<NB, PFV>(PQ[0], A, rw, lane16, abase, 0, lds, boff);
     x3v_plane<NB, PFV>(PQ[1], A, rw, lane16, abase, 1, lds + xv_plane<NB>(), boff);
-    X3V_PHASE(2)
+    pp.lap(2); tl.mark(10);
     x3v_stage_load<NB, 1>(a, w, lane, x12, xh);  // second pair's x: in flight through the E / O combine and the barrier
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -972,7 +939,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
                 PQ[1][mb][nb][i] = pp - qq;  // odd frame
             }
     __syncthreads();  // every wave is done reading the first pair of planes
-    X3V_TS(13)
+    tl.mark(21);
     // ---- second pair
     amax = fmaxf(amax, x3v_stage_store<NB, 1>(a, lds, dsh, w, lane, x12, xh));
     if (!(amax < 32768.0f) && a.err_flag) __hip_atomic_store(a.err_flag, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -982,12 +949,12 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
         for (int mb = 0; mb < 4; ++mb)
 #pragma unroll
             for (int q = 0; q < 2; ++q) A[p][mb][q] = buf_load_u4(rw, lane16, abase + (unsigned)((((16 + p) * 4 + mb) * 2 + q) * 1024));
-    X3V_TS(14)
+    tl.mark(22);
     __syncthreads();
-    X3V_PHASE(3)
+    pp.lap(3); tl.mark(11);
     x3v_plane<NB, PFV>(PQ[0], A, rw, lane16, abase, 2, lds, boff);
     x3v_plane<NB, PFV>(PQ[1], A, rw, lane16, abase, 3, lds + xv_plane<NB>(), boff);
-    X3V_PHASE(4)
+    pp.lap(4); tl.mark(12);
     // ---- residual rows of x for GEMM 2's accumulator start (issued here, consumed after the gate)
     bool tv[NB];
     unsigned vo4[NB];
@@ -1008,7 +975,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
         for (int r = 0; r < 16; ++r) xres[cb][r] = buf_load(rx, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
     }
     __syncthreads();  // every wave is done reading the V tile: the z tile overlays it (row = frame of the tile)
-    X3V_TS(15)
+    tl.mark(23);
     // ---- gate: lane (l15, kg) holds the pair's frames 2 l15 (PQ[0]) and 2 l15 + 1 (PQ[1]) of column block nb, channels 32 w + 16 m + 4 kg ..
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
@@ -1054,12 +1021,12 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
             for (int cb = 0; cb < NB; ++cb) acc[0][rb][cb][r] = (rb == 0 ? bias + xres[cb][r] : bias) * s2;
         }
     }
-    X3V_TS(16)
+    tl.mark(24);
     __syncthreads();
-    X3V_PHASE(8)
+    pp.lap(8); tl.mark(16);
     gemm_x3<S, X_KS2, 1, NB, XV_PF2>(acc, rw, lane16, (unsigned)(x_n1<S>() * 2 + w * X_KS2 * 2 * 2 * 1024), (unsigned)(X_KS2 * 2 * 2 * 1024), lds,
                                      xv_zpiece<NB>(), [&](int ks, int cb) { return (unsigned)((cb * 32 + l31) * XR + (ks * 16 + half * 8) * 2); });
-    X3V_PHASE(9)
+    pp.lap(9); tl.mark(17);
     // ---- epilogue
     const bool first = a.first != 0;
     float sk[NB][16];
@@ -1079,7 +1046,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
             for (int r = 0; r < 16; ++r) buf_store_agent((acc[0][0][cb][r] * is2) * RSQRT2, rxo, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
         }
     }
-    X3V_TS(17)
+    tl.mark(25);
 #pragma unroll
     for (int cb = 0; cb < NB; ++cb) {
         if (tv[cb]) {
@@ -1089,24 +1056,12 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
                 buf_store_agent(first ? acc[0][1][cb][r] * is2 : acc[0][1][cb][r] * is2 + sk[cb][r], rsk, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
         }
     }
-    X3V_PHASE(10)
+    pp.lap(10); tl.mark(18);
 }
-#undef X3V_PHASE
-#undef X3V_TS
 
 // the persistent (layer, tile) queue of diffnet_stack_x3_kernel (same flags, same publish protocol) on tiles of NB column blocks
-#if SET_X3_PROBE == 2
 #ifndef X3V_TL_TASK
-#define X3V_TL_TASK 10
-#endif
-#define X3V_KTS(p)                                \
-    {                                             \
-        __builtin_amdgcn_sched_barrier(0);        \
-        ts[p] = __builtin_amdgcn_s_memtime();     \
-        __builtin_amdgcn_sched_barrier(0);        \
-    }
-#else
-#define X3V_KTS(p)
+#define X3V_TL_TASK 10  // timeline build: the task of every block whose stamps are stored
 #endif
 template <int NB>
 __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetStackArgs a, int ntiles, int ntasks, int fault_tile) {
@@ -1115,14 +1070,14 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
     int *s_task = reinterpret_cast<int *>(lds + xv_tile<NB>() + NB * XC * sizeof(float));  // [0] next task, [1] peek result, [2] wait result
     int *counter = a.sync_ws + SQ_COUNTER, *abort_flag = a.sync_ws + SQ_ABORT, *done = a.sync_ws + SQ_FLAGS;
     const int tid = threadIdx.x;
-    uint64_t *dbg = (SET_X3_PROBE == 1 && blockIdx.x == 0 && tid == 0) ? g_x3_phase_buf : nullptr;
-    uint64_t tprev = dbg ? __builtin_amdgcn_s_memtime() : 0;
+    PhaseProbe<11> pp;
+    pp.start(SET_PHASE_PROBE == 1 && g_x3_phase_buf && blockIdx.x == 0);
+    PhaseTimeline<32> tl;
     if (tid == 0) s_task[0] = atomicAdd(counter, 1);
     __syncthreads();
     int n = __builtin_amdgcn_readfirstlane(s_task[0]);
     int i_done = -1, l_done = 0;
-    uint64_t ts[32] = {};
-#if SET_X3_PROBE == 2
+#if SET_PHASE_PROBE == 2
     int n_mine = 0;
 #endif
     while (n < ntasks) {
@@ -1130,7 +1085,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
         X3Tile lt;
         stack_fill_x3_tile(lt, a, l, i, NB, 1, x_nimg<S>());
         f32x4 PQ[2][4][NB];
-        X3V_KTS(0)
+        tl.mark(0);
         // the finished tile is published by every wave on its own, as soon as ITS stores are complete (agent-scope write-through stores: complete =
         // visible to every XCD): the tile's flag counts waves, 8 per layer.  (The block-wide form -- drain, barrier, one store -- published ~5 us
         // after the last wave's stores were issued, behind the next task's accumulator-start loads; profiles/r06_x3v_timeline.log,
@@ -1160,9 +1115,9 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
             if (l > 0) peek = min(ld_agent(f0), min(ld_agent(fl), ld_agent(fr))) / X3V_FLAG_UNIT;
             claimed = atomicAdd(counter, 1);
         }
-        X3V_KTS(1)
+        tl.mark(1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        X3V_KTS(2)
+        tl.mark(2);
         {
             float *dsh = reinterpret_cast<float *>(lds + xv_tile<NB>());
 #pragma unroll
@@ -1175,42 +1130,39 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
             s_task[1] = peek >= l ? 1 : 2;
         }
         __syncthreads();
-        X3V_KTS(3)
+        tl.mark(3);
         if (__builtin_amdgcn_readfirstlane(s_task[1]) == 2) {
             if (tid == 0) s_task[2] = stack_wait_tiles(f0, fl, fr, l * X3V_FLAG_UNIT, abort_flag, a.err_flag);
             __syncthreads();
             if (__builtin_amdgcn_readfirstlane(s_task[2]) == 0) break;
         }
         const int n_next = __builtin_amdgcn_readfirstlane(s_task[0]);
-        X3V_KTS(4)
-        x3v_main<NB>(lt, PQ, lds, dbg, tprev, ts);
-#if SET_X3_PROBE == 2
+        tl.mark(4);
+        x3v_main<NB>(lt, PQ, lds, pp, tl);
+#if SET_PHASE_PROBE == 2
         // timeline of this block's X3V_TL_TASK-th task, waves 0 and 7: row (2 block + wave / 7) of 32 dwords = ticks since the task's first stamp
         // (slot 5: the task number, 6: 1 if the dependency wait had to spin)
         if (++n_mine == X3V_TL_TASK && (tid == 0 || tid == 448) && g_x3_phase_buf) {
             const rsrc_t rt = make_rsrc(g_x3_phase_buf);
             const unsigned row = (unsigned)(2 * blockIdx.x + (tid ? 1 : 0)) * 128u;
 #pragma unroll
-            for (int k = 0; k < 32; ++k) __builtin_amdgcn_raw_buffer_store_b32((unsigned)(ts[k] - ts[0]), rt, (int)(row + 4 * k), 0, 0);
+            for (int k = 0; k < 32; ++k) __builtin_amdgcn_raw_buffer_store_b32((unsigned)(tl.ts[k] - tl.ts[0]), rt, (int)(row + 4 * k), 0, 0);
             __builtin_amdgcn_raw_buffer_store_b32((unsigned)n, rt, (int)(row + 20), 0, 0);
             __builtin_amdgcn_raw_buffer_store_b32((unsigned)s_task[1], rt, (int)(row + 24), 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32((unsigned)ts[0], rt, (int)(row + 28), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32((unsigned)tl.ts[0], rt, (int)(row + 28), 0, 0);
         } else if (n_mine == X3V_TL_TASK + 1 && (tid == 0 || tid == 448) && g_x3_phase_buf) {  // slot 31: the NEXT task's first stamp (absolute, as slot 7)
-            __builtin_amdgcn_raw_buffer_store_b32((unsigned)ts[0], make_rsrc(g_x3_phase_buf), (int)((unsigned)(2 * blockIdx.x + (tid ? 1 : 0)) * 128u + 124u), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32((unsigned)tl.ts[0], make_rsrc(g_x3_phase_buf), (int)((unsigned)(2 * blockIdx.x + (tid ? 1 : 0)) * 128u + 124u), 0, 0);
         }
 #endif
         i_done = i;
         l_done = l;
         n = n_next;
-        if (dbg) {
-            const uint64_t tn = __builtin_amdgcn_s_memtime();
-            dbg[5] += tn - tprev;
-            dbg[7] += 1;
-            tprev = tn;
-        }
+        pp.lap(5);
+        pp.count(7);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if ((tid & 63) == 0 && i_done >= 0) stack_publish_add(done, i_done, l_done, fault_tile);
+    pp.flush(g_x3_phase_buf);
 }
 
 template <int NB>
@@ -1360,14 +1312,8 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
     unsigned short *zt = reinterpret_cast<unsigned short *>(a.z_ws) + (int64_t)i * (2 * 32 * XC);  // [piece][frame][256]
     const rsrc_t rz = make_rsrc(zt);
     const rsrc_t rsk = make_rsrc(a.skip + (int64_t)b * XC * T);
-    uint64_t *dbg = (SET_X3_PROBE && blockIdx.x == 5 && tid == 0) ? g_x3_phase_buf : nullptr;  // debug (probe build only): phase ticks of one block, see below
-    uint64_t tprev = dbg ? __builtin_amdgcn_s_memtime() : 0;
-#define SX_PHASE(p)                                           \
-    if (dbg) {                                                \
-        const uint64_t tn = __builtin_amdgcn_s_memtime();     \
-        dbg[p] += tn - tprev;                                 \
-        tprev = tn;                                           \
-    }
+    PhaseProbe<8> pp;
+    pp.start(g_x3_phase_buf && blockIdx.x == 5);
     for (int l = 0; l < a.L; ++l) {
         const int d = 1 << (l % a.dilation_cycle_length);
         const unsigned short *img = reinterpret_cast<const unsigned short *>(a.wx3_all) + (int64_t)l * x_nimg<S>();
@@ -1392,7 +1338,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         if (tid == 0) *s_ok = l == 0 ? 1 : stack_wait_parts(ready + i, ready + il, ready + ir, 4 * l, abort_flag, a.err_flag, !nofence);
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(*s_ok) == 0) return;
-        SX_PHASE(0)
+        pp.lap(0);
         // ---- stage x + d as two fp16 pieces: thread (frame row f, 32 channels cg); rows 32 .. 32 + 2d - 1 by the lanes f < 2d
         {
             const int f = tid & 31, cg = tid >> 5;  // 8 channel groups
@@ -1444,12 +1390,12 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] *= s1;
         __syncthreads();
-        SX_PHASE(1)
+        pp.lap(1);
         // ---- GEMM 1: one 32-row block of  y = Wdil (*) (x + d)
         sx_gemm<X_KS1>(acc, A, rw, lane16, ab1, lds, piece_bytes, [&](int ks) {
             return (unsigned)((l31 + (ks >> 4) * d) * XR + ((ks & 15) * 16 + half * 8) * 2);
         });
-        SX_PHASE(2)
+        pp.lap(2);
         // ---- gate: the filter waves hand tanh(y_f) to the gate waves through LDS; z leaves already split
         if (rb == 1) {
 #pragma unroll
@@ -1479,7 +1425,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the z rows of this wave are visible to every XCD
         __syncthreads();
         if (tid == 0) stack_publish_add(zcnt, i, l, fault_tile, false);
-        SX_PHASE(3)
+        pp.lap(3);
         // ---- GEMM 2: A ring + accumulator start (residual rows: b_out + x; skip rows: b_out, the running sum joins in the
         //      epilogue) -- rows this very wave wrote one layer ago; the loads fly while lane 0 waits for the other parts' z
         const unsigned ab2 = (unsigned)(x_n1<S>() * 2 + ((w8 * X_KS2) * 2 + rb) * 2 * 1024);
@@ -1499,7 +1445,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         if (tid == 0) *s_ok = stack_wait_parts(zcnt + i, zcnt + i, zcnt + i, 4 * (l + 1), abort_flag, a.err_flag, !nofence);
         __syncthreads();
         if (__builtin_amdgcn_readfirstlane(*s_ok) == 0) return;
-        SX_PHASE(4)
+        pp.lap(4);
         // ---- the whole z tile (two pieces, 32 frames x 512 bytes each) -> LDS rows of XR bytes
         {
             u32x4_t zv[8];
@@ -1514,12 +1460,12 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
             }
         }
         __syncthreads();
-        SX_PHASE(5)
+        pp.lap(5);
         // ---- GEMM 2: one 32-row block of  o = Wout z
         sx_gemm<X_KS2>(acc, A, rw, lane16, ab2, lds, piece_bytes, [&](int ks) {
             return (unsigned)(l31 * XR + (ks * 16 + half * 8) * 2);
         });
-        SX_PHASE(6)
+        pp.lap(6);
         // ---- epilogue
         if (tv && rb == 0) {
 #pragma unroll
@@ -1533,9 +1479,9 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // every store of the block has completed; the LDS tile is free for the next layer
         if (tid == 0) stack_publish_add(ready, i, l, fault_tile, h == 0);
-        SX_PHASE(7)
+        pp.lap(7);
     }
-#undef SX_PHASE
+    pp.flush(g_x3_phase_buf);
 }
 
 }  // namespace
@@ -1558,11 +1504,6 @@ int set_launch_diffnet_stack_split_x2(const SetDiffnetStackArgs &a, const StackP
     hipLaunchKernelGGL(diffnet_stack_split_x2_kernel, dim3(4 * nt + extra), dim3(256), ldsz, s, a, tiles, nt, piece_bytes, stack_fault_tile(),
                        nofence);
     return set_check_launch("set_diffnet_stack");
-}
-
-extern "C" int set_debug_x3_phase_buffer(uint64_t *buf) {
-    SET_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_x3_phase_buf), &buf, sizeof(buf)), "set_debug_x3_phase_buffer");
-    return SET_OK;
 }
 
 extern "C" int64_t set_diffnet_layer_x3_image_size(int32_t mode) {

@@ -33,6 +33,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "phase_probe.h"
 
 typedef _Float16 rp_f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned rp_u32x4 __attribute__((ext_vector_type(4)));
@@ -41,9 +42,9 @@ typedef unsigned rp_u32x2 __attribute__((ext_vector_type(2)));
 // (device symbols do not link across translation units without -fgpu-rdc: this file keeps its own sticky range word, and
 // set_conv_x2_range_flag (csrc/conv_x2.hip) reads both through set_resblock_pair_range_flag_)
 __device__ int g_rp_range_flag = 0;
-// debug, builds with -DSET_RP_PROBE only (tools/resblock_phase_probe.py): thread 0 of every 16th block of batch row 1 adds the
-// s_memtime ticks of its phases to buf[0..4] and counts itself in buf[7], see set_debug_resblock_phase_buffer
-__device__ uint64_t *g_rp_phase_buf = nullptr;
+// probe builds (-DSET_PHASE_PROBE=1, tools/resblock_phase_probe.py): wave 0 of every 16th block of batch row 1 sums the s_memtime ticks of
+// its phases and adds them to buf[0..4] (atomically: several blocks sample), counting itself in buf[7]
+SET_PHASE_PROBE_BUFFER(g_rp_phase_buf, set_debug_resblock_phase_buffer)
 
 namespace {
 
@@ -89,20 +90,8 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
     const rsrc_t d_x = make_rsrc(xb);
     const unsigned lane16 = 16u * (unsigned)lane;
     const int rb_first = wm * RBW;
-#ifdef SET_RP_PROBE
-    uint64_t *const pbuf = g_rp_phase_buf;
-    const bool probe = pbuf != nullptr && tid == 0 && blockIdx.y == 1 && (blockIdx.x & 15) == 1;
-    uint64_t tprev = probe ? __builtin_amdgcn_s_memtime() : 0;
-    auto stamp = [&](int k) {
-        if (probe) {
-            const uint64_t t = __builtin_amdgcn_s_memtime();
-            atomicAdd(reinterpret_cast<unsigned long long *>(pbuf + k), (unsigned long long)(t - tprev));
-            tprev = t;
-        }
-    };
-#else
-    auto stamp = [](int) {};
-#endif
+    PhaseProbe<8> pp;
+    pp.start(g_rp_phase_buf && blockIdx.y == 1 && (blockIdx.x & 15) == 1);
 
     f32x16 acc[RBW][NCB];
 #pragma unroll
@@ -189,7 +178,7 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
             __syncthreads();  // MFMAs of the previous chunk are done with the tile
             commit_b(c * RP_KCH);
             __syncthreads();
-            stamp(0);  // wait for the chunk's loads + convert + LDS write
+            pp.lap(0);  // wait for the chunk's loads + convert + LDS write
             if (c + 1 < nchunks) issue_b((c + 1) * RP_KCH);
             for (int tap = 0; tap < K; ++tap) {
                 const int off = tap * a.dil;  // frame-row shift of this tap inside the chunk tile
@@ -221,7 +210,7 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
                     __builtin_amdgcn_s_setprio(0);
                 }
             }
-            stamp(1);  // GEMM 1 of the chunk issued
+            pp.lap(1);  // GEMM 1 of the chunk issued
         }
     }
     // the first fragments of W2 fly under epilogue 1
@@ -270,7 +259,7 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
     }
     if (!(amax < 32768.0f)) __hip_atomic_store(&g_rp_range_flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();
-    stamp(2);  // GEMM 1 drained + epilogue 1
+    pp.lap(2);  // GEMM 1 drained + epilogue 1
 
     // =========================== phase 2: y = W2 (*) t ============================================================
     for (int c = 0; c < nchunks; ++c) {
@@ -305,7 +294,7 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
         }
     }
 
-    stamp(3);  // GEMM 2 issued
+    pp.lap(3);  // GEMM 2 issued
     // ---- epilogue 2 (fp32): y = ((acc / s2 + b2) + x) (+ previous output) (/ out_div) on the NV central columns ----
     const bool has_acc = a.accumulate != 0, has_div = has_acc && a.out_div != 0.0f;
     const rsrc_t d_out = make_rsrc(a.out + (int64_t)b * a.out_bs);
@@ -345,10 +334,9 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
             }
         }
     }
-    stamp(4);  // GEMM 2 drained + epilogue 2 (residual / accumulate loads, stores issued)
-#ifdef SET_RP_PROBE
-    if (probe) atomicAdd(reinterpret_cast<unsigned long long *>(pbuf + 7), 1ull);
-#endif
+    pp.lap(4);  // GEMM 2 drained + epilogue 2 (residual / accumulate loads, stores issued)
+    pp.count(7);
+    pp.flush_atomic(g_rp_phase_buf);
 }
 
 template <int WM, int WN, int RBW, int NCB>
@@ -378,14 +366,6 @@ int set_resblock_pair_range_flag_(int *flag, int reset) {
         const int z = 0;
         SET_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_rp_range_flag), &z, sizeof(int)), "set_conv_x2_range_flag");
     }
-    return SET_OK;
-}
-
-extern "C" int set_debug_resblock_phase_buffer(uint64_t *buf) {
-#ifndef SET_RP_PROBE
-    if (buf) return set_fail(SET_E_UNSUPPORTED, "set_debug_resblock_phase_buffer", "library built without -DSET_RP_PROBE");
-#endif
-    SET_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_rp_phase_buf), &buf, sizeof(buf)), "set_debug_resblock_phase_buffer");
     return SET_OK;
 }
 

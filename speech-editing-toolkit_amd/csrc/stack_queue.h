@@ -14,7 +14,7 @@ constexpr int SQ_ABORT = 1;        // != 0: a wait gave up; every other wait giv
 constexpr int SQ_WAIT_TICKS = 2;   // diagnostics: s_memtime ticks / 1024 the claiming lanes spent waiting ...
 constexpr int SQ_FENCE_TICKS = 3;  // ... and publishing
 constexpr int SQ_FLAGS = 4;        // [ntiles] per-tile flags: layers done (block-wide store) or parts / waves done (add)
-// second per-tile array: the z rendezvous counters of the row-split kernels, the 9 phase sums of a -DSET_WINO_PHASES build
+// second per-tile array: the z rendezvous counters of the row-split kernels, the 9 phase sums of a -DSET_PHASE_PROBE=1 build
 __host__ __device__ constexpr int sq_flags2(int ntiles) { return SQ_FLAGS + ntiles; }
 constexpr int SQ_WINO_PHASE_WORDS = 12;
 constexpr int SQ_GROUP_WORDS = 16;  // fixed words of one stack: set_diffusion_loop gives utterance group g, first utterance b0, the

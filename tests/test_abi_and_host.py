@@ -24,7 +24,7 @@ def test_header_symbols_exported(built_lib):
     assert names == set(_lib.SIGNATURES), names ^ set(_lib.SIGNATURES)
     for n in names:
         assert hasattr(built_lib, n), n
-    assert built_lib.set_abi_version() == 3
+    assert built_lib.set_abi_version() == 4
 
 
 def test_struct_mirror_sizes(built_lib):
@@ -160,14 +160,16 @@ def test_training_reductions_have_no_atomic_twin():
     assert not hasattr(autograd_ops, "DETERMINISTIC_WGRAD")
 
 
-INSTRUMENT_BUILDS = (("diffnet_x3.hip", "-DSET_X3_PROBE=1"), ("diffnet_x3.hip", "-DSET_X3_PROBE=2"), ("diffnet.hip", "-DSET_WINO_PHASES"),
-                     ("bf16.hip", "-DSET_CONV_PROBE=1"), ("diffnet_bf16.hip", "-DSET_BF16_PROBE=1"), ("resblock_x2.hip", "-DSET_RP_PROBE=1"))
+PROBE_FILES = ("diffnet_x3.hip", "diffnet.hip", "diffnet_bf16.hip", "bf16.hip", "resblock_x2.hip")
+INSTRUMENT_BUILDS = tuple((f, "-DSET_PHASE_PROBE=1") for f in PROBE_FILES) + (("diffnet_x3.hip", "-DSET_PHASE_PROBE=2"),)
+RETIRED_PROBE_NAMES = ("X3_PHASE", "X3V_PHASE", "X3V_TS", "X3V_KTS", "SX_PHASE", "SP_PHASE", "WPH", "PHASE_STAMP", "BF16_PHASE", "LR_PHASE",
+                       "LT_PHASE", "CONV_PHASE", "SET_X3_PROBE", "SET_WINO_PHASES", "SET_BF16_PROBE", "SET_CONV_PROBE", "SET_RP_PROBE")
+needs_hipcc = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 
 
-@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
-def test_instrument_builds_compile():
-    """The phase-stamp builds that the live probes in tools/ load (tools/build_exp.sh) still compile for gfx950; the default build never
-    compiles their branches.  Device only, the flags of tools/isa_scan.py, in parallel."""
+def _device_asm(builds):
+    """[(file, define, return code, end of stderr, assembly lines)] of (file, define or None) builds: device only, the flags of
+    tools/isa_scan.py, in parallel.  Also returns the isa_scan module."""
     import importlib.util
     import subprocess
     import tempfile
@@ -178,15 +180,72 @@ def test_instrument_builds_compile():
 
     def one(build):
         f, define = build
-        out = os.path.join(tempfile.gettempdir(), "instrument_test_%d_%s_%s.s" % (os.getpid(), f, re.sub(r"\W", "_", define)))
-        r = subprocess.run(["hipcc"] + isa_scan.FLAGS + [define, "-o", out, os.path.join(isa_scan.CS, f)], capture_output=True, text=True)
+        out = os.path.join(tempfile.gettempdir(), "instrument_test_%d_%s_%s.s" % (os.getpid(), f, re.sub(r"\W", "_", define or "default")))
+        r = subprocess.run(["hipcc"] + isa_scan.FLAGS + ([define] if define else []) + ["-o", out, os.path.join(isa_scan.CS, f)],
+                           capture_output=True, text=True)
+        lines = []
         if os.path.exists(out):
+            lines = open(out).read().split("\n")
             os.remove(out)
-        return f, define, r.returncode, r.stderr[-2000:]
+        return f, define, r.returncode, r.stderr[-2000:], lines
 
-    with ThreadPoolExecutor(max_workers=len(INSTRUMENT_BUILDS)) as ex:
-        failed = [(f, d, err) for f, d, rc, err in ex.map(one, INSTRUMENT_BUILDS) if rc != 0]
+    with ThreadPoolExecutor(max_workers=len(builds)) as ex:
+        return list(ex.map(one, builds)), isa_scan
+
+
+@needs_hipcc
+def test_instrument_builds_compile():
+    """The phase-probe builds that the live probes in tools/ load (tools/build_exp.sh <tag> <file> -DSET_PHASE_PROBE=1; 2 = the x3v timeline)
+    still compile for gfx950; the default build never compiles their branches."""
+    built, _ = _device_asm(INSTRUMENT_BUILDS)
+    failed = [(f, d, err) for f, d, rc, err, _ in built if rc != 0]
     assert not failed, failed
+
+
+@needs_hipcc
+def test_shipped_kernels_hold_no_phase_stamps(built_lib):
+    """csrc/phase_probe.h is the only place a phase stamp is written, behind the one switch SET_PHASE_PROBE: in the default build of the five
+    instrumented files the only kernels that read s_memtime are the direct and the Winograd stack kernel (the SQ_WAIT_TICKS / SQ_FENCE_TICKS
+    diagnostics of their documented sync_ws words), and the retired stamp macros and switches are named nowhere in the sources, the
+    header, the package or the tools."""
+    built, isa_scan = _device_asm([(f, None) for f in PROBE_FILES])
+    allowed = re.compile(r"\d+(diffnet_stack_kernel|diffnet_stack_wino_kernel)I")
+    stamped, kernels = set(), 0
+    for f, _, rc, err, lines in built:
+        assert rc == 0, (f, err)
+        for name, body in isa_scan.kernels(lines):
+            kernels += 1
+            if any("s_memtime" in b for b in body):
+                stamped.add((f, name))
+    assert kernels >= 50, kernels  # the scan saw the kernels
+    assert stamped and all(f == "diffnet.hip" and allowed.search(name) for f, name in stamped), sorted(stamped)
+    assert {allowed.search(name).group(1) for _, name in stamped} == {"diffnet_stack_kernel", "diffnet_stack_wino_kernel"}
+    pkg = os.path.join(ROOT, "speech-editing-toolkit_amd")
+    retired = re.compile(r"\b(%s)\b" % "|".join(RETIRED_PROBE_NAMES))
+    files = [os.path.join(ROOT, "include", "set_amd.h")]
+    files += [os.path.join(pkg, "csrc", f) for f in sorted(os.listdir(os.path.join(pkg, "csrc"))) if f.endswith((".hip", ".h"))]
+    files += [os.path.join(pkg, f) for f in sorted(os.listdir(pkg)) if f.endswith(".py")]
+    files += [os.path.join(ROOT, "tools", f) for f in sorted(os.listdir(os.path.join(ROOT, "tools"))) if f.endswith(".py")]
+    for fn in files:
+        code = _strip_comments(open(fn).read(), python=fn.endswith(".py"))
+        assert not retired.search(code), (fn, retired.findall(code))
+    # one buffer + setter per file; the shipped setters take NULL only (no device call: this runs without a GPU)
+    from set_amd import _lib
+    word = C.c_uint64()
+    for name in ("bf16", "split", "x3", "resblock", "conv"):
+        fn = getattr(built_lib, "set_debug_%s_phase_buffer" % name)
+        assert fn(None) == _lib.OK
+        assert fn(C.addressof(word)) == _lib.E_UNSUPPORTED and b"SET_PHASE_PROBE" in built_lib.set_last_error(), name
+    a = _lib.SetDiffnetLayerArgs()
+    for k in ("x_in", "condproj", "dstep", "w1p", "b_dil", "w2p", "b_out", "skip"):
+        setattr(a, k, C.addressof(word))
+    a.x_out, a.dbg_clock, a.B, a.T, a.dil = C.addressof(word) + 4, C.addressof(word), 1, 1, 1
+    assert built_lib.set_diffnet_layer(C.byref(a), None) == _lib.E_UNSUPPORTED and b"SET_PHASE_PROBE" in built_lib.set_last_error()
+    for f in PROBE_FILES:
+        src = _strip_comments(open(os.path.join(pkg, "csrc", f)).read())
+        assert len(re.findall(r"^SET_PHASE_PROBE_BUFFER\(", src, flags=re.M)) == 1, f
+        gates = [g.strip() for g in re.findall(r"^#\s*(?:el)?if.*SET_PHASE_PROBE.*$", src, flags=re.M)]
+        assert gates == (["#if SET_PHASE_PROBE == 2"] * 2 if f == "diffnet_x3.hip" else []), (f, gates)  # the x3v timeline blocks only
 
 
 def test_state_dict_layout_matches_reference():

@@ -1,5 +1,6 @@
 """Phase shares of the layers m >= 1 of a fused group (set_diffnet_layers_fwd_bf16; s_memtime ticks of thread 0 of block (1, 1)) and
-the time per launch for several group sizes at B = 32, T = 800."""
+the time per launch for several group sizes at B = 32, T = 800.  Needs the probe build: tools/build_exp.sh probe diffnet_bf16.hip
+-DSET_PHASE_PROBE=1, then SET_AMD_LIB=build/exp/libset_amd_probe.so."""
 import os, sys, ctypes as C
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,4 +1,5 @@
-"""Phase timing of one block of the fused bf16 layer forward kernel (s_memtime stamps, 100 MHz reference clock)."""
+"""Phase timing of one block of the fused bf16 layer forward kernel (s_memtime ticks, 100 MHz reference clock, summed over the launches).
+Needs the probe build: tools/build_exp.sh probe diffnet_bf16.hip -DSET_PHASE_PROBE=1, then SET_AMD_LIB=build/exp/libset_amd_probe.so."""
 import os, sys, ctypes as C
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,13 +27,14 @@ if os.environ.get("TRAIN"):  # the training form: y / z saved in bf16 (quad-inte
     y16, z16 = torch.empty(B, 2 * Cc, T, dtype=torch.bfloat16, device=dev), torch.empty(B, Cc, T, dtype=torch.bfloat16, device=dev)
     a.y16, a.z16 = y16.data_ptr(), z16.data_ptr()
 for it in range(3):
+    buf.zero_()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(20):
         _lib.check(L.set_diffnet_layer_fwd_bf16(C.byref(a), None), "fwd")
     e1.record(); torch.cuda.synchronize()
     st = buf.cpu().tolist()
-    d = [(st[i + 1] - st[i]) / 100.0 for i in range(5)]
+    d = [st[i] / 100.0 / 20 for i in range(5)]
     print("tile %s: kernel %.1f us | stage %.1f gemm1 %.1f gate %.1f gemm2 %.1f epilogue %.1f (us, block (1,1))" % (
         os.environ.get("SET_AMD_BF16_TILE", "128"), e0.elapsed_time(e1) * 1000 / 20, *d))
 L.set_debug_bf16_phase_buffer(None)

@@ -1,7 +1,7 @@
-"""Per-stage phase times of one block of conv1d_bf16_kernel (measurement build: tools/build_exp.sh convprobe bf16.hip -DSET_CONV_PROBE=1, run with
+"""Per-stage phase times of one block of conv1d_bf16_kernel (measurement build: tools/build_exp.sh convprobe bf16.hip -DSET_PHASE_PROBE=1, run with
 SET_AMD_LIB=build/exp/libset_amd_convprobe.so).  Phases per stage: barrier 1 | wait for the stage's loads + LDS writes | barrier 2 | issue of the
 next stage's loads | fragment reads + MFMAs."""
-import ctypes as C, math, os, sys
+import math, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -10,7 +10,6 @@ from set_amd import ops, _lib
 torch.set_grad_enabled(False)
 dev = torch.device("cuda:0")
 L = _lib.lib()
-L.set_debug_conv_phase_buffer.argtypes = [C.c_void_p]
 buf = torch.zeros(8, dtype=torch.int64, device=dev)
 g = torch.Generator().manual_seed(0)
 SHAPES = [tuple(int(v) for v in s.split("x")) for s in os.environ.get("SHAPES", "16x768x192x9x800,16x192x768x9x800,32x192x192x5x800").split(",")]
@@ -23,7 +22,8 @@ for (B, Cin, Cout, K, T) in SHAPES:
     for _ in range(3):
         ops.conv1d(x, cw, b, dil=1, pad=(K - 1) // 2, impl="bf16", out=y)
     torch.cuda.synchronize()
-    assert L.set_debug_conv_phase_buffer(buf.data_ptr()) == 0
+    buf.zero_()
+    _lib.check(L.set_debug_conv_phase_buffer(buf.data_ptr()), "dbg")
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); ops.conv1d(x, cw, b, dil=1, pad=(K - 1) // 2, impl="bf16", out=y); e1.record(); torch.cuda.synchronize()
     L.set_debug_conv_phase_buffer(None)

@@ -1,4 +1,5 @@
-"""Diagnostic: per-phase s_memtime breakdown of diffnet_layer_kernel at the benchmark shape (B=32, T=800)."""
+"""Diagnostic: per-phase s_memtime breakdown of diffnet_layer_kernel at the benchmark shape (B=32, T=800).  Needs the probe build:
+tools/build_exp.sh probe diffnet.hip -DSET_PHASE_PROBE=1, then SET_AMD_LIB=build/exp/libset_amd_probe.so."""
 import os
 import sys
 
@@ -27,6 +28,7 @@ clk = torch.zeros(nblk, 8, dtype=torch.int64, device=dev)
 for it in range(3):
     ops.diffnet_layer(x, cp.data_ptr(), 512 * T, d.data_ptr(), 0, 1, w1p, bd, w2p, bo, xo, sk, 1, True, dbg_clock=clk)
 torch.cuda.synchronize()
+clk.zero_()  # the blocks ADD their phase sums
 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 ev0.record()
 ops.diffnet_layer(x, cp.data_ptr(), 512 * T, d.data_ptr(), 0, 1, w1p, bd, w2p, bo, xo, sk, 1, True, dbg_clock=clk)
@@ -34,8 +36,8 @@ ev1.record()
 torch.cuda.synchronize()
 ms = ev0.elapsed_time(ev1)
 c = clk.cpu().numpy().astype(np.uint64)
-d = (c[:, 1:7] - c[:, 0:6]).astype(np.float64)  # per-block deltas (s_memtime bases differ per XCD: only deltas are meaningful)
-tot = (c[:, 6] - c[:, 0]).astype(np.float64)
+d = c[:, 0:6].astype(np.float64)  # per-block phase sums of the one launch
+tot = d.sum(axis=1)
 labels = ["stage x", "GEMM1", "gate math", "barrier+z store", "GEMM2", "epilogue"]
 print("kernel %.1f us (hipEvent);  s_memtime ticks below; tick/us if block==kernel: %.1f" % (ms * 1e3, tot.max() / (ms * 1e3)))
 for i, n in enumerate(labels):

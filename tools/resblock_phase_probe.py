@@ -1,6 +1,7 @@
 """Phase shares of the fused ResBlock-pair kernel (s_memtime ticks of sampled blocks, set_debug_resblock_phase_buffer) and its
 time per launch at the HiFi-GAN V1 stage shapes (B = 64), next to the pair's HBM floor (read x + write out) and its MFMA time at
-the measured split-operand rate."""
+the measured split-operand rate.  Needs the probe build: tools/build_exp.sh probe resblock_x2.hip -DSET_PHASE_PROBE=1, then
+SET_AMD_LIB=build/exp/libset_amd_probe.so."""
 import math, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,5 +1,6 @@
 """Phase timing of one block of the row-split stack kernel (s_memtime ticks at 100 MHz, summed over the layers) and the
-kernel time per 20-layer launch, for small batches."""
+kernel time per 20-layer launch, for small batches.  Needs the probe build of the kernel's file: tools/build_exp.sh probe diffnet_x3.hip
+-DSET_PHASE_PROBE=1 (X2=0, the fp32 kernel: diffnet.hip), then SET_AMD_LIB=build/exp/libset_amd_probe.so."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

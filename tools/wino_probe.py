@@ -1,4 +1,6 @@
-"""Diagnostic: Winograd F(2,3) persistent stack vs the direct persistent stack (same real weights): max |diff| + time."""
+"""Diagnostic: Winograd F(2,3) persistent stack vs the direct persistent stack (same real weights): max |diff| + time.  WINO_PHASES=1 also
+prints the phase shares of the Winograd kernel (probe build: tools/build_exp.sh probe diffnet.hip -DSET_PHASE_PROBE=1, then
+SET_AMD_LIB=build/exp/libset_amd_probe.so; the words stay zero in the shipped library)."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,7 +39,8 @@ for mode in ("0", "2"):
     ms = e0.elapsed_time(e1) / 3
     w = ws[:4].cpu().tolist()
     if mode == "2" and os.environ.get("WINO_PHASES"):
-        nt = B * ((T + 63) // 64)
+        # the kernel tiles the concatenated frame axis here (dilation cycle 1, one step column, T even and >= 64: set_launch_diffnet_stack_f32)
+        nt = (B * T + 63) // 64 if T % 2 == 0 and T >= 64 else B * ((T + 63) // 64)
         ph = ws[4 + nt:4 + nt + 9].cpu().tolist(); tot = float(sum(ph))
         names = ["init+drain", "stage", "gemm1", "gate+prev", "gemm2", "epilogue", "barrier", "-", "flag/wait/claim"]
         print("   phases %%: %s" % "  ".join("%s %.1f" % (n, 100 * v / tot) for n, v in zip(names, ph) if n != "-"))

@@ -1,6 +1,7 @@
 """Split-operand stack kernel, block shape A/B at the benchmark shape: one 8-wave block per CU against two 4-wave blocks
 per CU (SET_AMD_X3_WAVES), over worker counts (SET_AMD_STACK_GRID).  Prints us per 20-layer launch, checks that every
-configuration gives the same bits, and the phase shares of block 0 (s_memtime) for the two defaults."""
+configuration gives the same bits, and the phase shares of block 0 (s_memtime) for the two defaults.  Needs the probe build:
+tools/build_exp.sh probe diffnet_x3.hip -DSET_PHASE_PROBE=1, then SET_AMD_LIB=build/exp/libset_amd_probe.so."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,5 +1,6 @@
 """Phase timing of block 0 of the split-operand stack kernel (s_memtime ticks, summed over its tasks) and the kernel time
-per 20-layer launch at the benchmark shape."""
+per 20-layer launch at the benchmark shape.  Needs the probe build: tools/build_exp.sh probe diffnet_x3.hip -DSET_PHASE_PROBE=1, then
+SET_AMD_LIB=build/exp/libset_amd_probe.so (the shipped library has no phase stamps: its setter refuses the buffer)."""
 import os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -40,10 +41,6 @@ for B, T in [tuple(int(v) for v in s.split("x")) for s in os.environ.get("SIZES"
     NAMES = ("claim+wait", "stage", "gemm1", "gate:tail-barrier", "gemm2", "epi+publish", "-", "-", "gate:xres+barrier", "gate:math+lds", "gate:init", "boundary:issue", "boundary:drain")
     if os.environ.get("X3_NAMES"):  # other kernels of the family stamp other phases (x3v: see x3v_main)
         NAMES = tuple(os.environ["X3_NAMES"].split(","))
-    if tot == 0:  # the shipped library has no phase stamps (SET_X3_PROBE=0): time only
-        print("B=%d T=%d: %.1f us per 20-layer launch (no phase stamps in this build: tools/build_exp.sh probe diffnet_x3.hip -DSET_X3_PROBE=1, "
-              "then SET_AMD_LIB=build/exp/libset_amd_probe.so)" % (B, T, us))
-        continue
     print("mode %d, ticks per us: %.1f" % (wx3.mode, tot / (us * n)))
     print("B=%d T=%d: %.1f us per 20-layer launch; block 0: %d tasks/launch, %.1f us per task | share: %s" % (
         B, T, us, ntask // n, us / (ntask / n), " ".join("%s %.1f%%" % (nm, 100.0 * v / tot) for nm, v in zip(NAMES, st) if nm != "-")))

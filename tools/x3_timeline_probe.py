@@ -1,4 +1,4 @@
-"""Timeline of ONE task of every block of diffnet_stack_x3v_kernel (timeline build: tools/build_exp.sh tl diffnet_x3.hip -DSET_X3_PROBE=2, then
+"""Timeline of ONE task of every block of diffnet_stack_x3v_kernel (timeline build: tools/build_exp.sh tl diffnet_x3.hip -DSET_PHASE_PROBE=2, then
 SET_AMD_LIB=build/exp/libset_amd_tl.so): every wave keeps s_memtime stamps of its X3V_TL_TASK-th task in SGPRs and waves 0 and 7 store them once,
 after the task -- no memory access between the stamps, unlike the summed phase counters of tools/x3_phase_probe.py.  Prints the median (and
 10 / 90 % quantiles) of every interval over the blocks, in us (ticks scaled by the median task period = next task's first stamp - this one's)."""
