@@ -830,6 +830,41 @@ int set_mask_fill_chan(const float *x, const float *e, const float *m, float *ou
 /* out[c] += sum_{b,t} d[b][c][t] * m[b][t]   (gradient of mask_emb) */
 int set_masked_channel_sum(const float *d, const float *m, float *out, int32_t B, int32_t C, int32_t T, void *stream);
 
+/* Log-mel front end: wav [B][wav_bs >= N] fp32 -> mel [B][T][n_mels] fp32 in one launch (the layout of the reference's item['mel']):
+ * Hann-windowed STFT, magnitude sqrt(re^2 + im^2 + mag_eps), filterbank product, log_scale * log(max(mel, floor)).  Replaces
+ * utils/audio/__init__.py:64-75 (librosa_wav2spec: pad = n_fft / 2, reflect = 0, clamp_input = 0, mag_eps = 0, floor = 1e-6,
+ * log_scale = 1 / ln 10) and modules/vocoder/hifigan/mel_utils.py:59-76 (pad = (n_fft - hop) / 2, reflect = 1, clamp_input = 1,
+ * mag_eps = 1e-9, floor = 1e-5, log_scale = 1).  Both GEMMs run on v_mfma_f32_32x32x2_f32; the spectrum stays on chip.
+ *   lengths   int64 [B] samples per row (NULL: N each), clamped to [0, N]; nothing past a row's length is read.  Row b has
+ *             T_b = 1 + (len_b + 2 pad - n_fft) / hop frames (0 when negative); frames T_b .. T-1 are written as 0.0.  With reflect = 1
+ *             the caller guarantees len_b > pad (the entry checks N only: lengths live on the device).
+ *   T         = 1 + (N + 2 pad - n_fft) / hop
+ *   table     image of W[2][nbins rounded up to 32s][n_fft], W[0][f][n] = win[n] cos(2 pi (bin_lo + f) n / n_fft),
+ *             W[1][f][n] = -win[n] sin(...), rows of bins >= bin_lo + nbins zero: set_log_mel_table_size(n_fft, nbins) floats ordered
+ *             [32-bin chunk][n / 4][lane 0..63][4], element e = W[e & 1][32 chunk + (lane & 31)][4 (n / 4) + 2 (e >> 1) + (lane >> 5)]
+ *   basis     image of mel_basis [n_mels][n_fft / 2 + 1], ordered [32-bin chunk][r 0..15][lane][4], element e < 3 =
+ *             mel_basis[32 e + (lane & 31)][bin_lo + 32 chunk + (r & 3) + 8 (r >> 2) + 4 (lane >> 5)] (0 outside the matrix), e = 3: 0
+ *   bin_lo    first bin computed, a multiple of 32; nbins bins from there (bin_lo + nbins <= n_fft / 2 + 1)
+ * Built for n_fft = 1024, hop = 256, n_mels <= 96: anything else is SET_E_UNSUPPORTED.  No atomics: bit-reproducible, and a row of a
+ * ragged batch equals the same waveform run alone.  table / basis 16-byte aligned; mel too when n_mels is a multiple of 4. */
+typedef struct SetLogMelArgs {
+    const float *wav;
+    const int64_t *lengths;
+    const float *table, *basis;
+    float *mel;
+    int64_t wav_bs;
+    double log_scale;
+    int32_t B, N, T;
+    int32_t n_fft, hop, n_mels;
+    int32_t bin_lo, nbins;
+    int32_t pad, reflect, clamp_input;
+    float mag_eps, floor;
+    int32_t pad_;
+} SetLogMelArgs;
+int64_t set_sizeof_log_mel_args(void);
+int64_t set_log_mel_table_size(int32_t n_fft, int32_t nbins);
+int set_log_mel(const SetLogMelArgs *args, void *stream);
+
 /* MFMA fragment-layout self test: runs a 32x32xK product through v_mfma_f32_32x32x2_f32 with the layout
  * this library assumes and returns the max abs error vs an in-kernel scalar reference via *max_err (HOST).
  * Synchronises.  Used by tests to pin the hardware layout assumption. */

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_PKG, "libset_amd.so")
 # measurement only (tools/build_exp.sh): load an experimental build of the library instead; never built or rebuilt from here
 _LIB_OVERRIDE = os.environ.get("SET_AMD_LIB")
 SOURCES = ["conv1d.hip", "conv_x2.hip", "resblock_x2.hip", "glue.hip", "diffnet.hip", "diffnet_x3.hip", "boundary.hip", "diffusion_ops.hip", "diffusion_loop.hip",
-           "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip"]
+           "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip", "melspec.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 # constants mirrored from set_amd.h
@@ -189,6 +189,18 @@ class SetAttnBwdArgs(C.Structure):
     ]
 
 
+class SetLogMelArgs(C.Structure):
+    _fields_ = [
+        ("wav", C.c_void_p), ("lengths", C.c_void_p), ("table", C.c_void_p), ("basis", C.c_void_p), ("mel", C.c_void_p),
+        ("wav_bs", C.c_int64), ("log_scale", C.c_double),
+        ("B", C.c_int32), ("N", C.c_int32), ("T", C.c_int32),
+        ("n_fft", C.c_int32), ("hop", C.c_int32), ("n_mels", C.c_int32),
+        ("bin_lo", C.c_int32), ("nbins", C.c_int32),
+        ("pad", C.c_int32), ("reflect", C.c_int32), ("clamp_input", C.c_int32),
+        ("mag_eps", C.c_float), ("floor", C.c_float), ("pad_", C.c_int32),
+    ]
+
+
 _V, _I32, _I64, _U64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/set_amd.h declares
@@ -325,6 +337,9 @@ SIGNATURES = {
     "set_stutter_head_loss": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _V]),
     "set_stutter_head_loss_bwd": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _V]),
     "set_stutter_head_bwd_reduce": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _V]),
+    "set_sizeof_log_mel_args": (_I64, []),
+    "set_log_mel_table_size": (_I64, [_I32, _I32]),
+    "set_log_mel": (C.c_int, [C.POINTER(SetLogMelArgs), _V]),
     "set_frame_weight": (C.c_int, [_V, _V, _I64, _I32, _V]),
     "set_l1_elem": (C.c_int, [_V, _V, _V, _V, _I64, _V]),
     "set_scale_bcast": (C.c_int, [_V, _V, _V, _I64, _I64, _V, _F, _V]),
@@ -431,6 +446,7 @@ def lib():
     assert L.set_sizeof_diffnet_layer_bf16_args() == C.sizeof(SetDiffnetLayerBf16Args), "SetDiffnetLayerBf16Args ABI mismatch"
     assert L.set_sizeof_diffnet_layers_bf16_args() == C.sizeof(SetDiffnetLayersBf16Args), "SetDiffnetLayersBf16Args ABI mismatch"
     assert L.set_sizeof_diffnet_layer_bf16_bwd_args() == C.sizeof(SetDiffnetLayerBf16BwdArgs), "SetDiffnetLayerBf16BwdArgs ABI mismatch"
+    assert L.set_sizeof_log_mel_args() == C.sizeof(SetLogMelArgs), "SetLogMelArgs ABI mismatch"
     _lib = L
     return L
 

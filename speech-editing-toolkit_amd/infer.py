@@ -122,6 +122,7 @@ class SpecDenoiserInfer:
             raise RuntimeError("SpecDenoiserInfer (set_amd) needs an MI355X: there is no CPU fallback for this path")
         self.hparams = hparams
         self.device = torch.device(device or "cuda")
+        self._log_mel = None  # melspec.LogMel of these hparams, built when an item arrives without 'mel'
         self.model = (model if model is not None else self.build_model()).to(self.device).eval()
         self.vocoder = (vocoder if vocoder is not None else self.build_vocoder()).to(self.device).eval()
 
@@ -150,8 +151,16 @@ class SpecDenoiserInfer:
         """inference/tts/base_tts_infer.py:44-47: c [B,T,80] -> wav [B, T*hop]"""
         return self.vocoder(ops.btc_to_bct(c.contiguous()))[:, 0]
 
+    def wav_to_mel(self, wav):
+        """wav [1,N] on the GPU -> mel [1,T,n_mels]: what librosa_wav2spec puts into item['mel'] upstream (inference/tts/spec_denoiser.py:258)."""
+        if self._log_mel is None:
+            from .melspec import LogMel
+            self._log_mel = LogMel(self.hparams, "librosa")
+        return self._log_mel(wav.contiguous())
+
     def input_to_batch(self, item):
-        """inference/tts/spec_denoiser.py:198-248 without the speaker encoder (`spk_embed` must be in the item)."""
+        """inference/tts/spec_denoiser.py:198-248 without the speaker encoder (`spk_embed` must be in the item).  An item without 'mel'
+        gets it from its 'wav' on the GPU."""
         dev = self.device
         if "spk_embed" not in item:
             raise KeyError("spk_embed: the speaker encoder (resemblyzer) is outside this build; pass the embedding")
@@ -166,8 +175,10 @@ class SpecDenoiserInfer:
                  "ph": [item.get("ph", "")], "ph2word": L("ph2word"), "edited_ph2word": L("edited_ph2word"),
                  "mel2ph": L("mel2ph"), "mel2word": L("mel2word"), "dur": L("dur"), "txt_tokens": L("ph_token"),
                  "edited_txt_tokens": L("edited_ph_token"), "words_region": item["words_region"],
-                 "edited_words_region": item["edited_words_region"], "mel": Fl("mel"), "spk_embed": Fl("spk_embed"),
-                 "f0": Fl("f0"), "uv": Fl("uv")}
+                 "edited_words_region": item["edited_words_region"], "mel": Fl("mel") if "mel" in item else self.wav_to_mel(Fl("wav")),
+                 "spk_embed": Fl("spk_embed"), "f0": Fl("f0"), "uv": Fl("uv")}
+        if "mel" not in item and batch["mel"].shape[1] != batch["mel2ph"].shape[1]:
+            raise ValueError("the waveform gives %d mel frames but mel2ph has %d" % (batch["mel"].shape[1], batch["mel2ph"].shape[1]))
         batch["txt_lengths"] = torch.tensor([batch["txt_tokens"].shape[1]], dtype=torch.int64, device=dev)
         if "wav" in item:
             batch["wav"] = Fl("wav")

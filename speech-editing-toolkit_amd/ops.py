@@ -575,6 +575,22 @@ def stutter_head(h, w, b):
     return logits
 
 
+def log_mel(wav, table, basis, lengths=None, *, n_fft, hop, n_mels, bin_lo, nbins, pad, reflect, clamp_input, mag_eps, floor, log_scale):
+    """set_log_mel: wav [B,N] -> log-mel [B,T,n_mels] in one launch (melspec.LogMel prepares `table` / `basis`, the packed DFT table and
+    filterbank images; `lengths` int64 [B] on the device or None).  Frames at or beyond a row's own count are 0.0."""
+    _f(wav, "wav"), _f(table, "table"), _f(basis, "basis"), _i(lengths, "lengths")
+    B, N = wav.shape
+    T = 1 + (N + 2 * pad - n_fft) // hop
+    mel = torch.empty(B, max(T, 0), n_mels, dtype=torch.float32, device=wav.device)
+    a = _lib.SetLogMelArgs(wav=_p(wav), lengths=_p(lengths), table=_p(table), basis=_p(basis), mel=_p(mel), wav_bs=wav.stride(0),
+                           log_scale=float(log_scale), B=B, N=N, T=T, n_fft=n_fft, hop=hop, n_mels=n_mels, bin_lo=bin_lo, nbins=nbins,
+                           pad=pad, reflect=int(reflect), clamp_input=int(clamp_input), mag_eps=float(mag_eps), floor=float(floor))
+    if table.numel() < _lib.lib().set_log_mel_table_size(n_fft, nbins) or basis.numel() < (nbins + 31) // 32 * 16 * 64 * 4:
+        raise ValueError("log_mel: table / basis images are smaller than n_fft = %d, nbins = %d need" % (n_fft, nbins))
+    check(_lib.lib().set_log_mel(C.byref(a), _stream()), "set_log_mel")
+    return mel
+
+
 def preln_self_attn(x, ln, attn, key_padding=None, mask=None, eps=1e-5):
     """Inference form of autograd_ops.preln_self_attn."""
     h = layernorm_ch(x, ln[0], ln[1], eps=eps)
