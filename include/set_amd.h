@@ -865,6 +865,36 @@ int64_t set_sizeof_log_mel_args(void);
 int64_t set_log_mel_table_size(int32_t n_fft, int32_t nbins);
 int set_log_mel(const SetLogMelArgs *args, void *stream);
 
+/* Mel-cepstral distortion (csrc/mcd.hip; utils/eval/mcd.py `get_metrics_mels`, utils/metrics/dtw.py).  All tensors fp32 and contiguous
+ * unless stated; every `len*` is int64 [B] on the device or NULL (every row full).  A length is read as clamped into [1, T] ([0, T] for
+ * set_mfcc): no kernel leaves its buffers whatever the device holds.  No atomics anywhere: two runs agree bit for bit, and a row of a ragged
+ * batch equals the same pair run alone.
+ *
+ * set_mfcc: mel [B][T][M] -> out [B][T][K], out[b][t][k-1] = sum_n x[n] table[k-1][n] in ascending n (fp32 FMA), x = mel or, with
+ *   take_log, log10(mel) rounded once from double.  table [K][M] = cos(pi k (2n+1) / (2M)), k = 1..K (metrics.dct_table).  Rows
+ *   t >= lengths[b] are written as +0.0.  K <= 64, M <= 96, else SET_E_UNSUPPORTED.
+ * set_dtw: x [B][Tx][K], y [B][Ty][K] -> dist [B] = D[len_x-1][len_y-1], steps [B] int32 = the length of the optimal path, and, when
+ *   dir != NULL, dir [B][Tx][Ty] uint8 = the predecessor chosen per cell (0 diagonal, 1 row above, 2 column before).
+ *   C[i][j] = sqrt(sum_k (x_ik - y_jk)^2) in the difference form; D[i][j] = C[i][j] + min(D[i-1][j-1], D[i-1][j], D[i][j-1]), +inf outside
+ *   the matrix, D[0][0] = C[0][0]; ties go to the first of the three in that order; L[i][j] = 1 + L[chosen], L[0][0] = 1.  Rows >= len_x and
+ *   columns >= len_y are never read, and dir outside [0, len_x) x [0, len_y) is not written.  One 256-thread block per pair, dynamic LDS
+ *   (320 (KP + 1) + 2 Ty + 16) * 4 bytes with KP = 40 (K <= 40) or 64.  K <= 64, Ty <= 8192, else SET_E_UNSUPPORTED.
+ * set_dtw_path: dir, steps -> path [B][Tx + Ty - 1][2] int32: entries 0 .. steps[b]-1 are (i, j) from (0, 0) to (len_x-1, len_y-1);
+ *   entries beyond are not written.
+ * set_zero_fill_dist: sum [B] = sum over t < max(len_x, len_y) of ||x_t - y_t||, a side read as zeros at and beyond its length.
+ * set_mcd_finish: frames [B] int64 = steps[b] (steps int32, from set_dtw) or, with steps == NULL, max(len_1, len_2);
+ *   mcd = num / frames and penalty = 2 - (len_1 + len_2) / frames, each computed in double and rounded once. */
+int set_mfcc(const float *mel, const int64_t *lengths, const float *table, float *out, int32_t B, int32_t T, int32_t M, int32_t K,
+             int32_t take_log, void *stream);
+int set_dtw(const float *x, const float *y, const int64_t *len_x, const int64_t *len_y, float *dist, int32_t *steps, uint8_t *dir, int32_t B,
+            int32_t Tx, int32_t Ty, int32_t K, void *stream);
+int set_dtw_path(const uint8_t *dir, const int64_t *len_x, const int64_t *len_y, const int32_t *steps, int32_t *path, int32_t B, int32_t Tx,
+                 int32_t Ty, void *stream);
+int set_zero_fill_dist(const float *x, const float *y, const int64_t *len_x, const int64_t *len_y, float *sum, int32_t B, int32_t Tx,
+                       int32_t Ty, int32_t K, void *stream);
+int set_mcd_finish(const float *num, const int32_t *steps, const int64_t *len_1, const int64_t *len_2, float *mcd, float *penalty,
+                   int64_t *frames, int32_t B, int32_t T1, int32_t T2, void *stream);
+
 /* MFMA fragment-layout self test: runs a 32x32xK product through v_mfma_f32_32x32x2_f32 with the layout
  * this library assumes and returns the max abs error vs an in-kernel scalar reference via *max_err (HOST).
  * Synchronises.  Used by tests to pin the hardware layout assumption. */

@@ -1,0 +1,138 @@
+"""Mel-cepstral distortion on the GPU (csrc/mcd.hip): mel -> MFCC -> exact DTW or zero fill -> (mcd, penalty, frames) per pair.
+
+After the reference's utils/eval/mcd.py `get_metrics_mels`, term by term:
+
+    mfcc      `get_mfccs_of_mel_spectogram`: librosa.feature.mfcc(S=., n_mfcc=K+1, norm=None, dct_type=2, lifter=0)[1:] / 2.  The factor 2
+              of the unnormalised DCT-II and the /2 cancel: c_k = sum_n x_n cos(pi k (2n+1) / (2M)), k = 1..K.
+    dtw       utils/metrics/dtw.py `accelerated_dtw(x, y, 'euclidean', warp=1)`: the exact dynamic time warping, ties to the first of
+              (diagonal, i-1, j-1) as `_traceback`'s argmin takes them.
+    mel_mcd   `get_metrics_mels`.  use_dtw: mcd = dist / steps, frames = steps.  Otherwise the shorter input is zero-filled:
+              mcd = sum ||.|| / max(len), frames = max(len).  penalty = 2 - (len_1 + len_2) / frames in both.
+    wav_mcd   melspec.LogMel(hparams, "librosa") on both waveforms, then mel_mcd.
+
+Two things are NOT what a run of the reference's file gives:
+  * The reference calls `fastdtw` (radius 1), an APPROXIMATION of DTW (and not a dependency here).  This module computes the exact DTW that
+    the reference's own utils/metrics/dtw.py defines, so its `dist` is <= fastdtw's, and the two are equal whenever fastdtw finds the optimum.
+  * eval/mcd.py's wav-level variant (HTK filterbank, orthonormal DCT of dB power, 34 coefficients) is not built.
+
+Mels are [B, T, M], the package's layout; the reference's single-pair (k, n) = [M, T] layout is one `transpose` away.  Everything is a
+kernel of libset_amd.so: CPU tensors are refused, there is no eager fallback.  The only host work is the DCT table (float64, once per
+(K, M) and device) and the check of lengths that arrive as host values.
+"""
+import numpy as np
+import torch
+
+from . import ops
+
+K_MAX, M_MAX = 64, 96
+_TABLES = {}  # (K, M, device) -> the DCT table on that device
+
+
+def dct_table(n_mfcc, n_mels):
+    """float32 [K, M]: cos(pi k (2n+1) / (2M)) for k = 1..K, each rounded once from float64; the angle is reduced exactly in integers,
+    (k (2n+1)) mod 4M, as melspec.dft_table does."""
+    k = np.arange(1, n_mfcc + 1, dtype=np.int64)[:, None]
+    n = np.arange(n_mels, dtype=np.int64)[None, :]
+    ang = 2.0 * np.pi * ((k * (2 * n + 1)) % (4 * n_mels)).astype(np.float64) / (4 * n_mels)
+    return np.cos(ang).astype(np.float32)
+
+
+def _table(K, M, device):
+    key = (K, M, device)
+    if key not in _TABLES:
+        _TABLES[key] = torch.from_numpy(dct_table(K, M)).to(device)
+    return _TABLES[key]
+
+
+def _lengths(lengths, B, T, device, name, lo=1):
+    """int64 [B] on `device`, or None.  Host values (list, array, CPU tensor) are checked against [lo, T] here; a device tensor is passed
+    through without a host sync, and the kernels read each value clamped into that range."""
+    if lengths is None:
+        return None
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype != torch.int64 or lengths.shape != (B,):
+            raise ValueError("%s must be int64 [%d], got %s %s" % (name, B, lengths.dtype, tuple(lengths.shape)))
+        return lengths.contiguous()
+    host = np.asarray(lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths).astype(np.int64).reshape(-1)
+    if host.shape[0] != B or host.min() < lo or host.max() > T:
+        raise ValueError("%s must be %d values in [%d, %d], got %s" % (name, B, lo, T, host.tolist()))
+    return torch.from_numpy(host).to(device)
+
+
+def mfcc(mel, lengths=None, n_mfcc=39, take_log=False):
+    """mel [B, T, M] (or [T, M]) -> MFCC 1..n_mfcc [B, T, n_mfcc]; x = mel, or log10(mel) with take_log.  Rows t >= lengths[b] are +0.0.
+    n_mfcc <= 64, M <= 96."""
+    ops._f(mel, "mel")
+    single = mel.dim() == 2
+    if single:
+        mel = mel[None]
+    if mel.dim() != 3:
+        raise ValueError("mel must be [B, T, M] or [T, M], got %s" % (tuple(mel.shape),))
+    B, T, M = mel.shape
+    n_mfcc = int(n_mfcc)
+    if not 1 <= n_mfcc <= K_MAX or not 1 <= M <= M_MAX:
+        raise ValueError("mfcc is built for 1 <= n_mfcc <= %d and n_mels <= %d, got n_mfcc = %d, n_mels = %d" % (K_MAX, M_MAX, n_mfcc, M))
+    out = ops.mfcc(mel, _table(n_mfcc, M, mel.device), _lengths(lengths, B, T, mel.device, "lengths", lo=0), take_log)
+    return out[0] if single else out
+
+
+def dtw(x, y, len_x=None, len_y=None, return_path=False, *, warp=1, w=float("inf"), s=1.0):
+    """Exact DTW of x [B, Tx, K] and y [B, Ty, K] (or [Tx, K] and [Ty, K]: one pair) under the euclidean cost ->
+    (dist [B] fp32, steps [B] int32), with return_path also (path [B, Tx+Ty-1, 2] int32, count [B] int32): row b's path is
+    path[b, :count[b]], from (0, 0) to (len_x-1, len_y-1); entries beyond are zero.  `steps` (= count) is the path's length, carried forward
+    with D, so no traceback runs unless the path is asked for.  Only warp=1, w=inf, s=1.0 are built.  K <= 64, Ty <= 8192."""
+    if warp != 1 or w != float("inf") or s != 1.0:
+        raise NotImplementedError("dtw is built for warp=1, w=inf, s=1.0 only, got warp=%r, w=%r, s=%r" % (warp, w, s))
+    ops._f(x, "x"), ops._f(y, "y")
+    single = x.dim() == 2 and y.dim() == 2
+    if single:
+        x, y = x[None], y[None]
+    if x.dim() != 3 or y.dim() != 3 or x.shape[0] != y.shape[0]:
+        raise ValueError("x and y must be [B, Tx, K] and [B, Ty, K] (or [Tx, K] and [Ty, K]), got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+    if x.shape[2] != y.shape[2]:
+        raise ValueError("the number of coefficients per frame has to be the same for both inputs, got %d and %d" % (x.shape[2], y.shape[2]))
+    B, Tx, K = x.shape
+    Ty = y.shape[1]
+    if K > K_MAX:
+        raise ValueError("dtw is built for K <= %d, got %d" % (K_MAX, K))
+    len_x, len_y = _lengths(len_x, B, Tx, x.device, "len_x"), _lengths(len_y, B, Ty, x.device, "len_y")
+    if not return_path:
+        dist, steps = ops.dtw(x, y, len_x, len_y)
+        return (dist[0], steps[0]) if single else (dist, steps)
+    dir_ = torch.empty(B, Tx, Ty, dtype=torch.uint8, device=x.device)
+    dist, steps = ops.dtw(x, y, len_x, len_y, dir=dir_)
+    path = ops.dtw_path(dir_, steps, len_x, len_y, path=torch.zeros(B, Tx + Ty - 1, 2, dtype=torch.int32, device=x.device))
+    return (dist[0], steps[0], path[0], steps[0]) if single else (dist, steps, path, steps)
+
+
+def mel_mcd(mel_1, mel_2, len_1=None, len_2=None, *, n_mfcc=39, take_log=False, use_dtw=False):
+    """`get_metrics_mels` for a batch: mel_1 [B, T1, M], mel_2 [B, T2, M] (or one pair [T1, M], [T2, M]; the reference's (k, n) arrays are
+    `.T` of these) with frame counts len_1 / len_2 -> (mcd [B] fp32, penalty [B] fp32, frames [B] int64), all on the device; nothing is
+    synchronised or copied to the host.  take_log=False when log10 has already been applied, as for the mels of this package."""
+    ops._f(mel_1, "mel_1"), ops._f(mel_2, "mel_2")
+    single = mel_1.dim() == 2 and mel_2.dim() == 2
+    if single:
+        mel_1, mel_2 = mel_1[None], mel_2[None]
+    if mel_1.dim() != 3 or mel_2.dim() != 3 or mel_1.shape[0] != mel_2.shape[0]:
+        raise ValueError("mel_1 and mel_2 must be [B, T1, M] and [B, T2, M], got %s and %s" % (tuple(mel_1.shape), tuple(mel_2.shape)))
+    if mel_1.shape[2] != mel_2.shape[2]:
+        raise ValueError("the number of mel bands has to be equal, got %d and %d" % (mel_1.shape[2], mel_2.shape[2]))
+    B, T1, _ = mel_1.shape
+    T2 = mel_2.shape[1]
+    len_1, len_2 = _lengths(len_1, B, T1, mel_1.device, "len_1"), _lengths(len_2, B, T2, mel_1.device, "len_2")
+    c1, c2 = mfcc(mel_1, len_1, n_mfcc, take_log), mfcc(mel_2, len_2, n_mfcc, take_log)
+    if use_dtw:
+        num, steps = ops.dtw(c1, c2, len_1, len_2)
+    else:
+        num, steps = ops.zero_fill_dist(c1, c2, len_1, len_2), None
+    out = ops.mcd_finish(num, steps, len_1, len_2, T1, T2)
+    return tuple(o[0] for o in out) if single else out
+
+
+def wav_mcd(wav_1, wav_2, hparams, len_1=None, len_2=None, **kw):
+    """melspec.LogMel(hparams, "librosa") on both waveforms ([B, N] or [N]; len_1 / len_2 in samples), then mel_mcd(**kw)."""
+    from .melspec import LogMel
+    fe = LogMel(hparams, "librosa")
+    mel_1, fr_1 = (fe(wav_1), None) if len_1 is None else fe(wav_1, len_1)
+    mel_2, fr_2 = (fe(wav_2), None) if len_2 is None else fe(wav_2, len_2)
+    return mel_mcd(mel_1, mel_2, fr_1, fr_2, **kw)

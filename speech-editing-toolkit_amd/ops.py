@@ -591,6 +591,94 @@ def log_mel(wav, table, basis, lengths=None, *, n_fft, hop, n_mels, bin_lo, nbin
     return mel
 
 
+def _len_arg(lengths, B, name):
+    _i(lengths, name)
+    if lengths is not None and lengths.shape != (B,):
+        raise ValueError("%s must be [%d], got %s" % (name, B, tuple(lengths.shape)))
+
+
+def _out_arg(t, shape, dtype, ref, name):
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=ref.device)
+    _chk(t, dtype, name)
+    if tuple(t.shape) != tuple(shape) or t.device != ref.device:
+        raise ValueError("%s must be %s on %s, got %s on %s" % (name, tuple(shape), ref.device, tuple(t.shape), t.device))
+    return t
+
+
+def mfcc(mel, table, lengths=None, take_log=False, out=None):
+    """set_mfcc: mel [B,T,M] -> [B,T,K] against the DCT-II table [K,M] (metrics.dct_table); rows at or beyond `lengths` are +0.0."""
+    _f(mel, "mel"), _f(table, "table")
+    if mel.dim() != 3 or table.dim() != 2 or table.shape[1] != mel.shape[2]:
+        raise ValueError("mfcc: mel must be [B,T,M] and table [K,M], got %s and %s" % (tuple(mel.shape), tuple(table.shape)))
+    B, T, M = mel.shape
+    K = table.shape[0]
+    _len_arg(lengths, B, "lengths")
+    out = _out_arg(out, (B, T, K), torch.float32, mel, "out")
+    check(_lib.lib().set_mfcc(_p(mel), _p(lengths), _p(table), _p(out), B, T, M, K, int(bool(take_log)), _stream()), "set_mfcc")
+    return out
+
+
+def _pair_args(x, y, len_x, len_y, what):
+    _f(x, "x"), _f(y, "y")
+    if x.dim() != 3 or y.dim() != 3 or x.shape[0] != y.shape[0]:
+        raise ValueError("%s: x and y must be [B,Tx,K] and [B,Ty,K], got %s and %s" % (what, tuple(x.shape), tuple(y.shape)))
+    if x.shape[2] != y.shape[2]:
+        raise ValueError("%s: x has %d coefficients per frame, y has %d" % (what, x.shape[2], y.shape[2]))
+    if y.device != x.device:
+        raise ValueError("%s: x and y must be on one device" % what)
+    _len_arg(len_x, x.shape[0], "len_x"), _len_arg(len_y, x.shape[0], "len_y")
+    return x.shape[0], x.shape[1], y.shape[1], x.shape[2]
+
+
+def dtw(x, y, len_x=None, len_y=None, dist=None, steps=None, dir=None):
+    """set_dtw: the exact DTW of x [B,Tx,K] and y [B,Ty,K] under the euclidean cost -> (dist [B] fp32, steps [B] int32).  `dir`
+    ([B,Tx,Ty] uint8, optional) receives the chosen predecessor of every cell inside [0, len_x) x [0, len_y) and is left as it was
+    elsewhere.  `dist` / `steps`: optional output tensors."""
+    B, Tx, Ty, K = _pair_args(x, y, len_x, len_y, "dtw")
+    dist = _out_arg(dist, (B,), torch.float32, x, "dist")
+    steps = _out_arg(steps, (B,), torch.int32, x, "steps")
+    if dir is not None:
+        _out_arg(dir, (B, Tx, Ty), torch.uint8, x, "dir")
+    check(_lib.lib().set_dtw(_p(x), _p(y), _p(len_x), _p(len_y), _p(dist), _p(steps), _p(dir), B, Tx, Ty, K, _stream()), "set_dtw")
+    return dist, steps
+
+
+def dtw_path(dir, steps, len_x=None, len_y=None, path=None):
+    """set_dtw_path: dir [B,Tx,Ty] uint8 and steps [B] int32 (both from `dtw`) -> path [B,Tx+Ty-1,2] int32, entries 0 .. steps[b]-1 of
+    row b in path order from (0, 0); entries beyond are left as they were."""
+    _chk(dir, torch.uint8, "dir"), _chk(steps, torch.int32, "steps")
+    if dir.dim() != 3 or steps.shape != (dir.shape[0],):
+        raise ValueError("dtw_path: dir must be [B,Tx,Ty] and steps [B], got %s and %s" % (tuple(dir.shape), tuple(steps.shape)))
+    B, Tx, Ty = dir.shape
+    _len_arg(len_x, B, "len_x"), _len_arg(len_y, B, "len_y")
+    path = _out_arg(path, (B, Tx + Ty - 1, 2), torch.int32, dir, "path")
+    check(_lib.lib().set_dtw_path(_p(dir), _p(len_x), _p(len_y), _p(steps), _p(path), B, Tx, Ty, _stream()), "set_dtw_path")
+    return path
+
+
+def zero_fill_dist(x, y, len_x=None, len_y=None):
+    """set_zero_fill_dist: sum over t < max(len_x, len_y) of ||x_t - y_t||, the shorter side read as zeros -> [B] fp32."""
+    B, Tx, Ty, K = _pair_args(x, y, len_x, len_y, "zero_fill_dist")
+    out = torch.empty(B, dtype=torch.float32, device=x.device)
+    check(_lib.lib().set_zero_fill_dist(_p(x), _p(y), _p(len_x), _p(len_y), _p(out), B, Tx, Ty, K, _stream()), "set_zero_fill_dist")
+    return out
+
+
+def mcd_finish(num, steps, len_1, len_2, T1, T2):
+    """set_mcd_finish: (mcd [B] fp32 = num / frames, penalty [B] fp32 = 2 - (len_1 + len_2) / frames, frames [B] int64), frames =
+    `steps` (int32, from `dtw`) or, with steps None, max(len_1, len_2)."""
+    _f(num, "num"), _chk(steps, torch.int32, "steps")
+    B = num.shape[0]
+    _len_arg(len_1, B, "len_1"), _len_arg(len_2, B, "len_2")
+    mcd = torch.empty(B, dtype=torch.float32, device=num.device)
+    penalty = torch.empty(B, dtype=torch.float32, device=num.device)
+    frames = torch.empty(B, dtype=torch.int64, device=num.device)
+    check(_lib.lib().set_mcd_finish(_p(num), _p(steps), _p(len_1), _p(len_2), _p(mcd), _p(penalty), _p(frames), B, int(T1), int(T2),
+                                    _stream()), "set_mcd_finish")
+    return mcd, penalty, frames
+
+
 def preln_self_attn(x, ln, attn, key_padding=None, mask=None, eps=1e-5):
     """Inference form of autograd_ops.preln_self_attn."""
     h = layernorm_ch(x, ln[0], ln[1], eps=eps)
