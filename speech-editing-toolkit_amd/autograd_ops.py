@@ -4,14 +4,13 @@ torch.autograd is used as the tape only: every forward AND backward below is a k
 (include/set_amd.h, "Training" section).  Ops without gradients (masks, integer bookkeeping) are re-exported
 from ops.py unchanged.
 """
-import collections
 import ctypes as C
 import functools
 import os
 
 import torch
 
-from . import _lib, ops
+from . import _lib, leaf_stream, ops
 from ._lib import SetAmdError  # noqa: E402
 from ._lib import ACT, PRO, IMPL_NAIVE, check
 from .ops import _p, _stream, _uniform_stride, ConvWeight
@@ -31,6 +30,9 @@ length_regulate = ops.length_regulate
 L = _lib.lib
 
 
+# --------------------------------------------------------------------------------------------------
+# Gradient targets and step-scoped temporaries: the zero arena, where a parameter gradient goes, the per-stream scratch pools
+# --------------------------------------------------------------------------------------------------
 class _ZeroArena:
     """Zero-initialised gradient temporaries (split-K wgrad targets, bias sums, scatter-add targets) of one training
     step come out of ONE buffer cleared by ONE memset, instead of ~300 separate small fills per step (each a launch
@@ -45,210 +47,6 @@ class _ZeroArena:
 
 _ARENAS = {}        # owner id -> _ZeroArena
 _ACTIVE = [None]    # the arena of the optimisation step in progress (steps do not nest)
-
-# --------------------------------------------------------------------------------------------------
-# Leaf stream: gradient kernels nothing else in the backward pass waits for
-# --------------------------------------------------------------------------------------------------
-# A weight / bias gradient that goes straight into the flat optimizer's .grad (FlatAdamW.sink) is a LEAF of the step's dependency graph: the
-# next reader is the optimizer (or the bucket all-reduce).  On the compute stream these kernels sit in the middle of the critical chain of
-# input-gradient kernels: ~3.8 ms of the 11 ms spec_denoiser bf16 step (three grouped layer weight-gradient GEMMs 2.3 ms, ~35 conditioner
-# weight gradients, ~70 ordered bias / partial reductions), most of it while the chain itself runs 5-40 us kernels on a few dozen workgroups.
-# They are enqueued on a second HIP stream instead, ordered after the compute stream by an event at the point of the call, and the optimizer
-# step / bucket launch waits for that stream (leaf_join / leaf_fence).  Results are unchanged bit for bit: same kernels, same operands, each
-# target written by exactly one stream.  Tensors handed to a leaf kernel stay referenced until the join (their storage must not be reused by
-# the compute stream before the leaf kernel has read it); reduction scratch buffers are per stream.  SET_AMD_LEAF_STREAM=0 switches it off.
-# Host cost per fork: one C call (set_stream_order); torch's Event / Stream / record_stream wrappers cost ~28 us per fork (1.1 ms per step).
-# Operand lifetime (round 6, advisor item): the operands are no longer all held until the end of backward() -- the fp32 DiffNet stack alone kept
-# d_o and dy of 20 layers (2.1 GB at B = 32, T = 800) alive that way, growing with depth.  After every ~SET_AMD_LEAF_MARK_MB (128) MB of newly
-# held operands a marker event is recorded on the leaf stream (set_stream_mark); at the next fork the markers that have completed
-# (set_stream_mark_done, a non-blocking query) release everything held before them: those kernels have RUN, so whoever gets the storage
-# next cannot race them.  Above SET_AMD_LEAF_KEEP_MB (8192; 0 = no accounting) MB of held operand STORAGE (views of one saved buffer count
-# once) the compute stream is made to wait for the leaf stream (an early leaf_join) -- the bound, sized for a 288 GB part; not the normal
-# path at the benchmark shapes: every early join gives up overlap (a first accounting that counted every view -- 18 GB "held" in the fp32
-# step -- joined early and cost it 0.9 ms: 31.9 against 30.9 ms, profiles/r06_leaf_accounting_ab.log).  Measured (profiles/r06_leaf_operands.log): the lowest-priority leaf stream runs late, so markers rarely
-# complete inside a backward pass -- it is the cap that bounds the memory; with a 64 MB cap the step joins 26 times and stays bit-identical.
-_LEAF = {}  # device index -> {"stream" (torch object, kept alive), "raw" (handle), "dirty", "keep" (operands of queued leaf kernels), ...}
-_LEAF_STATS = {"max_keep_bytes": 0, "released_by_marker": 0, "early_joins": 0}
-
-
-def _mb_env(name, default):
-    try:
-        return max(0, int(os.environ.get(name, default))) << 20
-    except ValueError:
-        return int(default) << 20
-
-
-def _storages(obj, out):
-    """(storage address, storage bytes) of every tensor in obj (tuples / lists nested): operands are often VIEWS of one saved buffer
-    (every layer's slice of the [L, B, 512, T] tensors of the fused stack) -- counting numel per view made the fp32 step look like
-    18 GB of held operands and join early for nothing (profiles/r06_leaf_accounting_ab.log)."""
-    if isinstance(obj, torch.Tensor):
-        s_ = obj.untyped_storage()
-        out.append((s_.data_ptr(), s_.nbytes()))
-    elif isinstance(obj, (tuple, list)):
-        for o in obj:
-            _storages(o, out)
-
-
-def _leaf_hold(st, obj):
-    keys = None
-    if st["cap_bytes"]:  # SET_AMD_LEAF_KEEP_MB=0: no accounting (operands held until the join, as in round 5)
-        keys, stor = [], st["stor"]
-        _storages(obj, keys)
-        for k, n in keys:
-            ent = stor.get(k)
-            if ent is None:
-                stor[k] = [1, n]
-                st["bytes"] += n
-                st["unmarked"] += n
-            else:
-                ent[0] += 1
-    st["keep"].append((obj, keys))
-    st["count"] += 1
-    if st["bytes"] > _LEAF_STATS["max_keep_bytes"]:
-        _LEAF_STATS["max_keep_bytes"] = st["bytes"]
-
-
-def _leaf_drop(st, keys):
-    if keys:
-        stor = st["stor"]
-        for k, n in keys:
-            ent = stor.get(k)
-            if ent is not None:
-                ent[0] -= 1
-                if ent[0] <= 0:
-                    del stor[k]
-                    st["bytes"] -= n
-
-
-def _leaf_release_all(st):
-    st["keep"].clear()
-    st["marks"].clear()
-    st["stor"].clear()
-    st["base"], st["bytes"], st["unmarked"] = st["count"], 0, 0
-
-
-def _leaf_poll(st):
-    """Release the operands whose leaf kernels have finished (markers that completed); non-blocking."""
-    marks = st["marks"]
-    while marks and L().set_stream_mark_done(marks[0][0]) == 1:
-        _, upto = marks.popleft()
-        keep = st["keep"]
-        while st["base"] < upto:
-            _, keys = keep.popleft()
-            _leaf_drop(st, keys)
-            st["base"] += 1
-            _LEAF_STATS["released_by_marker"] += 1
-
-
-def _leaf_mark(st):
-    """After the kernels of a fork have been enqueued: a marker once enough new operands are held and a slot of the device's ring is free."""
-    if st["unmarked"] < st["mark_bytes"] or len(st["marks"]) >= 8:
-        return
-    busy = {m[0] for m in st["marks"]}
-    slot = next(s for s in range(8 * (st["idx"] % 8), 8 * (st["idx"] % 8) + 8) if s not in busy)
-    check(L().set_stream_mark(st["raw"], slot, st["idx"]), "set_stream_mark")
-    st["marks"].append((slot, st["count"]))
-    st["unmarked"] = 0
-
-
-def leaf_stats(reset=False):
-    """{"max_keep_bytes", "released_by_marker", "early_joins"} since the last reset (tests / probes)."""
-    out = dict(_LEAF_STATS)
-    if reset:
-        for k in _LEAF_STATS:
-            _LEAF_STATS[k] = 0
-    return out
-
-
-def leaf_enabled():
-    return os.environ.get("SET_AMD_LEAF_STREAM", "1") != "0"
-
-
-def _leaf_state(dev):
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    st = _LEAF.get(idx)
-    if st is None:
-        # lowest priority: its chip-filling GEMMs yield workgroup slots to the compute stream's short kernels (a default-priority stream
-        # measured the same step time, profiles/r05_training_ab.log; one form kept)
-        raw = C.c_void_p()
-        with torch.cuda.device(idx):
-            check(L().set_stream_create_low_priority(C.byref(raw)), "set_stream_create_low_priority")
-        stream = torch.cuda.ExternalStream(raw.value, device=torch.device("cuda", idx))
-        st = _LEAF[idx] = {"stream": stream, "raw": raw, "dirty": False, "keep": collections.deque(), "idx": idx,
-                           "marks": collections.deque(), "stor": {}, "count": 0, "base": 0, "bytes": 0, "unmarked": 0,
-                           "mark_bytes": _mb_env("SET_AMD_LEAF_MARK_MB", 128), "cap_bytes": _mb_env("SET_AMD_LEAF_KEEP_MB", 8192)}
-    return st
-
-
-def _order(st, fork):
-    """fork: the leaf stream waits for the current stream; else (join) the current stream waits for the leaf stream: one C call on a cached
-    event (torch's Event / Stream.wait_event / record_stream wrappers cost ~28 us per fork)."""
-    if fork:
-        check(L().set_stream_order(_stream(), st["raw"], 2 * st["idx"]), "set_stream_order")
-    else:
-        check(L().set_stream_order(st["raw"], _stream(), 2 * st["idx"] + 1), "set_stream_order")
-
-
-class leaf_work:
-    """with leaf_work(device, use, *tensors) as on_leaf: kernels launched inside (ops._stream()) go to the device's leaf stream, ordered after
-    everything enqueued on the current stream so far, when `use` holds.  `tensors`: the operands; they are kept referenced until the
-    compute stream has been made to wait for the leaf stream (leaf_join), so the allocator cannot hand their storage to a compute-stream
-    kernel that might run before the leaf kernel has read it.  Nothing may be ALLOCATED inside (torch's current stream is unchanged)."""
-
-    def __init__(self, dev, use, *tensors):
-        self.on = bool(use) and dev.type == "cuda" and leaf_enabled() and getattr(ops._STREAM_TLS, "leaf", None) is None
-        self.dev, self.tensors = dev, tensors
-
-    def __enter__(self):
-        if not self.on:
-            return False
-        st = _leaf_state(self.dev)
-        if st["marks"]:
-            _leaf_poll(st)
-        if st["cap_bytes"] and st["bytes"] > st["cap_bytes"]:  # the bound: the compute stream waits for the leaf stream, everything held so far is released
-            _order(st, False)
-            _leaf_release_all(st)
-            _LEAF_STATS["early_joins"] += 1
-        _order(st, True)
-        _leaf_hold(st, self.tensors)
-        ops._STREAM_TLS.leaf = st["raw"]
-        self._st = st
-        if not st["dirty"]:
-            st["dirty"] = True
-            try:  # the stream that ran backward() waits for the leaf stream when the pass is over: callers may read .grad right away
-                torch.autograd.Variable._execution_engine.queue_callback(leaf_join)
-            except RuntimeError:
-                pass  # not inside a backward pass (a test calling a backward function by hand): FlatAdamW.step() / abort_step() join
-        return True
-
-    def __exit__(self, *exc):
-        if self.on:
-            ops._STREAM_TLS.leaf = None
-            if exc[0] is None:
-                _leaf_mark(self._st)
-        return False
-
-
-def leaf_join():
-    """The current stream waits for everything enqueued on the leaf streams (before the optimizer reads the gradients); the operands
-    held for the leaf kernels are released (whatever reuses their storage is ordered after this point)."""
-    for idx, st in _LEAF.items():
-        if st["dirty"]:
-            with torch.cuda.device(idx):
-                _order(st, False)
-            st["dirty"] = False
-            _leaf_release_all(st)
-
-
-def leaf_fence(dev):
-    """For a consumer that must see BOTH streams' work without stalling the compute stream (a bucket all-reduce launched from an autograd
-    hook): returns the leaf stream (torch object) after making it wait for the current stream, or None when no leaf work is pending."""
-    st = _LEAF.get(dev.index if dev.index is not None else torch.cuda.current_device()) if dev.type == "cuda" else None
-    if st is None or not st["dirty"]:
-        return None
-    _order(st, True)
-    return st["stream"]
 
 
 def zero_arena_begin(device, min_floats=0, owner=None):
@@ -304,30 +102,44 @@ def _tape_tgt(param, dev, cw=None):
     return tmp, tmp
 
 
+def _grouped_targets(params, dev):
+    """Where the gradients of one parameter kind of all layers go: (base pointer, element stride between layers, what to hand to
+    autograd per layer).  In place when the flat optimizer owns every one of them at a uniform stride (its layout is: each layer's
+    parameters contiguous, in the same order); otherwise one zeroed [L, ...] temporary whose slices autograd accumulates."""
+    sinks = [grad_sink(p_) for p_ in params]
+    n = params[0].numel()
+    if all(t is not None for t in sinks):
+        step = _uniform_stride(sinks)
+        if step is not None:
+            return sinks[0].data_ptr(), step, [None] * len(params)
+        # owned, but not at a uniform stride (never seen with FlatAdamW): through autograd like unowned parameters
+    tmp = _gzeros(len(params) * n, dev).view(len(params), *params[0].shape)
+    return tmp.data_ptr(), n, [tmp[l] for l in range(len(params))]
+
+
+def _leaves(dev, rets, *operands):
+    """The block in which the gradient kernels of some parameters are launched: on the leaf stream when EVERY target is written in place
+    (rets: what _tape_tgt / _grouped_targets hand to autograd for them, None for a .grad view) -- the optimizer is then their next
+    reader; else where they stand, on the compute stream.  operands: every tensor those kernels read (leaf_stream.py: held until they
+    have run; one left out is a race between the two streams).  Nothing may be allocated inside."""
+    for r in rets:
+        if r is not None:
+            return leaf_stream.leaf_work(dev, False)
+    return leaf_stream.leaf_work(dev, True, *operands)
+
+
 _DET_SCRATCH = {}  # (device, stream) -> per-block / per-slice partial results of the ordered reductions (reused: stream-ordered)
 _WG_SCRATCH = {}  # (device, stream) -> slice-partial buffer of the ordered weight-gradient path (reused: stream-ordered)
 
 
-def _stream_key(device):
-    """(device, raw handle of the current stream): scratch buffers are reused in stream order, so every stream has its own."""
-    return (device, _stream().value)
-
-
-def _leaf_keep(buf):
-    """A scratch buffer replaced while the leaf stream is the launch stream: kernels queued there may still use it -- held until the join."""
-    if getattr(ops._STREAM_TLS, "leaf", None) is not None:
-        for st in _LEAF.values():
-            if st["dirty"]:
-                _leaf_hold(st, buf)
-
-
 def _scratch(pool, slack, device, n_floats):
-    """The current stream's buffer of `pool`, regrown (x 1.25 + slack) when it is smaller than n_floats."""
-    key = _stream_key(device)
+    """The current stream's buffer of `pool` (reused in stream order, so every stream has its own), regrown (x 1.25 + slack) when it is
+    smaller than n_floats."""
+    key = (device, _stream().value)
     buf = pool.get(key)
     if buf is None or buf.numel() < n_floats:
         if buf is not None:
-            _leaf_keep(buf)
+            leaf_stream.hold_until_join(buf)
         buf = torch.empty(int(n_floats * 1.25) + slack, dtype=torch.float32, device=device)
         pool[key] = buf
     return buf
@@ -337,6 +149,9 @@ _det_scratch = functools.partial(_scratch, _DET_SCRATCH, 4096)  # (device, n_flo
 _wg_scratch = functools.partial(_scratch, _WG_SCRATCH, 1024)
 
 
+# --------------------------------------------------------------------------------------------------
+# The steps most backward nodes share
+# --------------------------------------------------------------------------------------------------
 def channel_sum_(x, out, B, Cc, T):
     """out[c] += sum_{b,t} x[b][c][t], per-slice partials combined in slice order (deterministic)."""
     check(L().set_channel_sum_det(_p(x), _p(out), B, Cc, T, _p(_det_scratch(x.device, 2048 + Cc)), _stream()), "set_channel_sum_det")
@@ -369,19 +184,58 @@ def conv_wgrad_grouped(g, x, chan_add, dw_ptr, groups, g_gs, x_gs, add_gs, dw_gs
           "set_conv1d_wgrad_det_grouped")
 
 
-def _grouped_targets(params, dev):
-    """Where the gradients of one parameter kind of all layers go: (base pointer, element stride between layers, what to hand to
-    autograd per layer).  In place when the flat optimizer owns every one of them at a uniform stride (its layout is: each layer's
-    parameters contiguous, in the same order); otherwise one zeroed [L, ...] temporary whose slices autograd accumulates."""
-    sinks = [grad_sink(p_) for p_ in params]
-    n = params[0].numel()
-    if all(t is not None for t in sinks):
-        step = _uniform_stride(sinks)
-        if step is not None:
-            return sinks[0].data_ptr(), step, [None] * len(params)
-        # owned, but not at a uniform stride (never seen with FlatAdamW): through autograd like unowned parameters
-    tmp = _gzeros(len(params) * n, dev).view(len(params), *params[0].shape)
-    return tmp.data_ptr(), n, [tmp[l] for l in range(len(params))]
+def _conv_leaves(g, x, chan_add, w, b, cw, B, Cin, Cout, K, dil, pad, T, T_in, pro=0, pro_param=0.0):
+    """Weight gradient (w: the parameter; None: not wanted) and bias gradient (b likewise) of the conv y = W (*) P(x + chan_add) + b with
+    output gradient g, as leaves.  cw: the ConvWeight the conv reads w through (plain [Cout,Cin,K] rows, possibly a row slice of a larger
+    parameter), None: the whole parameter.  Returns what to hand to autograd for (w, b): None where the kernel wrote the optimizer's .grad
+    view (autograd still fires the parameter's post-accumulate hook: bucket launch).  g may be the engine's own gradient buffer or a
+    residual's gradient: held as an operand, it is not accumulated into in place (input_buffer.cpp: can_accumulate_inplace)."""
+    dev = g.device
+    t_w, r_w = _tape_tgt(w, dev, cw) if w is not None else (None, None)
+    t_b, r_b = _tape_tgt(b, dev) if b is not None else (None, None)  # (a bias is never a slice: autograd takes a [Cout] gradient for a [Cout] input only)
+    with _leaves(dev, (r_w, r_b), g, x, chan_add):
+        if w is not None:
+            conv_wgrad(g, x, chan_add, t_w, B, Cin, Cout, K, dil, pad, T, T_in, pro, pro_param,
+                       dw_ptr=t_w.data_ptr() + (4 * cw.base if cw is not None else 0))
+        if b is not None:
+            channel_sum_(g, t_b, B, Cout, T)
+    return r_w, r_b
+
+
+def _conv_dgrad(g, cw, dil, pad, T_in, **kw):
+    """Input gradient of a conv = convolution of G with W'[ci][co][tap] = W[co][ci][tap], taps at s + pad - tap*dil."""
+    return ops.conv1d(g, cw.transposed(), None, dil=-dil, pad=-pad, T_iter=T_in, T_out=T_in, **kw)
+
+
+def _masked_grad(dy, mask, alias=True):
+    """dy * mask[b][t]: the gradient through a conv's masked identity epilogue (also the gradient of its residual input).  Without a
+    mask that is dy itself (alias=False: a copy of it)."""
+    if mask is None and alias:
+        return dy
+    g = torch.empty_like(dy)
+    B, Cc, T = dy.shape
+    check(L().set_conv_epilogue_bwd(_p(dy), None, _p(mask), _p(g), B, Cc, T, 0, 1.0, _stream()), "set_conv_epilogue_bwd")
+    return g
+
+
+def _row_sum(x):
+    """[B, C] sums over t of x [B, C, T] (the gradient of a per-channel addend)."""
+    B, Cc, T = x.shape
+    out = torch.empty(B, Cc, dtype=torch.float32, device=x.device)
+    check(L().set_row_sum(_p(x), _p(out), B * Cc, T, 1.0, _stream()), "set_row_sum")
+    return out
+
+
+def _head_views(heads, *packed):
+    """The (q, k, v) MatViews [B * heads, T, d] of one packed [B, 3H, T] tensor (qkv,) or of (q [B, H, T], kv [B, 2H, T])."""
+    MV = ops.MatView
+    if len(packed) == 1:
+        qkv = packed[0]
+        H = qkv.shape[1] // 3
+        return MV.heads(qkv, heads, 0, H), MV.heads(qkv, heads, H, H), MV.heads(qkv, heads, 2 * H, H)
+    q, kv = packed
+    H = q.shape[1]
+    return MV.heads(q, heads), MV.heads(kv, heads, 0, H), MV.heads(kv, heads, H, H)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -414,40 +268,19 @@ class _Conv1dFn(torch.autograd.Function):
                   "set_conv_epilogue_bwd")
         dres = None
         if has_res and ctx.needs_input_grad[4]:
-            if act == "none" and alpha == 1.0:
-                dres = g
-            else:
-                dres = torch.empty_like(dy)
-                check(L().set_conv_epilogue_bwd(_p(dy), None, _p(mask), _p(dres), B, Cout, T, 0, 1.0, _stream()),
-                      "set_conv_epilogue_bwd")
+            dres = g if act == "none" and alpha == 1.0 else _masked_grad(dy, mask, alias=False)
         dx = dadd = None
         if ctx.needs_input_grad[0] or (has_add and ctx.needs_input_grad[3]):
-            # input gradient = convolution of G with W'[ci][co][tap] = W[co][ci][tap], taps at s + pad - tap*dil
-            dx = ops.conv1d(g, cw.transposed(), None, dil=-dil, pad=-pad, alpha=(1.0 / pro_param) if pro == "div" else 1.0,
-                            T_iter=T_in, T_out=T_in, impl=impl)
+            dx = _conv_dgrad(g, cw, dil, pad, T_in, alpha=(1.0 / pro_param) if pro == "div" else 1.0, impl=impl)
             if has_add and ctx.needs_input_grad[3]:
-                dadd = torch.empty(B, Cin, dtype=torch.float32, device=dy.device)
-                check(L().set_row_sum(_p(dx), _p(dadd), B * Cin, T_in, 1.0, _stream()), "set_row_sum")
-        dw = db = r_w = r_b = None
+                dadd = _row_sum(dx)
+        r_w = r_b = None
         want_w, want_b = ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
         if want_w:
-            # plain [Cout,Cin,K] rows, possibly a row slice of a larger parameter (packed q/k/v projections)
             assert cw.stap == 1 and cw.sci == cw.K and cw.sco == cw.Cin * cw.K, "plain conv layout"
-            dw, r_w = _tape_tgt(ctx.wparam, dy.device, cw)
-        if want_b:
-            db, r_b = _tape_tgt(ctx.bparam, dy.device)  # (a bias is never a slice: autograd takes a [Cout] gradient for a [Cout] input only)
-        # gradients that go straight into .grad are leaves of this backward pass (the optimizer is their next reader): leaf stream
-        # (g may be the engine's own gradient buffer dy, or be handed on as the residual's gradient: the autograd engine accumulates a later
-        # arrival into such a buffer IN PLACE only while it holds the last reference to it (input_buffer.cpp: can_accumulate_inplace), and
-        # leaf_work keeps a reference to its operands until the streams are joined -- so nothing rewrites g under the leaf kernels)
-        on_leaf = r_w is None and r_b is None and (want_w or want_b)
-        with leaf_work(dy.device, on_leaf, g, x, chan_add):
-            if want_w:
-                conv_wgrad(g, x, chan_add, dw, B, Cin, Cout, cw.K, dil, pad, T, T_in, PRO[pro], pro_param,
-                           dw_ptr=dw.data_ptr() + 4 * cw.base)
-            if want_b:
-                channel_sum_(g, db, B, Cout, T)
-        # (a gradient written in place is handed on as None; autograd still fires the parameter's post-accumulate hook: bucket launch)
+        if want_w or want_b:
+            r_w, r_b = _conv_leaves(g, x, chan_add, ctx.wparam if want_w else None, ctx.bparam if want_b else None, cw,
+                                    B, Cin, Cout, cw.K, dil, pad, T, T_in, PRO[pro], pro_param)
         return (dx if ctx.needs_input_grad[0] else None, r_w, r_b, dadd, dres, None, None, None, None, None, None, None,
                 None, None, None)
 
@@ -560,32 +393,21 @@ class _PreLnFfnFn(torch.autograd.Function):
         dy = dy.contiguous()
         B, Cc, T = dy.shape
         Cmid, T1, T_in = z.shape[1], z.shape[2], h.shape[2]
-        dev = dy.device
         # ---- second conv (1x1, + residual, * mask): G2 = dy * mask is also the residual's gradient
         if ctx.drop is not None:  # the branch's gradient is keep * G2 / (1 - p) (same Philox keys as the forward)
             g2, gb = torch.empty_like(dy), torch.empty_like(dy)
             p_, seed_, off_ = ctx.drop
             check(L().set_conv_epilogue_bwd_dropout(_p(dy), _p(mask), _p(g2), _p(gb), B, Cc, T, float(p_), int(seed_), int(off_),
                                                     _stream()), "set_conv_epilogue_bwd_dropout")
-        elif mask is None:
-            g2 = gb = dy
         else:
-            g2 = torch.empty_like(dy)
-            check(L().set_conv_epilogue_bwd(_p(dy), None, _p(mask), _p(g2), B, Cc, T, 0, 1.0, _stream()), "set_conv_epilogue_bwd")
-            gb = g2
-        df = ops.conv1d(gb, cw2.transposed(), None, dil=-1, pad=0, T_iter=T1, T_out=T1)
-        (t_w2, r_w2), (t_b2, r_b2) = _tape_tgt(p_w2, dev, cw2), _tape_tgt(p_b2, dev)
-        with leaf_work(dev, r_w2 is None and r_b2 is None, gb, f):  # (gb may be dy itself: kept referenced, see _Conv1dFn.backward)
-            conv_wgrad(gb, f, None, t_w2, B, Cmid, Cc, 1, 1, 0, T, T1, dw_ptr=t_w2.data_ptr() + 4 * cw2.base)
-            channel_sum_(gb, t_b2, B, Cc, T)
+            g2 = gb = _masked_grad(dy, mask)
+        df = _conv_dgrad(gb, cw2, 1, 0, T1)
+        r_w2, r_b2 = _conv_leaves(gb, f, None, p_w2, p_b2, cw2, B, Cmid, Cc, 1, 1, 0, T, T1)
         # ---- activation backward with the first conv's alpha folded in: G1 = gradient of the raw conv + bias
         g1 = torch.empty_like(z)
         check(L().set_act_bwd_scaled(_p(z), _p(df), _p(g1), z.numel(), ACT[act], float(act_param), float(alpha), _stream()), "set_act_bwd_scaled")
-        dh = ops.conv1d(g1, cw1.transposed(), None, dil=-dil, pad=-pad, T_iter=T_in, T_out=T_in)
-        (t_w1, r_w1), (t_b1, r_b1) = _tape_tgt(p_w1, dev, cw1), _tape_tgt(p_b1, dev)
-        with leaf_work(dev, r_w1 is None and r_b1 is None, g1, h):
-            conv_wgrad(g1, h, None, t_w1, B, Cc, Cmid, cw1.K, dil, pad, T1, T_in, dw_ptr=t_w1.data_ptr() + 4 * cw1.base)
-            channel_sum_(g1, t_b1, B, Cmid, T1)
+        dh = _conv_dgrad(g1, cw1, dil, pad, T_in)
+        r_w1, r_b1 = _conv_leaves(g1, h, None, p_w1, p_b1, cw1, B, Cc, Cmid, cw1.K, dil, pad, T1, T_in)
         # ---- LayerNorm backward, then the residual branch joins (same order as the fan-out node of the per-op tape: LN branch + residual)
         dxl, r_g, r_bt = _preln_tail(x, gamma, p_gamma, p_beta, dh, g2, eps)
         return (dxl, r_g, r_bt, r_w1, r_b1, r_w2, r_b2) + (None,) * 11
@@ -660,7 +482,7 @@ class _StutterLossFn(torch.autograd.Function):
         check(L().set_stutter_head_loss_bwd(_p(h), _p(w), _p(logits), _p(labels), _p(stats), _p(g_ce), _p(g_focal), _p(dh), None, None,
                                             _p(part), B, Cc, T, _stream()), "set_stutter_head_loss_bwd")
         (t_w, r_w), (t_b, r_b) = _tape_tgt(p_w, dev), _tape_tgt(p_b, dev)
-        with leaf_work(dev, r_w is None and r_b is None, part):
+        with _leaves(dev, (r_w, r_b), part):
             check(L().set_stutter_head_bwd_reduce(_p(part), _p(t_w), _p(t_b), B, Cc, T, _stream()), "set_stutter_head_bwd_reduce")
         return dh, r_w, r_b, None
 
@@ -695,7 +517,7 @@ class _EmbeddingFn(torch.autograd.Function):
         # ordered scatter (no atomics): gradient rows transposed to [B][T][C], per-(utterance, segment) partial tables
         doutT = ops.bct_to_btc(dout)
         S = L().set_scatter_rows_segments(T)
-        with leaf_work(dout.device, r_tab is None, dout, doutT, idx):
+        with _leaves(dout.device, (r_tab,), dout, doutT, idx):
             check(L().set_scatter_rows_det(_p(idx), _p(doutT), _p(dtab), B, T, Cc, n_rows, float(scale), ctx.padding_idx, 0,
                                            _p(_det_scratch(dout.device, B * S * n_rows * Cc)), _stream()), "set_scatter_rows_det")
         return None, r_tab, (dout if has_base else None), None, None
@@ -743,13 +565,8 @@ class _AddChanMaskFn(torch.autograd.Function):
     def backward(ctx, dout):
         (mask,) = ctx.saved_tensors
         dout = dout.contiguous()
-        B, Cc, T = dout.shape
         dx = ops.add_chan_mask(dout, None, mask) if mask is not None else dout
-        dadd = None
-        if ctx.has_add and ctx.needs_input_grad[1]:
-            dadd = torch.empty(B, Cc, dtype=torch.float32, device=dout.device)
-            check(L().set_row_sum(_p(dx), _p(dadd), B * Cc, T, 1.0, _stream()), "set_row_sum")
-        return dx, dadd, None
+        return dx, (_row_sum(dx) if ctx.has_add and ctx.needs_input_grad[1] else None), None
 
 
 def add_chan_mask(x, add=None, mask=None, out=None):
@@ -943,31 +760,24 @@ class _DiffNetStackFn(torch.autograd.Function):
             dxr = torch.empty_like(dx)
             d_o = torch.empty(B, 2 * C_, T, dtype=torch.float32, device=dev)
             check(L().set_res_skip_bwd(_p(dx), _p(dskip), _p(dxr), _p(d_o), B, C_, T, _stream()), "set_res_skip_bwd")
+            out_p, cond_p, dil_p = layer.output_projection, layer.conditioner_projection, layer.dilated_conv
+            (dw_out, r_wo), (db_out, r_bo), (dw_cond, r_wc), (db, r_bc), (db2, r_bd), (dw_dil, r_wd) = [
+                _tape_tgt(p_, dev) for p_ in (out_p.weight, out_p.bias, cond_p.weight, cond_p.bias, dil_p.bias, dil_p.weight)]
             # output_projection (1x1, 256 -> 512)
-            dw_out, r_wo = _tape_tgt(layer.output_projection.weight, dev)
-            db_out, r_bo = _tape_tgt(layer.output_projection.bias, dev)
-            dw_cond, r_wc = _tape_tgt(layer.conditioner_projection.weight, dev)
-            db, r_bc = _tape_tgt(layer.conditioner_projection.bias, dev)
-            db2, r_bd = _tape_tgt(layer.dilated_conv.bias, dev)
-            dw_dil, r_wd = _tape_tgt(layer.dilated_conv.weight, dev)
-            dz = ops.conv1d(d_o, layer._w_out.transposed(), None, dil=-1, pad=0, T_iter=T, T_out=T)
+            dz = _conv_dgrad(d_o, layer._w_out, 1, 0, T)
             # gate
             dy = torch.empty(B, 2 * C_, T, dtype=torch.float32, device=dev)
             check(L().set_gate_bwd(_p(y_all[l]), _p(dz), _p(dy), B, C_, T, _stream()), "set_gate_bwd")
             # conditioner_projection (1x1, H -> 512): y = ... + W_cond cond + b_cond
             if need_cond:
-                ops.conv1d(dy, layer._w_cond.transposed(), None, dil=-1, pad=0, T_iter=T, T_out=T, out=dcond,
-                           accumulate=True)
+                _conv_dgrad(dy, layer._w_cond, 1, 0, T, out=dcond, accumulate=True)
             # dilated conv (k=3) on x_l + d_l
             dl = dmat[:, l * C_:(l + 1) * C_].contiguous()
-            dxd = ops.conv1d(dy, layer._w_dil.transposed(), None, dil=-dil, pad=-dil, T_iter=T, T_out=T)
-            ddl = torch.empty(B, C_, dtype=torch.float32, device=dev)
-            check(L().set_row_sum(_p(dxd), _p(ddl), B * C_, T, 1.0, _stream()), "set_row_sum")
-            dd[:, l * C_:(l + 1) * C_] = ddl
+            dxd = _conv_dgrad(dy, layer._w_dil, dil, dil, T)
+            dd[:, l * C_:(l + 1) * C_] = _row_sum(dxd)
             dx = ops.sum_div(dxd, dxr)
-            # the layer's six parameter gradients: leaves (leaf stream when they go straight into .grad)
-            in_place = all(r is None for r in (r_wo, r_bo, r_wc, r_bc, r_bd, r_wd))
-            with leaf_work(dev, in_place, d_o, dy, z_all, cond, x_all, dl):
+            # the layer's six parameter gradients: leaves
+            with _leaves(dev, (r_wo, r_bo, r_wc, r_bc, r_bd, r_wd), d_o, dy, z_all, cond, x_all, dl):
                 conv_wgrad(d_o, z_all[l], None, dw_out, B, C_, 2 * C_, 1, 1, 0, T, T)
                 channel_sum_(d_o, db_out, B, 2 * C_, T)
                 conv_wgrad(dy, cond, None, dw_cond, B, H, 2 * C_, 1, 1, 0, T, T)
@@ -1119,8 +929,7 @@ def _bf16_stack_bwd_grouped(a, layers, per, cond, dmat, x_all, y16, z16, dy16_al
     # written straight into .grad (every r_* entry None): leaves of the backward pass -- 2.3 ms of chip-filling GEMMs that run on the
     # leaf stream under the conditioner's backward (hundreds of 5-40 us kernels on a few dozen workgroups each)
     G16, GX16 = _lib.DTYPE_BF16_G16, _lib.DTYPE_BF16_G16_X16
-    in_place = all(r is None for r in r_out + r_c + r_d)
-    with leaf_work(dev, in_place, do16_all, dy16_all, z16, cond, x_all, dl_all):
+    with _leaves(dev, r_out + r_c + r_d, do16_all, dy16_all, z16, cond, x_all, dl_all):
         conv_wgrad_grouped(do16_all, z16, None, p_out, L_, n_act, B * C_ * T, 0, s_out, B, C_, 2 * C_, 1, 1, 0, T, T, GX16)
         conv_wgrad_grouped(dy16_all, cond, None, p_c, L_, n_act, 0, 0, s_c, B, H, 2 * C_, 1, 1, 0, T, T, G16)
         conv_wgrad_grouped(dy16_all, x_all, dl_all, p_d, L_, n_act, B * C_ * T, B * C_, s_d, B, C_, 2 * C_, 3, dil, dil, T, T, G16)
@@ -1202,8 +1011,7 @@ class _StepProjFn(torch.autograd.Function):
         dh = torch.empty_like(h)
         scratch = _det_scratch(dev, L().set_step_proj_bwd_scratch_floats(L_, Cc, N))
         check(L().set_step_proj_bwd_dh(_p(g), _p(ws[0]), ctx.w_ls, _p(dh), _p(scratch), L_, Cc, N, _stream()), "set_step_proj_bwd_dh")
-        sinks = all(r is None for r in r_w) and all(r is None for r in r_b)  # every dW / db goes straight into the flat gradient buffer
-        with leaf_work(dev, sinks, h, g):
+        with _leaves(dev, r_w + r_b, h, g):
             check(L().set_step_proj_bwd_dw(_p(h), _p(g), C.c_void_p(p_w), s_w, C.c_void_p(p_b), s_b, L_, Cc, N, _stream()),
                   "set_step_proj_bwd_dw")
         return (dh, None, None, *r_w, *r_b)
@@ -1247,95 +1055,48 @@ def _attn_bwd(qv, kv, vv, p, do, dqv, dkv, dvv, heads, alpha):
     ops.bmm(MV.scores(ds).t, qv, dkv, alpha=alpha)  # dK = alpha dS^T Q
 
 
-class _SelfAttnFn(torch.autograd.Function):
-    """qkv [B, 3H, T] (packed in_proj output) -> o [B, H, T] (+ p when asked).  Default: the fused kernels -- the scores
-    never reach HBM and the backward recomputes P from the saved log-sum-exp (csrc/attention_fused.hip); SET_AMD_ATTN_FUSED=0:
-    bmm -> softmax -> bmm with the probabilities saved."""
+class _AttnFn(torch.autograd.Function):
+    """packed: (qkv [B, 3H, T],) -- self-attention on a packed in_proj output -- or (q [B, H, T], kv [B, 2H, Tk]) -> o [B, H, T] (+ p when
+    asked); one gradient per packed tensor.  Default: the fused kernels -- the scores never reach HBM and the backward recomputes P from
+    the saved log-sum-exp (csrc/attention_fused.hip); SET_AMD_ATTN_FUSED=0: bmm -> softmax -> bmm with the probabilities saved."""
 
     @staticmethod
-    def forward(ctx, qkv, heads, kpm, fill, alpha, want_p):
-        qkv = qkv.contiguous()
-        H = qkv.shape[1] // 3
-        MV = ops.MatView
-        ctx.cfg = (heads, alpha, kpm, fill)
-        if ops.attention_fused_on(H // heads):
-            o, lse, p = ops.attention_fused(MV.heads(qkv, heads, 0, H), MV.heads(qkv, heads, H, H), MV.heads(qkv, heads, 2 * H, H),
-                                            heads, kpm, fill, alpha, want_p)
-            ctx.fused = True
-            ctx.save_for_backward(qkv, o, lse)
+    def forward(ctx, heads, kpm, fill, alpha, want_p, *packed):
+        packed = tuple(t.contiguous() for t in packed)
+        views = _head_views(heads, *packed)
+        ctx.cfg = (heads, alpha, kpm, fill, len(packed))
+        ctx.fused = ops.attention_fused_on(views[0].cols)  # (head size)
+        if ctx.fused:
+            o, lse, p = ops.attention_fused(*views, heads, kpm, fill, alpha, want_p)
+            ctx.save_for_backward(*packed, o, lse)
         else:
-            o, p = ops.attention_views(MV.heads(qkv, heads, 0, H), MV.heads(qkv, heads, H, H), MV.heads(qkv, heads, 2 * H, H),
-                                       heads, kpm, fill, alpha)
-            ctx.fused = False
-            ctx.save_for_backward(qkv, p)
+            o, p = ops.attention_views(*views, heads, kpm, fill, alpha)
+            ctx.save_for_backward(*packed, p)
         if p is None:
-            p = qkv.new_empty(0)
+            p = packed[0].new_empty(0)
         ctx.mark_non_differentiable(p)
         return o, p
 
     @staticmethod
     def backward(ctx, do, _dp):
-        heads, alpha, kpm, fill = ctx.cfg
-        qkv = ctx.saved_tensors[0]
-        H = qkv.shape[1] // 3
-        MV = ops.MatView
-        d = torch.empty_like(qkv)
-        views = (MV.heads(qkv, heads, 0, H), MV.heads(qkv, heads, H, H), MV.heads(qkv, heads, 2 * H, H))
-        dviews = (MV.heads(d, heads, 0, H), MV.heads(d, heads, H, H), MV.heads(d, heads, 2 * H, H))
+        heads, alpha, kpm, fill, n = ctx.cfg
+        packed, rest = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        grads = tuple(torch.empty_like(t) for t in packed)
+        views, dviews = _head_views(heads, *packed), _head_views(heads, *grads)
         if ctx.fused:
-            _, o, lse = ctx.saved_tensors
-            ops.attention_fused_bwd(*views, o, lse, do.contiguous(), *dviews, heads, kpm, fill, alpha)
+            ops.attention_fused_bwd(*views, *rest, do.contiguous(), *dviews, heads, kpm, fill, alpha)
         else:
-            _attn_bwd(*views, ctx.saved_tensors[1], do.contiguous(), *dviews, heads, alpha)
-        return d, None, None, None, None, None
-
-
-class _CrossAttnFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, kv, heads, kpm, fill, alpha, want_p):
-        q, kv = q.contiguous(), kv.contiguous()
-        H = q.shape[1]
-        MV = ops.MatView
-        ctx.cfg = (heads, alpha, kpm, fill)
-        if ops.attention_fused_on(H // heads):
-            o, lse, p = ops.attention_fused(MV.heads(q, heads), MV.heads(kv, heads, 0, H), MV.heads(kv, heads, H, H), heads, kpm,
-                                            fill, alpha, want_p)
-            ctx.fused = True
-            ctx.save_for_backward(q, kv, o, lse)
-        else:
-            o, p = ops.attention_views(MV.heads(q, heads), MV.heads(kv, heads, 0, H), MV.heads(kv, heads, H, H), heads, kpm,
-                                       fill, alpha)
-            ctx.fused = False
-            ctx.save_for_backward(q, kv, p)
-        if p is None:
-            p = q.new_empty(0)
-        ctx.mark_non_differentiable(p)
-        return o, p
-
-    @staticmethod
-    def backward(ctx, do, _dp):
-        heads, alpha, kpm, fill = ctx.cfg
-        q, kv = ctx.saved_tensors[:2]
-        H = q.shape[1]
-        MV = ops.MatView
-        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        views = (MV.heads(q, heads), MV.heads(kv, heads, 0, H), MV.heads(kv, heads, H, H))
-        dviews = (MV.heads(dq, heads), MV.heads(dkv, heads, 0, H), MV.heads(dkv, heads, H, H))
-        if ctx.fused:
-            o, lse = ctx.saved_tensors[2:]
-            ops.attention_fused_bwd(*views, o, lse, do.contiguous(), *dviews, heads, kpm, fill, alpha)
-        else:
-            _attn_bwd(*views, ctx.saved_tensors[2], do.contiguous(), *dviews, heads, alpha)
-        return dq, dkv, None, None, None, None, None
+            _attn_bwd(*views, rest[0], do.contiguous(), *dviews, heads, alpha)
+        return (None,) * 5 + grads
 
 
 def self_attention(qkv, heads, key_padding_mask=None, fill=float("-inf"), alpha=1.0, want_p=False):
     """(o, p): p is an empty tensor unless want_p (the fused kernels do not materialise the probabilities)."""
-    return _SelfAttnFn.apply(qkv, heads, key_padding_mask, fill, alpha, want_p)
+    return _AttnFn.apply(heads, key_padding_mask, fill, alpha, want_p, qkv)
 
 
 def cross_attention(q, kv, heads, key_padding_mask=None, fill=-1e8, alpha=1.0, want_p=True):
-    return _CrossAttnFn.apply(q, kv, heads, key_padding_mask, fill, alpha, want_p)
+    return _AttnFn.apply(heads, key_padding_mask, fill, alpha, want_p, q, kv)
 
 
 def _preln_tail(x, gamma, p_gamma, p_beta, dh, g2, eps):
@@ -1357,12 +1118,9 @@ class _PreLnSelfAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, w_in, w_out, cw_qkv, cw_out, heads, kpm, fill, alpha, mask, eps):
         x = x.contiguous()
-        H = x.shape[1]
-        MV = ops.MatView
         h = ops.layernorm_ch(x, gamma, beta, None, eps)
         qkv = ops.conv1d(h, cw_qkv)
-        o, lse, _ = ops.attention_fused(MV.heads(qkv, heads, 0, H), MV.heads(qkv, heads, H, H), MV.heads(qkv, heads, 2 * H, H), heads, kpm,
-                                        fill, alpha, False)
+        o, lse, _ = ops.attention_fused(*_head_views(heads, qkv), heads, kpm, fill, alpha, False)
         y = ops.conv1d(o, cw_out, None, res=x, mask=mask)
         ctx.save_for_backward(x, gamma, mask, kpm, h, qkv, o, lse)
         ctx.cfg, ctx.cws, ctx.params = (heads, fill, alpha, eps), (cw_qkv, cw_out), (gamma, beta, w_in, w_out)
@@ -1376,23 +1134,13 @@ class _PreLnSelfAttnFn(torch.autograd.Function):
         p_gamma, p_beta, p_win, p_wout = ctx.params
         dy = dy.contiguous()
         B, H, T = dy.shape
-        dev, MV = dy.device, ops.MatView
-        if mask is None:
-            g2 = dy
-        else:
-            g2 = torch.empty_like(dy)
-            check(L().set_conv_epilogue_bwd(_p(dy), None, _p(mask), _p(g2), B, H, T, 0, 1.0, _stream()), "set_conv_epilogue_bwd")
-        do = ops.conv1d(g2, cw_out.transposed(), None, dil=-1, pad=0, T_iter=T, T_out=T)
-        t_wo, r_wo = _tape_tgt(p_wout, dev)
-        with leaf_work(dev, r_wo is None, g2, o):
-            conv_wgrad(g2, o, None, t_wo, B, H, H, 1, 1, 0, T, T)
+        g2 = _masked_grad(dy, mask)
+        do = _conv_dgrad(g2, cw_out, 1, 0, T)
+        r_wo, _ = _conv_leaves(g2, o, None, p_wout, None, None, B, H, H, 1, 1, 0, T, T)
         dqkv = torch.empty_like(qkv)
-        ops.attention_fused_bwd(MV.heads(qkv, heads, 0, H), MV.heads(qkv, heads, H, H), MV.heads(qkv, heads, 2 * H, H), o, lse, do,
-                                MV.heads(dqkv, heads, 0, H), MV.heads(dqkv, heads, H, H), MV.heads(dqkv, heads, 2 * H, H), heads, kpm, fill, alpha)
-        dh = ops.conv1d(dqkv, cw_qkv.transposed(), None, dil=-1, pad=0, T_iter=T, T_out=T)
-        t_wi, r_wi = _tape_tgt(p_win, dev)
-        with leaf_work(dev, r_wi is None, dqkv, h):
-            conv_wgrad(dqkv, h, None, t_wi, B, H, 3 * H, 1, 1, 0, T, T)
+        ops.attention_fused_bwd(*_head_views(heads, qkv), o, lse, do, *_head_views(heads, dqkv), heads, kpm, fill, alpha)
+        dh = _conv_dgrad(dqkv, cw_qkv, 1, 0, T)
+        r_wi, _ = _conv_leaves(dqkv, h, None, p_win, None, None, B, H, 3 * H, 1, 1, 0, T, T)
         dx, r_g, r_b = _preln_tail(x, gamma, p_gamma, p_beta, dh, g2, eps)
         return (dx, r_g, r_b, r_wi, r_wo) + (None,) * 8
 
@@ -1405,12 +1153,10 @@ class _PreLnCrossAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, enc, gamma, beta, w_in, w_out, cw_q, cw_kv, cw_out, heads, kpm, fill, alpha, want_p, eps):
         x, enc = x.contiguous(), enc.contiguous()
-        H = x.shape[1]
-        MV = ops.MatView
         h = ops.layernorm_ch(x, gamma, beta, None, eps)
         q = ops.conv1d(h, cw_q)
         kv = ops.conv1d(enc, cw_kv)
-        o, lse, p = ops.attention_fused(MV.heads(q, heads), MV.heads(kv, heads, 0, H), MV.heads(kv, heads, H, H), heads, kpm, fill, alpha, want_p)
+        o, lse, p = ops.attention_fused(*_head_views(heads, q, kv), heads, kpm, fill, alpha, want_p)
         y = ops.conv1d(o, cw_out, None, res=x)
         ctx.save_for_backward(x, enc, gamma, kpm, h, q, kv, o, lse)
         ctx.cfg, ctx.cws, ctx.params = (heads, fill, alpha, eps), (cw_q, cw_kv, cw_out), (gamma, beta, w_in, w_out)
@@ -1428,19 +1174,16 @@ class _PreLnCrossAttnFn(torch.autograd.Function):
         g2 = dy.contiguous()
         B, H, T = g2.shape
         Tk = enc.shape[2]
-        dev, MV = g2.device, ops.MatView
-        do = ops.conv1d(g2, cw_out.transposed(), None, dil=-1, pad=0, T_iter=T, T_out=T)
-        t_wo, r_wo = _tape_tgt(p_wout, dev)
-        with leaf_work(dev, r_wo is None, g2, o):
-            conv_wgrad(g2, o, None, t_wo, B, H, H, 1, 1, 0, T, T)
+        dev = g2.device
+        do = _conv_dgrad(g2, cw_out, 1, 0, T)
+        r_wo, _ = _conv_leaves(g2, o, None, p_wout, None, None, B, H, H, 1, 1, 0, T, T)
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-        ops.attention_fused_bwd(MV.heads(q, heads), MV.heads(kv, heads, 0, H), MV.heads(kv, heads, H, H), o, lse, do,
-                                MV.heads(dq, heads), MV.heads(dkv, heads, 0, H), MV.heads(dkv, heads, H, H), heads, kpm, fill, alpha)
-        dh = ops.conv1d(dq, cw_q.transposed(), None, dil=-1, pad=0, T_iter=T, T_out=T)
-        denc = ops.conv1d(dkv, cw_kv.transposed(), None, dil=-1, pad=0, T_iter=Tk, T_out=Tk) if ctx.needs_input_grad[1] else None
+        ops.attention_fused_bwd(*_head_views(heads, q, kv), o, lse, do, *_head_views(heads, dq, dkv), heads, kpm, fill, alpha)
+        dh = _conv_dgrad(dq, cw_q, 1, 0, T)
+        denc = _conv_dgrad(dkv, cw_kv, 1, 0, Tk) if ctx.needs_input_grad[1] else None
         # rows [0, H) of the packed weight from the queries, rows [H, 3H) from the keys / values: together the whole parameter, once
         t_wi, r_wi = _tape_tgt(p_win, dev)
-        with leaf_work(dev, r_wi is None, dq, dkv, h, enc):
+        with _leaves(dev, (r_wi,), dq, dkv, h, enc):
             conv_wgrad(dq, h, None, t_wi, B, H, H, 1, 1, 0, T, T, dw_ptr=t_wi.data_ptr() + 4 * cw_q.base)
             conv_wgrad(dkv, enc, None, t_wi, B, H, 2 * H, 1, 1, 0, Tk, Tk, dw_ptr=t_wi.data_ptr() + 4 * cw_kv.base)
         dx, r_g, r_b = _preln_tail(x, gamma, p_gamma, p_beta, dh, g2, eps)

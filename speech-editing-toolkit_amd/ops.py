@@ -171,7 +171,7 @@ _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 import threading  # noqa: E402
 
-_STREAM_TLS = threading.local()  # .leaf: raw handle of the leaf stream while autograd_ops.leaf_work is open IN THIS THREAD (kernels only)
+_STREAM_TLS = threading.local()  # .leaf: raw handle of the leaf stream while leaf_stream.leaf_work is open IN THIS THREAD (kernels only)
 
 
 def _stream():

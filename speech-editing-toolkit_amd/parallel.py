@@ -7,6 +7,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import leaf_stream
+
 
 def init_from_env(backend=None):
     """Initialise torch.distributed from RANK / WORLD_SIZE / MASTER_* (torchrun).  Returns (rank, world, local_rank)."""
@@ -219,10 +221,9 @@ class GradBucketer:
         s, e = self.buckets[b]
         leaf = None
         if self.flat_g.is_cuda:
-            # gradient kernels of this bucket may still be queued on the leaf stream (autograd_ops.leaf_work): the collective is enqueued
+            # gradient kernels of this bucket may still be queued on the leaf stream (leaf_stream.leaf_work): the collective is enqueued
             # behind BOTH streams -- from the leaf stream, after it has been made to wait for the compute stream -- without stalling backward
-            from . import autograd_ops as A
-            leaf = A.leaf_fence(self.flat_g.device)
+            leaf = leaf_stream.leaf_fence(self.flat_g.device)
         if leaf is not None:
             with torch.cuda.stream(leaf):
                 self._works[b] = dist.all_reduce(self.flat_g[s:e], op=dist.ReduceOp.SUM, async_op=True)

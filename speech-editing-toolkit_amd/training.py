@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import autograd_ops as A
-from . import ops, parallel
+from . import leaf_stream, ops, parallel
 
 
 class FlatAdamW:
@@ -102,7 +102,7 @@ class FlatAdamW:
         """A step that failed between zero_grad() and step(): close the zero arena and leave the "in step" state, so that a
         later backward outside a zero_grad()/step() pair goes through autograd instead of writing into the flat buffer."""
         A.zero_arena_end()
-        A.leaf_join()
+        leaf_stream.leaf_join()
         self.in_step = False
 
     def step(self):
@@ -110,7 +110,7 @@ class FlatAdamW:
         whatever is left goes now) -> clip_grad_norm_(max_norm) + AdamW on the mean gradient, then the warm-up
         schedule (base_task.py:129-137)."""
         A.zero_arena_end()
-        A.leaf_join()  # (normally done already, by the callback at the end of backward())
+        leaf_stream.leaf_join()  # (normally done already, by the callback at the end of backward())
         self.in_step = False
         self._learned = True
         if not self._unused_checked:  # once: a parameter declared unreachable that did receive a gradient would silently diverge across ranks

@@ -662,6 +662,59 @@ def test_tape_tgt_is_the_one_gradient_target_rule():
     assert tgt is ret and not tgt.any() and owner.calls == {id(owned): 1}
 
 
+def test_operand_ledger_counts_storages_once_and_releases_in_order():
+    """leaf_stream.OperandLedger, the host bookkeeping of what the leaf stream's queued kernels still read (no library or GPU call: CPU
+    tensors serve): bytes per distinct storage, a marker due every mark_bytes of newly held storage, release up to a marker's count in
+    FIFO order, release-all, and a cap of 0 meaning "hold, but count nothing"."""
+    import torch
+    from set_amd.leaf_stream import OperandLedger
+    buf = torch.zeros(4, 256)                      # 4096 bytes, one storage
+    other, third = torch.zeros(512), torch.zeros(100)   # 2048 and 400 bytes
+    led = OperandLedger(mark_bytes=4096, cap_bytes=1 << 20)
+    # two views of one storage count its bytes once; nested tuples / lists are walked; None and non-tensors are ignored
+    led.hold((buf[0], None))
+    assert (led.bytes, led.unmarked, led.count, led.base) == (4096, 4096, 1, 0)
+    led.hold([(buf[2:], 3), [other]])
+    assert (led.bytes, led.unmarked, led.count, len(led.entries)) == (4096 + 2048, 4096 + 2048, 2, 2)
+    assert led.peak_bytes == 6144 and not led.over_cap()
+    # a marker is due at mark_bytes of NEW storage, and no longer right after marking (another view of a held storage adds nothing)
+    assert led.mark_due()
+    first = led.mark()
+    assert first == 2 and led.unmarked == 0 and not led.mark_due()
+    led.hold(buf[1])
+    assert not led.mark_due() and (led.bytes, led.count) == (6144, 3)
+    led.hold(third)
+    assert led.unmarked == 400 and not led.mark_due() and led.peak_bytes == 6544
+    # releasing up to the marker's count pops exactly the entries queued before it, oldest first; buf stays counted while entry 3 views it
+    assert led.release_upto(first) == 2
+    assert (led.base, len(led.entries), led.bytes) == (2, 2, 4096 + 400) and led.entries[0][0] is not None
+    assert led.entries[0][0].data_ptr() == buf[1].data_ptr()
+    assert led.release_upto(first) == 0            # nothing twice
+    assert led.release_upto(3) == 1 and led.bytes == 400 and set(led.storages) == {third.untyped_storage().data_ptr()}
+    # release-all leaves the counts consistent: a later marker covers only what is held after it
+    led.hold(other)
+    led.release_all()
+    assert (led.base, led.count, led.bytes, led.unmarked, len(led.entries), led.storages) == (5, 5, 0, 0, 0, {})
+    led.hold(buf)
+    assert led.mark_due() and led.mark() == 6 and led.release_upto(6) == 1 and (led.base, led.bytes) == (6, 0)
+    assert led.peak_bytes == 6544                  # the peak follows the held bytes and survives the releases
+    # over the cap: strictly more than cap_bytes of held storage
+    tight = OperandLedger(mark_bytes=1, cap_bytes=4096)
+    tight.hold(buf)
+    assert not tight.over_cap()
+    tight.hold(third)
+    assert tight.over_cap() and tight.peak_bytes == 4496
+    # cap 0: no byte accounting (nothing is ever over the cap, the peak stays 0), entries are still held and released by count
+    off = OperandLedger(mark_bytes=4096, cap_bytes=0)
+    off.hold((buf, other))
+    off.hold(third)
+    assert (off.bytes, off.unmarked, off.peak_bytes, off.storages) == (0, 0, 0, {}) and not off.over_cap() and not off.mark_due()
+    assert off.count == 2 and off.entries[0][0][0] is buf
+    assert off.release_upto(1) == 1 and len(off.entries) == 1 and off.entries[0][0] is third
+    off.release_all()
+    assert (off.base, off.count, len(off.entries)) == (2, 2, 0)
+
+
 def test_diffnet_stack_refuses_a_bare_tuple():
     """ops.diffnet_stack takes its weight images as an ops.StackImages (fields by name): a tuple in the old positional order is a TypeError
     before anything is launched (refused on the host: no device needed)."""

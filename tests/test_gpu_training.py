@@ -735,12 +735,12 @@ def test_preln_ffn_node_equals_the_per_op_tape(dev, dtype, shape, monkeypatch):
 @pytest.mark.parametrize("dtype,size", [("f32", "tiny"), ("bf16", "tiny"), ("bf16", "full")])
 def test_leaf_stream_updates_equal_the_single_stream_updates_bit_for_bit(dev, dtype, size, monkeypatch):
     """Round 5: weight / bias gradients that go straight into the flat optimizer's .grad run on a second HIP stream beside the
-    chain of input-gradient kernels (autograd_ops.leaf_work), joined at the end of backward().  Same kernels, same operands, every target
+    chain of input-gradient kernels (leaf_stream.leaf_work), joined at the end of backward().  Same kernels, same operands, every target
     written by one stream: two identical replicas -- one with the leaf stream, one with SET_AMD_LEAF_STREAM=0 -- must hold bit-identical
     losses, parameters and Adam moments after every one of six updates (dropout on, different batches and seeds, warm-up moving the lr).
     `full` is the benchmark shape (B = 32, T = 800, 20 layers: the grouped layer weight gradients really do overlap the conditioner's
     backward there); a race between the streams, or an operand freed under a leaf kernel, would show up as a difference."""
-    from set_amd import autograd_ops as A, ops
+    from set_amd import leaf_stream, ops
     from set_amd.synthetic import synthetic_inputs
     from set_amd.training import FlatAdamW
     ops.set_compute_dtype(dtype)
@@ -764,7 +764,7 @@ def test_leaf_stream_updates_equal_the_single_stream_updates_bit_for_bit(dev, dt
             sample = {k: v.to(dev) for k, v in sample.items()}
             monkeypatch.setenv("SET_AMD_LEAF_STREAM", "1")
             tot_a, parts_a, _ = ta.training_step(sample, oa, t=t, seed=500 + 13 * it)
-            used_leaf = any(st["stream"] is not None for st in A._LEAF.values())
+            used_leaf = any(st.stream is not None for st in leaf_stream._STREAMS.values())
             monkeypatch.setenv("SET_AMD_LEAF_STREAM", "0")
             tot_b, parts_b, _ = tb.training_step(sample, ob, t=t, seed=500 + 13 * it)
             torch.cuda.synchronize()
@@ -783,7 +783,7 @@ def test_leaf_stream_operands_are_released_as_their_kernels_finish(dev):
     held bytes stays under the cap without an early join; (b) budgets of 1 MB / 64 MB -- early joins happen and the peak drops to the cap plus
     the largest single set of operands (the fused stack's, ~1.1 GB); (c) a replica without the leaf stream: losses, parameters and Adam
     moments bit-identical after each of three updates in all three."""
-    from set_amd import autograd_ops as A
+    from set_amd import leaf_stream
     from set_amd.synthetic import synthetic_inputs
     from set_amd.training import FlatAdamW
     reps = []
@@ -803,12 +803,12 @@ def test_leaf_stream_operands_are_released_as_their_kernels_finish(dev):
             outs = []
             for name, (task, opt) in zip(("default", "tight", "single"), reps):
                 os.environ["SET_AMD_LEAF_STREAM"] = "0" if name == "single" else "1"
-                for st in A._LEAF.values():
-                    st["mark_bytes"], st["cap_bytes"] = ((1 << 20, 64 << 20) if name == "tight" else (128 << 20, 8192 << 20))
-                A.leaf_stats(reset=True)
+                for st in leaf_stream._STREAMS.values():
+                    st.ledger.mark_bytes, st.ledger.cap_bytes = ((1 << 20, 64 << 20) if name == "tight" else (128 << 20, 8192 << 20))
+                leaf_stream.leaf_stats(reset=True)
                 tot, parts, _ = task.training_step(sample, opt, t=t, seed=900 + it)
                 torch.cuda.synchronize()
-                stats[name] = A.leaf_stats()
+                stats[name] = leaf_stream.leaf_stats()
                 outs.append((tot, opt))
             for tot, opt in outs[1:]:
                 assert torch.equal(tot, outs[0][0]), it
@@ -819,8 +819,8 @@ def test_leaf_stream_operands_are_released_as_their_kernels_finish(dev):
         assert stats["tight"]["early_joins"] > 0 and stats["tight"]["max_keep_bytes"] < stats["default"]["max_keep_bytes"]
         assert stats["tight"]["max_keep_bytes"] <= (64 << 20) + (1280 << 20)
     finally:
-        for st in A._LEAF.values():
-            st["mark_bytes"], st["cap_bytes"] = 128 << 20, 8192 << 20
+        for st in leaf_stream._STREAMS.values():
+            st.ledger.mark_bytes, st.ledger.cap_bytes = 128 << 20, 8192 << 20
         if old_env is None:
             os.environ.pop("SET_AMD_LEAF_STREAM", None)
         else:

@@ -1,4 +1,4 @@
-"""Soak of the training path's leaf stream (autograd_ops.leaf_work): two identical replicas at the benchmark shape, one with the leaf stream,
+"""Soak of the training path's leaf stream (leaf_stream.leaf_work): two identical replicas at the benchmark shape, one with the leaf stream,
 one with SET_AMD_LEAF_STREAM=0, STEPS optimisation steps each on changing batches / seeds (dropout on); after every step the losses, the
 flat parameter buffer and both Adam moments must be bit-identical.  A race between the two streams (a target written by both, an operand
 freed or rewritten under a leaf kernel) shows up as the first differing step.
