@@ -96,11 +96,6 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
     return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __global__ void __launch_bounds__(256) softmax_rows_kernel(const float *x, const float *kpm, float *y, int64_t rows, int cols,
                                                           int64_t rows_per_batch, float fill) {

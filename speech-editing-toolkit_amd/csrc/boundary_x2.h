@@ -1,42 +1,12 @@
-// Shared by csrc/boundary.hip (the step-boundary kernels of the reverse loop) and csrc/diffusion_ops.hip (set_randn, set_posterior_step):
-// Philox4x32-10 + Box-Muller, and the two-piece fp16 GEMM of the step boundary (skip projection, output head, next step's input projection;
-// diffnet.py:118-120,128-131, spec_denoiser.py:86-101).
+// The step-boundary kernels of the reverse loop (csrc/boundary.hip): the two-piece fp16 GEMM of the step boundary (skip projection, output
+// head, next step's input projection; diffnet.py:118-120,128-131, spec_denoiser.py:86-101).  The posterior's noise comes from philox.h.
 #pragma once
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
 constexpr int BX_DC = 256;             // residual channels
-// ---- Philox4x32-10 (counter based) + Box-Muller ------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-__device__ __forceinline__ void randn4(uint64_t seed, uint64_t ctr, float out[4]) {
-    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
-    philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    // (0,1] uniforms, Box-Muller
-    const float u0 = ((float)(c[0] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u1 = ((float)(c[1] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(c[2] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float u3 = ((float)(c[3] >> 8) + 1.0f) * (1.0f / 16777216.0f);
-    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
-    float s0, c0, s1, c1;
-    sincosf(6.28318530717958647692f * u1, &s0, &c0);
-    sincosf(6.28318530717958647692f * u3, &s1, &c1);
-    out[0] = r0 * c0; out[1] = r0 * s0; out[2] = r1 * c1; out[3] = r1 * s1;
-}
-
 typedef _Float16 bx_f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned bx_u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned bx_u32x2 __attribute__((ext_vector_type(2)));

@@ -10,6 +10,7 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 // ---- host-side error plumbing -------------------------------------------------------------
 extern thread_local char g_set_err[512];
@@ -116,6 +117,18 @@ __device__ __forceinline__ float dev_pro(float v, int pro, float p) {
         default: return v;
     }
 }
+// the gate of the fused layer kernels (hardware exp and reciprocal) and their bf16 conversions
+__device__ __forceinline__ float fsig(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+__device__ __forceinline__ float ftanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
+__device__ __forceinline__ unsigned short f2bf(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
+__device__ __forceinline__ float bf2f(unsigned short u) { return __builtin_bit_cast(float, (unsigned)u << 16); }
+
+// sum over the 64 lanes of a wave, every lane gets it
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
 
 // ---- MFMA f32 32x32x2 fragment maps (cdna_hip_programming.md section 3) --------------------
 //   A operand: lane l holds A[i = l & 31][k = l >> 5]
@@ -145,6 +158,9 @@ __device__ __forceinline__ float buf_load(rsrc_t r, unsigned voff, unsigned soff
 __device__ __forceinline__ f32x4 buf_load4(rsrc_t r, unsigned voff, unsigned soff) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
+}
+__device__ __forceinline__ u32x4_t buf_load_u4(rsrc_t r, unsigned voff, unsigned soff) {
+    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
 }
 __device__ __forceinline__ void buf_store4(f32x4 v, rsrc_t r, unsigned voff, unsigned soff) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));

@@ -27,7 +27,6 @@
 #include "rows_sum.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
 // probe builds (-DSET_PHASE_PROBE=1): block (1, 1) of the layer kernels sums the s_memtime ticks of its phases and adds them to buf.
 //   diffnet_layer_fwd_bf16_kernel (tools/bf16_phase_probe.py), wave 0: buf[0..4] = stage, GEMM 1, gate, GEMM 2, epilogue
@@ -50,14 +49,9 @@ constexpr int KS2 = FC / 16;         // 16 k-steps of GEMM 2
 constexpr int PF = 4;                // A-fragment prefetch distance (k-steps)
 constexpr float RSQRT2 = 0.70710678118654752440f;
 
-__device__ __forceinline__ unsigned short f2bf(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
-__device__ __forceinline__ float bf2f(unsigned short u) { return __builtin_bit_cast(float, (unsigned)u << 16); }
 __device__ __forceinline__ unsigned pack2(float lo, float hi) { return (unsigned)f2bf(lo) | ((unsigned)f2bf(hi) << 16); }
 __device__ __forceinline__ f32x16 mma16(u32x4_t a, u32x4_t b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ u32x4_t buf_load_u4(rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
 }
 __device__ __forceinline__ unsigned short buf_load_u16(rsrc_t r, unsigned voff, unsigned soff) {
     return (unsigned short)__builtin_amdgcn_raw_buffer_load_b16(r, (int)voff, (int)soff, 0);
@@ -78,9 +72,6 @@ __device__ __forceinline__ void buf_store_q4(u32x2_t v, rsrc_t r, unsigned voff,
 __device__ __forceinline__ u32x2_t buf_load_q4(rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0);
 }
-__device__ __forceinline__ float fsig(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float ftanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-__device__ __forceinline__ int urow(int r) { return (r & 3) + 8 * (r >> 2); }  // + 4 * (lane >> 5)
 
 // acc[NRB][NCB] += A * B over `nks` k-steps.  A: image [ks][NRB][lane][8 bf16] at `img` (byte offsets), one b128 load
 // per (ks, rb), ring of PF k-steps.  B: bfrag(ks, cb) returns the LDS byte address of this lane's 16-byte fragment.
@@ -311,7 +302,7 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
             }
         }
     }
-    // ---- accumulators start at the biases (b_dil + b_cond): row of register r = row0(rb) + urow(r) + 4 half
+    // ---- accumulators start at the biases (b_dil + b_cond): row of register r = row0(rb) + urow16(r) + 4 half
     f32x16 acc[2 * RBW][NCB];
     const unsigned lb = 16u * (unsigned)half;  // byte offset of the lane's 4-row group
 #pragma unroll
@@ -355,7 +346,7 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) xres[q][cb][r] = buf_load(rx, vo4[cb], (unsigned)(row0(q) + urow(r)) * T4);
+            for (int r = 0; r < 16; ++r) xres[q][cb][r] = buf_load(rx, vo4[cb], (unsigned)(row0(q) + urow16(r)) * T4);
     __syncthreads();  // every wave is done reading the x tile
 #pragma unroll
     for (int q = 0; q < RBW; ++q)
@@ -413,7 +404,7 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
         for (int cb = 0; cb < NCB; ++cb) {
             if (tv[cb]) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) buf_store(acc[q][cb][r] * RSQRT2, rxo, vo4[cb], (unsigned)(row0(q) + urow(r)) * T4);
+                for (int r = 0; r < 16; ++r) buf_store(acc[q][cb][r] * RSQRT2, rxo, vo4[cb], (unsigned)(row0(q) + urow16(r)) * T4);
             }
         }
     float sk[RBW][NCB][16];
@@ -422,7 +413,7 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sk[q][cb][r] = buf_load(rsk, vo4[cb], (unsigned)(row0(q) + urow(r)) * T4);
+            for (int r = 0; r < 16; ++r) sk[q][cb][r] = buf_load(rsk, vo4[cb], (unsigned)(row0(q) + urow16(r)) * T4);
 #pragma unroll
     for (int q = 0; q < RBW; ++q)
 #pragma unroll
@@ -431,7 +422,7 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     buf_store(first ? acc[RBW + q][cb][r] : acc[RBW + q][cb][r] + sk[q][cb][r], rsk, vo4[cb],
-                              (unsigned)(row0(q) + urow(r)) * T4);
+                              (unsigned)(row0(q) + urow16(r)) * T4);
             }
         }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -663,8 +654,8 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
         for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                xkeep[cb][r] = buf_load(rx, vo4[cb], (unsigned)(row_g + urow(r)) * T4);
-                skacc[cb][r] = first0 ? 0.0f : buf_load(rsk, vo4[cb], (unsigned)(row_g + urow(r)) * T4);
+                xkeep[cb][r] = buf_load(rx, vo4[cb], (unsigned)(row_g + urow16(r)) * T4);
+                skacc[cb][r] = first0 ? 0.0f : buf_load(rsk, vo4[cb], (unsigned)(row_g + urow16(r)) * T4);
             }
     }
     // per-lane LDS byte offsets of the B fragments (frame row l31, k half) and of the lane's 4-row groups in the bias vectors
@@ -692,7 +683,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
         const rsrc_t rw1 = make_rsrc(img), rw2 = make_rsrc(img + OFF_W2B);
         const unsigned bbm = bb0 + (unsigned)(m * 4096);
         f32x16 acc[2][NCB];
-        // accumulators start at b_dil + b_cond: register r <-> row (rb ? 256 : 0) + row_g + urow(r) + 4 half
+        // accumulators start at b_dil + b_cond: register r <-> row (rb ? 256 : 0) + row_g + urow16(r) + 4 half
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -784,8 +775,8 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
                 if (st[cb]) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        buf_store(xkeep[cb][r], rxo, vo4[cb], (unsigned)(row_g + urow(r)) * T4);
-                        buf_store(skacc[cb][r], rsk, vo4[cb], (unsigned)(row_g + urow(r)) * T4);
+                        buf_store(xkeep[cb][r], rxo, vo4[cb], (unsigned)(row_g + urow16(r)) * T4);
+                        buf_store(skacc[cb][r], rsk, vo4[cb], (unsigned)(row_g + urow16(r)) * T4);
                     }
                 }
             }
@@ -999,7 +990,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) accx[0][cb][r] = buf_load(rx, vo4[cb], (unsigned)(row_g + urow(r)) * T4);
+        for (int r = 0; r < 16; ++r) accx[0][cb][r] = buf_load(rx, vo4[cb], (unsigned)(row_g + urow16(r)) * T4);
     const unsigned bc0 = CS + (unsigned)(l31 * CR + half * 16);   // conditioner tile
     const unsigned bx0 = XS + (unsigned)(l31 * XR + half * 16);   // x tile, tap 0 (and the z tile)
     // byte offsets of the lane's 4-row groups in a bias vector: GEMM 1 block [16 gate ; 16 filter] rows, GEMM 2 32-row blocks
@@ -1071,7 +1062,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) sko[cb][r] = sk_zero ? 0.0f : buf_load(rsk, vo4[cb], (unsigned)(row_g + urow(r)) * T4);
+                for (int r = 0; r < 16; ++r) sko[cb][r] = sk_zero ? 0.0f : buf_load(rsk, vo4[cb], (unsigned)(row_g + urow16(r)) * T4);
         } else {
 #pragma unroll
             for (int cb = NSKR; cb < NCB; ++cb) {
@@ -1139,7 +1130,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
                 for (int cb = 0; cb < NCB; ++cb) {
                     if (st[cb]) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) buf_store(acc[0][cb][r] + sko[cb][r], rsk, vo4[cb], (unsigned)(row_g + urow(r)) * T4);
+                        for (int r = 0; r < 16; ++r) buf_store(acc[0][cb][r] + sko[cb][r], rsk, vo4[cb], (unsigned)(row_g + urow16(r)) * T4);
                     }
                 }
             }
@@ -1191,7 +1182,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
             for (int cb = 0; cb < NCB; ++cb) {
                 if (st[cb]) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) buf_store(accx[0][cb][r], rxo, vo4[cb], (unsigned)(row_g + urow(r)) * T4);
+                    for (int r = 0; r < 16; ++r) buf_store(accx[0][cb][r], rxo, vo4[cb], (unsigned)(row_g + urow16(r)) * T4);
                 }
             }
         }
@@ -1353,7 +1344,7 @@ __global__ void __launch_bounds__(512, NT == 128 ? 1 : 2) diffnet_layer_bwd_bf16
         for (int r = 0; r < 16; ++r) {
             const float a0 = half_sum(sg[r]), a1 = half_sum(sf[r]);
             if (l31 == 0) {
-                const int c = 32 * w + urow(r) + 4 * half;
+                const int c = 32 * w + urow16(r) + 4 * half;
                 a.part_dby[(int64_t)part_row * 2 * FC + c] = a0;
                 a.part_dby[(int64_t)part_row * 2 * FC + FC + c] = a1;
             }
@@ -1384,12 +1375,12 @@ __global__ void __launch_bounds__(512, NT == 128 ? 1 : 2) diffnet_layer_bwd_bf16
         // waiting for those stores (round 3's `load 16 -> store 16` per column block paid a load AND a store round trip, 8 times).
         float rv[2][16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) rv[0][r] = buf_load(rdxo, vo4[0], (unsigned)(32 * w + urow(r)) * T4);
+        for (int r = 0; r < 16; ++r) rv[0][r] = buf_load(rdxo, vo4[0], (unsigned)(32 * w + urow16(r)) * T4);
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
             if (cb + 1 < NCB) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) rv[(cb + 1) & 1][r] = buf_load(rdxo, vo4[cb + 1], (unsigned)(32 * w + urow(r)) * T4);
+                for (int r = 0; r < 16; ++r) rv[(cb + 1) & 1][r] = buf_load(rdxo, vo4[cb + 1], (unsigned)(32 * w + urow16(r)) * T4);
             }
             __builtin_amdgcn_sched_barrier(0);
             if (cen[cb]) {
@@ -1397,30 +1388,30 @@ __global__ void __launch_bounds__(512, NT == 128 ? 1 : 2) diffnet_layer_bwd_bf16
                 for (int r = 0; r < 16; ++r) {
                     const float v = dxd[0][cb][r];
                     sd[r] += v;
-                    buf_store(has_dxo ? v + rv[cb & 1][r] * RSQRT2 : v, rdx, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
+                    buf_store(has_dxo ? v + rv[cb & 1][r] * RSQRT2 : v, rdx, vo4[cb], (unsigned)(32 * w + urow16(r)) * T4);
                 }
             }
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float a0 = half_sum(sd[r]);
-            if (l31 == 0) a.part_dd[(int64_t)part_row * FC + 32 * w + urow(r) + 4 * half] = a0;
+            if (l31 == 0) a.part_dd[(int64_t)part_row * FC + 32 * w + urow16(r) + 4 * half] = a0;
         }
         if (w < 6) {
             float pv[2][16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) pv[0][r] = buf_load(rdc, vo4[0], (unsigned)(32 * w + urow(r)) * T4);
+            for (int r = 0; r < 16; ++r) pv[0][r] = buf_load(rdc, vo4[0], (unsigned)(32 * w + urow16(r)) * T4);
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) {
                 if (cb + 1 < NCB) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) pv[(cb + 1) & 1][r] = buf_load(rdc, vo4[cb + 1], (unsigned)(32 * w + urow(r)) * T4);
+                    for (int r = 0; r < 16; ++r) pv[(cb + 1) & 1][r] = buf_load(rdc, vo4[cb + 1], (unsigned)(32 * w + urow16(r)) * T4);
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 if (cen[cb]) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        buf_store(a.dcond_first ? dcn[0][cb][r] : pv[cb & 1][r] + dcn[0][cb][r], rdc, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
+                        buf_store(a.dcond_first ? dcn[0][cb][r] : pv[cb & 1][r] + dcn[0][cb][r], rdc, vo4[cb], (unsigned)(32 * w + urow16(r)) * T4);
                 }
             }
         }

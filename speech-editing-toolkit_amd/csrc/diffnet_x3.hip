@@ -40,7 +40,6 @@
 #include "stack_queue.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 
 // probe builds (-DSET_PHASE_PROBE=1): wave 0 of ONE block sums the s_memtime ticks of its phases and adds them to buf (the kernels ran
@@ -64,8 +63,6 @@ constexpr int X_KS1 = 48;          // k-steps of GEMM 1 (3 taps x 16)
 constexpr int X_KS2 = 16;          // k-steps of GEMM 2
 constexpr float RSQRT2 = 0.70710678118654752440f;
 
-__device__ __forceinline__ unsigned short f2bf(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
-__device__ __forceinline__ float bf2f(unsigned short u) { return __builtin_bit_cast(float, (unsigned)u << 16); }
 // a = p0 + p1 + p2 exactly (up to 2^-24 |a|): the three bf16 pieces of an fp32 value
 __device__ __forceinline__ void split3(float a, unsigned short &p0, unsigned short &p1, unsigned short &p2) {
     p0 = f2bf(a);
@@ -112,12 +109,6 @@ template <typename S> constexpr int64_t x_n2() { return 8LL * X_KS2 * 2 * S::NP 
 constexpr int X_KSV = 32;
 template <typename S> constexpr int64_t x_nv() { return S::MODE == 2 ? 8LL * X_KSV * 4 * S::NP * 512 + 8 : 0; }
 template <typename S> constexpr int64_t x_nimg() { return x_n1<S>() + x_n2<S>() + 8 + x_nv<S>(); }
-__device__ __forceinline__ u32x4_t buf_load_u4(rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
-}
-__device__ __forceinline__ float fsig(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float ftanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }
-__device__ __forceinline__ int urow(int r) { return (r & 3) + 8 * (r >> 2); }  // + 4 * (lane >> 5)
 // read-once streams (the conditioner projection, the running skip sum): nt = evict-first at the L2, which the layer images live in
 constexpr int X_NT = 2;  // cache policy bit nt; measured (round 6, profiles/r06_x3w_nt_ab.log): 1.664 against 1.688 ms per launch with plain loads
 __device__ __forceinline__ float buf_load_nt(rsrc_t r, unsigned voff, unsigned soff) {
@@ -320,8 +311,8 @@ __device__ __forceinline__ void x3_init(const X3Tile &a, f32x16 (&acc)[NU][2][NC
                 const float *bd = a.b_dil + (rb ? XC : 0) + 32 * (NU * w + u);  // wave-uniform: scalar loads, no vector-memory slots
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const unsigned ur = (unsigned)((rb ? XC : 0) + 32 * (NU * w + u) + urow(r));
-                    const float blo = bd[urow(r)], bhi = bd[urow(r) + 4];
+                    const unsigned ur = (unsigned)((rb ? XC : 0) + 32 * (NU * w + u) + urow16(r));
+                    const float blo = bd[urow16(r)], bhi = bd[urow16(r) + 4];
                     acc[u][rb][cb][r] = (half ? bhi : blo) + buf_load_nt(rcp, vo4, ur * T4);
                 }
             }
@@ -453,7 +444,7 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
 #pragma unroll
             for (int u = 0; u < NU; ++u)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) xres[u][cb][r] = buf_load(rx, vo4[cb], (unsigned)(row0(u, 0) + urow(r)) * T4);
+                for (int r = 0; r < 16; ++r) xres[u][cb][r] = buf_load(rx, vo4[cb], (unsigned)(row0(u, 0) + urow16(r)) * T4);
         }
     };
     if constexpr (NU == 1) load_xres();
@@ -494,7 +485,7 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
             const float *bo = a.b_out + row0(u, rb);  // wave-uniform: scalar loads
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float blo = bo[urow(r)], bhi = bo[urow(r) + 4];
+                const float blo = bo[urow16(r)], bhi = bo[urow16(r) + 4];
                 const float bias = half ? bhi : blo;
 #pragma unroll
                 for (int cb = 0; cb < NCB; ++cb) acc[u][rb][cb][r] = (rb == 0 ? bias + xres[u][cb][r] : bias) * s2;
@@ -511,7 +502,7 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
 #pragma unroll
             for (int u = 0; u < NU; ++u)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) sk[u][cb][r] = buf_load_nt(rsk, vo4[cb], (unsigned)(32 * (NU * w + u) + urow(r)) * T4);
+                for (int r = 0; r < 16; ++r) sk[u][cb][r] = buf_load_nt(rsk, vo4[cb], (unsigned)(32 * (NU * w + u) + urow16(r)) * T4);
         }
     };
     if constexpr (NU == 1) load_sk();
@@ -534,7 +525,7 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
             for (int u = 0; u < NU; ++u)
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
-                    buf_store_agent((acc[u][0][cb][r] * is2) * RSQRT2, rxo, vo4[cb], (unsigned)(row0(u, 0) + urow(r)) * T4);
+                    buf_store_agent((acc[u][0][cb][r] * is2) * RSQRT2, rxo, vo4[cb], (unsigned)(row0(u, 0) + urow16(r)) * T4);
         }
     }
     const bool first = a.first != 0;
@@ -550,7 +541,7 @@ __device__ __forceinline__ void x3_main(const X3Tile &a, f32x16 (&acc)[NU][2][NC
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     buf_store_agent(first ? acc[u][1][cb][r] * is2 : acc[u][1][cb][r] * is2 + sk[u][cb][r], rsk, vo4[cb],
-                                    (unsigned)(32 * (NU * w + u) + urow(r)) * T4);
+                                    (unsigned)(32 * (NU * w + u) + urow16(r)) * T4);
         }
     }
 }
@@ -972,7 +963,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
     for (int cb = 0; cb < NB; ++cb) {
         const rsrc_t rx = make_rsrc(a.xin + ub[cb]);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) xres[cb][r] = buf_load(rx, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
+        for (int r = 0; r < 16; ++r) xres[cb][r] = buf_load(rx, vo4[cb], (unsigned)(32 * w + urow16(r)) * T4);
     }
     __syncthreads();  // every wave is done reading the V tile: the z tile overlays it (row = frame of the tile)
     tl.mark(23);
@@ -1015,7 +1006,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
         const float *bo = a.b_out + (rb ? XC : 0) + 32 * w;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float blo = bo[urow(r)], bhi = bo[urow(r) + 4];
+            const float blo = bo[urow16(r)], bhi = bo[urow16(r) + 4];
             const float bias = half ? bhi : blo;
 #pragma unroll
             for (int cb = 0; cb < NB; ++cb) acc[0][rb][cb][r] = (rb == 0 ? bias + xres[cb][r] : bias) * s2;
@@ -1035,7 +1026,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
         for (int cb = 0; cb < NB; ++cb) {
             const rsrc_t rsk = make_rsrc(a.skp + ub[cb]);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sk[cb][r] = buf_load_nt(rsk, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
+            for (int r = 0; r < 16; ++r) sk[cb][r] = buf_load_nt(rsk, vo4[cb], (unsigned)(32 * w + urow16(r)) * T4);
         }
     }
 #pragma unroll
@@ -1043,7 +1034,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
         if (tv[cb]) {
             const rsrc_t rxo = make_rsrc(a.xout + ub[cb]);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) buf_store_agent((acc[0][0][cb][r] * is2) * RSQRT2, rxo, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
+            for (int r = 0; r < 16; ++r) buf_store_agent((acc[0][0][cb][r] * is2) * RSQRT2, rxo, vo4[cb], (unsigned)(32 * w + urow16(r)) * T4);
         }
     }
     tl.mark(25);
@@ -1053,7 +1044,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
             const rsrc_t rsk = make_rsrc(a.skp + ub[cb]);
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                buf_store_agent(first ? acc[0][1][cb][r] * is2 : acc[0][1][cb][r] * is2 + sk[cb][r], rsk, vo4[cb], (unsigned)(32 * w + urow(r)) * T4);
+                buf_store_agent(first ? acc[0][1][cb][r] * is2 : acc[0][1][cb][r] * is2 + sk[cb][r], rsk, vo4[cb], (unsigned)(32 * w + urow16(r)) * T4);
         }
     }
     pp.lap(10); tl.mark(18);
@@ -1332,8 +1323,8 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float blo = bd[urow(r)], bhi = bd[urow(r) + 4];
-            acc[r] = (half ? bhi : blo) + buf_load(rcp, vo4, (unsigned)(rb * XC + ch0 + urow(r)) * T4);
+            const float blo = bd[urow16(r)], bhi = bd[urow16(r) + 4];
+            acc[r] = (half ? bhi : blo) + buf_load(rcp, vo4, (unsigned)(rb * XC + ch0 + urow16(r)) * T4);
         }
         if (tid == 0) *s_ok = l == 0 ? 1 : stack_wait_parts(ready + i, ready + il, ready + ir, 4 * l, abort_flag, a.err_flag, !nofence);
         __syncthreads();
@@ -1399,7 +1390,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         // ---- gate: the filter waves hand tanh(y_f) to the gate waves through LDS; z leaves already split
         if (rb == 1) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) gs[(32 * (j & 1) + urow(r) + 4 * half) * 32 + l31] = ftanh(acc[r] * is1);
+            for (int r = 0; r < 16; ++r) gs[(32 * (j & 1) + urow16(r) + 4 * half) * 32 + l31] = ftanh(acc[r] * is1);
         }
         __syncthreads();  // gs complete; every wave is done reading the x tile
         if (rb == 0) {
@@ -1409,7 +1400,7 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int r = 4 * g + e;
-                    const float zz = fsig(acc[r] * is1) * gs[(32 * (j & 1) + urow(r) + 4 * half) * 32 + l31];
+                    const float zz = fsig(acc[r] * is1) * gs[(32 * (j & 1) + urow16(r) + 4 * half) * 32 + l31];
                     S::split(tv ? zz : 0.0f, p[e]);
                 }
                 const unsigned off = (unsigned)(l31 * (XC * 2) + (ch0 + 8 * g + 4 * half) * 2);  // [frame][256] fp16, no padding
@@ -1434,11 +1425,11 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         {
             const rsrc_t rp = make_rsrc(rb == 0 ? ((l & 1) ? a.xb : a.xa) + (int64_t)b * XC * T : a.skip + (int64_t)b * XC * T);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) prev[r] = buf_load(rp, vo4, (unsigned)(ch0 + urow(r)) * T4);
+            for (int r = 0; r < 16; ++r) prev[r] = buf_load(rp, vo4, (unsigned)(ch0 + urow16(r)) * T4);
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float blo = bo[urow(r)], bhi = bo[urow(r) + 4];
+            const float blo = bo[urow16(r)], bhi = bo[urow16(r) + 4];
             const float bias = half ? bhi : blo;
             acc[r] = (rb == 0 ? bias + prev[r] : bias) * s2;
         }
@@ -1469,12 +1460,12 @@ __global__ void __launch_bounds__(256, 1) diffnet_stack_split_x2_kernel(SetDiffn
         // ---- epilogue
         if (tv && rb == 0) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) buf_store_agent((acc[r] * is2) * RSQRT2, rxout, vo4, (unsigned)(ch0 + urow(r)) * T4);
+            for (int r = 0; r < 16; ++r) buf_store_agent((acc[r] * is2) * RSQRT2, rxout, vo4, (unsigned)(ch0 + urow16(r)) * T4);
         } else if (tv) {
             const bool first = l == 0;
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                buf_store(first ? acc[r] * is2 : acc[r] * is2 + prev[r], rsk, vo4, (unsigned)(ch0 + urow(r)) * T4);
+                buf_store(first ? acc[r] * is2 : acc[r] * is2 + prev[r], rsk, vo4, (unsigned)(ch0 + urow16(r)) * T4);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();  // every store of the block has completed; the LDS tile is free for the next layer

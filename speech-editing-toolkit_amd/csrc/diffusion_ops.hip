@@ -2,7 +2,7 @@
 // update of a DiffNet layer (any residual_channels; also the device-side cross-check of the fused kernels), the sinusoidal step embedding,
 // Philox normal noise, the posterior step, q_sample, and the self test of the MFMA fragment layout.
 #include "common.h"
-#include "boundary_x2.h"
+#include "philox.h"
 
 namespace {
 __global__ void __launch_bounds__(256) gate_kernel(const float *y, float *z, int B, int C, int T) {
@@ -37,7 +37,7 @@ __global__ void __launch_bounds__(256) sinusoid_kernel(const float *t, float *ou
     out[i] = j < half ? sinf(ang) : cosf(ang);
 }
 
-// (Philox4x32-10 + Box-Muller: csrc/boundary_x2.h, shared with the step-boundary kernels of csrc/boundary.hip)
+// (Philox4x32-10 + Box-Muller: csrc/philox.h, shared with the step-boundary kernels of csrc/boundary.hip)
 
 // seed_delta (set_rng_seed_delta, may be NULL): a device word ADDED to the seed argument -- a captured graph carries the seed of the
 // step it was captured at; the replay of step k stores (seed_k - seed_captured) there and draws exactly the eager step's numbers

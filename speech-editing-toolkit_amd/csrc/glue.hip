@@ -5,6 +5,7 @@
 #include <mutex>
 
 #include "common.h"
+#include "elementwise.h"
 #include "pitch_edges.h"
 
 // ---- LayerNorm over C of [B][C][T]: block = 32 frames x 8 channel groups (loads coalesced along t, 128 B per group
@@ -168,50 +169,27 @@ extern "C" int set_expand_states(const float *enc, const int64_t *mel2ph, float 
     return set_check_launch("set_expand_states");
 }
 
-__global__ void __launch_bounds__(256) add_chan_mask_kernel(const float *x, const float *add, const float *mask,
-                                                            float *out, int B, int C, int T) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * C * T) return;
-    const int t = (int)(i % T);
-    const int c = (int)((i / T) % C);
-    const int b = (int)(i / ((int64_t)T * C));
-    float v = x[i];
-    if (add) v += add[(int64_t)b * C + c];
-    if (mask) v *= mask[(int64_t)b * T + t];
-    out[i] = v;
-}
-// four consecutive frames per thread (T % 4 == 0, 16-byte aligned operands): same arithmetic per element
-__global__ void __launch_bounds__(256) add_chan_mask_vec4_kernel(const float *x, const float *add, const float *mask, float *out,
-                                                                 int64_t n4, int C, int T) {
-    const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i4 >= n4) return;
-    const int64_t i = i4 * 4;
-    const int t = (int)(i % T);
-    const int c = (int)((i / T) % C);
-    const int b = (int)(i / ((int64_t)T * C));
-    f32x4 v = *reinterpret_cast<const f32x4 *>(x + i);
-    if (add) {
-        const float a = add[(int64_t)b * C + c];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] += a;
+namespace {
+// out = (x + add[b][c]) * mask[b][t], add and mask optional (elementwise.h: elements i .. i + W - 1 of one row, T % 4 == 0 when W = 4)
+struct AddChanMask {
+    const float *x, *add, *mask;
+    float *out;
+    int C, T;
+    template <int W> __device__ void run(int64_t i) const {
+        const int t = (int)(i % T);
+        const int c = (int)((i / T) % C);
+        const int b = (int)(i / ((int64_t)T * C));
+        ew_t<W> v = ew_ld<W>(x + i);
+        if (add) v += add[(int64_t)b * C + c];
+        if (mask) v *= ew_ld<W>(mask + (int64_t)b * T + t);
+        ew_st<W>(out + i, v);
     }
-    if (mask) {
-        const f32x4 m = *reinterpret_cast<const f32x4 *>(mask + (int64_t)b * T + t);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] *= m[e];
-    }
-    *reinterpret_cast<f32x4 *>(out + i) = v;
-}
+};
+}  // namespace
 extern "C" int set_add_chan_mask(const float *x, const float *add, const float *mask, float *out, int32_t B, int32_t C,
                                  int32_t T, void *stream) {
     SET_REQUIRE(x && out && B > 0 && C > 0 && T > 0, "set_add_chan_mask");
-    if (T % 4 == 0 && set_aligned16(x, out, mask))
-        hipLaunchKernelGGL(add_chan_mask_vec4_kernel, dim3(set_blocks((int64_t)B * C * T / 4, 256)), dim3(256), 0, (hipStream_t)stream, x, add,
-                           mask, out, (int64_t)B * C * T / 4, C, T);
-    else
-    hipLaunchKernelGGL(add_chan_mask_kernel, dim3(set_blocks((int64_t)B * C * T, 256)), dim3(256), 0,
-                       (hipStream_t)stream, x, add, mask, out, B, C, T);
-    return set_check_launch("set_add_chan_mask");
+    return ew_launch(AddChanMask{x, add, mask, out, C, T}, (int64_t)B * C * T, T % 4 == 0 && set_aligned16(x, out, mask), stream, "set_add_chan_mask");
 }
 
 // ---- masked ground-truth durations: one block per utterance, LDS histogram ---------------------

@@ -18,11 +18,6 @@ __device__ __forceinline__ int label_of(const int64_t *labels, int64_t i) {
     const int64_t y = labels[i];
     return y < 0 ? 0 : (y > 2 ? 2 : (int)y);  // the host remaps to {0, 1, 2}; clamped for memory safety only
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // softmax pieces of one row: p[3], log p_y
 __device__ __forceinline__ void row_softmax(const float z[3], int y, float p[3], float &logp_y) {

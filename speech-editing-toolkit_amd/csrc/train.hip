@@ -4,6 +4,8 @@
 // their gradients, fused AdamW and the global grad norm.  Input gradients of convolutions reuse set_conv1d
 // (a convolution with transposed weight addressing and negated dilation/padding).
 #include "common.h"
+#include "elementwise.h"
+#include "philox.h"
 #include "rows_sum.h"
 
 namespace {
@@ -174,7 +176,7 @@ __global__ void __launch_bounds__(256) channel_sum_kernel(const float *x, int B,
         const float *row = x + ((int64_t)b * C + c) * T;
         for (int t = threadIdx.x; t < T; t += 256) s += row[t];
     }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) part[(int64_t)blockIdx.y * C + c] = red[0] + red[1] + red[2] + red[3];
@@ -186,48 +188,30 @@ __global__ void __launch_bounds__(256) row_sum_kernel(const float *x, float *out
     const int lane = threadIdx.x & 63;
     float s = 0.0f;
     for (int t = lane; t < T; t += 64) s += x[row * T + t];
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    s = wave_sum(s);
     if (lane == 0) out[row] = s * scale;
 }
 
+// ---- elementwise ops (elementwise.h: run<W> handles elements i .. i + W - 1, W = 4 with 16-byte accesses or W = 1) --------------
 // G = dY * mask * alpha * [relu: y > 0]      (epilogue backward of set_conv1d; act in {none, relu})
-__global__ void __launch_bounds__(256) conv_epilogue_bwd_kernel(const float *dy, const float *y, const float *mask,
-                                                                float *g, int B, int C, int T, int act, float alpha) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * C * T) return;
-    const int t = (int)(i % T);
-    const int b = (int)(i / ((int64_t)C * T));
-    float v = dy[i];
-    if (mask) v *= mask[(int64_t)b * T + t];
-    if (act == SET_ACT_RELU && !(y[i] > 0.0f)) v = 0.0f;
-    g[i] = v * alpha;
-}
-
-// four consecutive frames per thread (T % 4 == 0, 16-byte aligned operands): the same arithmetic per element, 16-byte accesses and one
-// index division per four elements (round 6: the one-element forms of these elementwise kernels ran at 2 - 4 TB/s)
-__global__ void __launch_bounds__(256) conv_epilogue_bwd_vec4_kernel(const float *dy, const float *y, const float *mask, float *g,
-                                                                     int64_t n4, int64_t CT, int T, int act, float alpha) {
-    const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i4 >= n4) return;
-    const int64_t i = i4 * 4;
-    f32x4 v = *reinterpret_cast<const f32x4 *>(dy + i);
-    if (mask) {
-        const int64_t b = i / CT;
-        const int t = (int)(i % T);
-        const f32x4 m = *reinterpret_cast<const f32x4 *>(mask + b * T + t);
+struct ConvEpilogueBwd {
+    const float *dy, *y, *mask;
+    float *g;
+    int64_t CT;
+    int T, act;
+    float alpha;
+    template <int W> __device__ void run(int64_t i) const {
+        ew_t<W> v = ew_ld<W>(dy + i);
+        if (mask) v *= ew_ld<W>(mask + (i / CT) * T + i % T);
+        if (act == SET_ACT_RELU) {
+            const ew_t<W> yv = ew_ld<W>(y + i);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] *= m[e];
+            for (int e = 0; e < W; ++e)
+                if (!(ew_at<W>(yv, e) > 0.0f)) ew_set<W>(v, e, 0.0f);
+        }
+        ew_st<W>(g + i, v * alpha);
     }
-    if (act == SET_ACT_RELU) {
-        const f32x4 yv = *reinterpret_cast<const f32x4 *>(y + i);
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (!(yv[e] > 0.0f)) v[e] = 0.0f;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = v[e] * alpha;
-    *reinterpret_cast<f32x4 *>(g + i) = v;
-}
+};
 
 // ---- activations with saved pre-activation z ----------------------------------------------------------------
 __device__ __forceinline__ float dev_act_grad(float z, int act, float p) {
@@ -249,110 +233,76 @@ __device__ __forceinline__ float dev_act_grad(float z, int act, float p) {
         default: return 1.0f;
     }
 }
-__global__ void __launch_bounds__(256) act_fwd_kernel(const float *z, float *y, int64_t n, int act, float p) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) y[i] = dev_act(z[i], act, p);
-}
-__global__ void __launch_bounds__(256) act_bwd_kernel(const float *z, const float *dy, float *dz, int64_t n, int act,
-                                                      float p) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) dz[i] = dy[i] * dev_act_grad(z[i], act, p);
-}
-// the same followed by the conv epilogue's alpha (dz = (dy act'(z)) alpha: the two roundings of act_bwd + conv_epilogue_bwd, one launch)
-__global__ void __launch_bounds__(256) act_bwd_scaled_kernel(const float *z, const float *dy, float *dz, int64_t n, int act, float p,
-                                                             float scale) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) {
-        const float t = dy[i] * dev_act_grad(z[i], act, p);
-        dz[i] = t * scale;
-    }
-}
-
-__global__ void __launch_bounds__(256) act_fwd_vec4_kernel(const float *z, float *y, int64_t n4, int act, float p) {
-    const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i4 >= n4) return;
-    const f32x4 zv = *reinterpret_cast<const f32x4 *>(z + i4 * 4);
-    f32x4 o;
+struct ActFwd {
+    const float *z;
+    float *y;
+    int act;
+    float p;
+    template <int W> __device__ void run(int64_t i) const {
+        const ew_t<W> zv = ew_ld<W>(z + i);
+        ew_t<W> o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = dev_act(zv[e], act, p);
-    *reinterpret_cast<f32x4 *>(y + i4 * 4) = o;
-}
-// scaled != 0: dz = (dy act'(z)) scale (act_bwd_scaled_kernel's two roundings), else dz = dy act'(z)
-__global__ void __launch_bounds__(256) act_bwd_vec4_kernel(const float *z, const float *dy, float *dz, int64_t n4, int act, float p,
-                                                           int scaled, float scale) {
-    const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i4 >= n4) return;
-    const f32x4 zv = *reinterpret_cast<const f32x4 *>(z + i4 * 4), dv = *reinterpret_cast<const f32x4 *>(dy + i4 * 4);
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float t = dv[e] * dev_act_grad(zv[e], act, p);
-        o[e] = scaled ? t * scale : t;
+        for (int e = 0; e < W; ++e) ew_set<W>(o, e, dev_act(ew_at<W>(zv, e), act, p));
+        ew_st<W>(y + i, o);
     }
-    *reinterpret_cast<f32x4 *>(dz + i4 * 4) = o;
-}
+};
+// dz = dy act'(z); scaled: dz = (dy act'(z)) scale, the conv epilogue's alpha in the same launch (the two roundings of act_bwd + conv_epilogue_bwd)
+struct ActBwd {
+    const float *z, *dy;
+    float *dz;
+    int act;
+    float p;
+    bool scaled;
+    float scale;
+    template <int W> __device__ void run(int64_t i) const {
+        const ew_t<W> zv = ew_ld<W>(z + i), dv = ew_ld<W>(dy + i);
+        ew_t<W> o;
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const float t = ew_at<W>(dv, e) * dev_act_grad(ew_at<W>(zv, e), act, p);
+            ew_set<W>(o, e, scaled ? t * scale : t);
+        }
+        ew_st<W>(dz + i, o);
+    }
+};
 
-// ---- gate / res-skip backward ---------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) gate_bwd_kernel(const float *y, const float *dz, float *dy, int B, int C,
-                                                       int T) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * C * T) return;
-    const int64_t ct = i % ((int64_t)C * T), b = i / ((int64_t)C * T);
-    const float *yb = y + b * 2 * C * T;
-    float *dyb = dy + b * 2 * C * T;
-    const float s = dev_sigmoid(yb[ct]), th = tanhf(yb[(int64_t)C * T + ct]);
-    const float d = dz[i];
-    dyb[ct] = d * th * s * (1.0f - s);
-    dyb[(int64_t)C * T + ct] = d * s * (1.0f - th * th);
-}
+// ---- gate / res-skip backward; y, dy, d_o are [B][2C][T], CT = C * T (a unit never straddles two utterances: CT % 4 == 0 when W = 4) ----------
+// (the one-element form moved 131 MB in 62 us at B = 32, T = 800, 2.1 TB/s -- 20 launches per fp32 training step)
+struct GateBwd {
+    const float *y, *dz;
+    float *dy;
+    int64_t CT;
+    template <int W> __device__ void run(int64_t i) const {
+        const int64_t b = i / CT, ct = i - b * CT;
+        const float *yb = y + b * 2 * CT + ct;
+        float *dyb = dy + b * 2 * CT + ct;
+        const ew_t<W> yg = ew_ld<W>(yb), yf = ew_ld<W>(yb + CT), d = ew_ld<W>(dz + i);
+        ew_t<W> og, of;
+#pragma unroll
+        for (int e = 0; e < W; ++e) {
+            const float s = dev_sigmoid(ew_at<W>(yg, e)), th = tanhf(ew_at<W>(yf, e));
+            ew_set<W>(og, e, ew_at<W>(d, e) * th * s * (1.0f - s));
+            ew_set<W>(of, e, ew_at<W>(d, e) * s * (1.0f - th * th));
+        }
+        ew_st<W>(dyb, og);
+        ew_st<W>(dyb + CT, of);
+    }
+};
 // forward: x_out = (x + o[:C]) / sqrt2 ; skip_out = skip_in + o[C:]
 // backward: dx = dx_out / sqrt2 ; do[:C] = dx_out / sqrt2 ; do[C:] = dskip_out
-// four consecutive elements per thread (16-byte accesses; C * T a multiple of 4, 16-byte aligned operands): the one-element form above moves
-// 131 MB in 62 us at B = 32, T = 800 (2.1 TB/s) -- 20 launches per fp32 training step.  Same arithmetic per element: same bits.
-__global__ void __launch_bounds__(256) gate_bwd_vec4_kernel(const float *y, const float *dz, float *dy, int64_t n4, int64_t ct4_per_b,
-                                                            int64_t CT) {
-    const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i4 >= n4) return;
-    const int64_t b = i4 / ct4_per_b, ct = (i4 - b * ct4_per_b) * 4;
-    const float *yb = y + b * 2 * CT + ct;
-    float *dyb = dy + b * 2 * CT + ct;
-    const f32x4 yg = *reinterpret_cast<const f32x4 *>(yb), yf = *reinterpret_cast<const f32x4 *>(yb + CT);
-    const f32x4 d = *reinterpret_cast<const f32x4 *>(dz + i4 * 4);
-    f32x4 og, of;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const float s = dev_sigmoid(yg[e]), th = tanhf(yf[e]);
-        og[e] = d[e] * th * s * (1.0f - s);
-        of[e] = d[e] * s * (1.0f - th * th);
+struct ResSkipBwd {
+    const float *dx_out, *dskip;
+    float *dx, *d_o;
+    int64_t CT;
+    template <int W> __device__ void run(int64_t i) const {
+        const int64_t b = i / CT, ct = i - b * CT;
+        const ew_t<W> v = ew_ld<W>(dx_out + i) / 1.41421356237309504880f;
+        ew_st<W>(dx + i, v);
+        float *ob = d_o + b * 2 * CT + ct;
+        ew_st<W>(ob, v);
+        ew_st<W>(ob + CT, ew_ld<W>(dskip + i));
     }
-    *reinterpret_cast<f32x4 *>(dyb) = og;
-    *reinterpret_cast<f32x4 *>(dyb + CT) = of;
-}
-__global__ void __launch_bounds__(256) res_skip_bwd_kernel(const float *dx_out, const float *dskip, float *dx, float *d_o,
-                                                           int B, int C, int T) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)B * C * T) return;
-    const int64_t ct = i % ((int64_t)C * T), b = i / ((int64_t)C * T);
-    const float v = dx_out[i] / 1.41421356237309504880f;
-    dx[i] = v;
-    float *ob = d_o + b * 2 * C * T;
-    ob[ct] = v;
-    ob[(int64_t)C * T + ct] = dskip[i];
-}
-__global__ void __launch_bounds__(256) res_skip_bwd_vec4_kernel(const float *dx_out, const float *dskip, float *dx, float *d_o, int64_t n4,
-                                                                int64_t ct4_per_b, int64_t CT) {
-    const int64_t i4 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i4 >= n4) return;
-    const int64_t b = i4 / ct4_per_b, ct = (i4 - b * ct4_per_b) * 4;
-    const f32x4 g = *reinterpret_cast<const f32x4 *>(dx_out + i4 * 4);
-    f32x4 v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = g[e] / 1.41421356237309504880f;
-    *reinterpret_cast<f32x4 *>(dx + i4 * 4) = v;
-    float *ob = d_o + b * 2 * CT + ct;
-    *reinterpret_cast<f32x4 *>(ob) = v;
-    *reinterpret_cast<f32x4 *>(ob + CT) = *reinterpret_cast<const f32x4 *>(dskip + i4 * 4);
-}
+};
 
 // ---- LayerNorm over channels, backward: block = 32 frames x 8 channel groups (as the forward kernel), column sums
 //      through LDS; x and dy of the thread's <= 32 channels are fetched once as two batches and stay in registers for
@@ -497,49 +447,39 @@ __global__ void __launch_bounds__(64 * ROWS_RG) lnb_partial_sum_kernel(const flo
 }
 
 // ---- dropout: keep mask from Philox(seed, offset + i/4); same kernel for forward and backward ------------------
-__device__ __forceinline__ void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1, n3 = (uint32_t)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
+// One quad per thread (the counter advances once per four elements); vec: 16-byte aligned operands, then a whole quad is one load and one store
 __global__ void __launch_bounds__(256) dropout_kernel(const float *x, float *y, int64_t n, float p, uint64_t seed,
                                                       uint64_t offset, const uint64_t *seed_delta, int vec) {
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (q * 4 >= n) return;
     if (seed_delta) seed += *seed_delta;  // set_rng_seed_delta: see randn_kernel
-    const uint64_t ctr = offset + (uint64_t)q;
-    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x5eedu, 0u};
-    philox_round(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    bool keep[4];
+    dropout_keep4(seed, offset, q, p, keep);
     const float inv = 1.0f / (1.0f - p);
-    if (vec && q * 4 + 3 < n) {  // 16-byte aligned operands: one load, one store (same values)
-        const f32x4 xv = *reinterpret_cast<const f32x4 *>(x + q * 4);
-        f32x4 o;
+    const bool whole = vec && q * 4 + 3 < n;
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (whole) {
+        v = *reinterpret_cast<const f32x4 *>(x + q * 4);
+    } else {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float u = (float)(c[k] >> 8) * (1.0f / 16777216.0f);
-            o[k] = u >= p ? xv[k] * inv : 0.0f;
-        }
-        *reinterpret_cast<f32x4 *>(y + q * 4) = o;
-        return;
+        for (int k = 0; k < 4; ++k)
+            if (q * 4 + k < n) v[k] = x[q * 4 + k];
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t i = q * 4 + k;
-        if (i >= n) break;
-        const float u = (float)(c[k] >> 8) * (1.0f / 16777216.0f);
-        y[i] = u >= p ? x[i] * inv : 0.0f;
+    for (int k = 0; k < 4; ++k) v[k] = keep[k] ? v[k] * inv : 0.0f;
+    if (whole) {
+        *reinterpret_cast<f32x4 *>(y + q * 4) = v;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (q * 4 + k < n) y[q * 4 + k] = v[k];
     }
 }
 
 // ---- dropout on the branch of a residual sub-block (modules/commons/conv.py:57-65, training):
 //   forward  y = (x + keep(i) z/(1-p)) * mask[b][t]
 //   backward g2 = dy * mask (the residual's gradient), gz = keep(i) g2/(1-p) (the branch's)
-// keep(i) is dropout_kernel's decision for element i of the [B][C][T] tensor (same Philox counter, same threshold), and every
+// keep(i) is dropout_kernel's decision for element i of the [B][C][T] tensor (the same dropout_keep4 draw), and every
 // product / sum is the one the per-op tape (dropout, add, mask) rounds: the fused node and the tape agree bit for bit.
 __global__ void __launch_bounds__(256) residual_dropout_kernel(const float *x, const float *z, const float *mask, float *y, float *gz,
                                                                int64_t n, int64_t CT, int T, float p, uint64_t seed, uint64_t offset,
@@ -547,24 +487,22 @@ __global__ void __launch_bounds__(256) residual_dropout_kernel(const float *x, c
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (q * 4 >= n) return;
     if (seed_delta) seed += *seed_delta;
-    const uint64_t ctr = offset + (uint64_t)q;
-    uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0x5eedu, 0u};
-    philox_round(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    bool keep[4];
+    dropout_keep4(seed, offset, q, p, keep);
     const float inv = 1.0f / (1.0f - p);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int64_t i = q * 4 + k;
         if (i >= n) break;
-        const bool keep = (float)(c[k] >> 8) * (1.0f / 16777216.0f) >= p;
         const float m = mask ? mask[(i / CT) * T + i % T] : 1.0f;
         if (gz == nullptr) {  // forward: x = residual, z = branch
-            float v = x[i] + (keep ? z[i] * inv : 0.0f);
+            float v = x[i] + (keep[k] ? z[i] * inv : 0.0f);
             if (mask) v *= m;
             y[i] = v;
         } else {  // backward: x = dy; y = g2, gz = branch gradient
             const float g = mask ? x[i] * m * 1.0f : x[i];
             y[i] = g;
-            gz[i] = keep ? g * inv : 0.0f;
+            gz[i] = keep[k] ? g * inv : 0.0f;
         }
     }
 }
@@ -1219,60 +1157,32 @@ extern "C" int set_conv_epilogue_bwd(const float *dy, const float *y, const floa
                                      int32_t T, int32_t act, float alpha, void *stream) {
     SET_REQUIRE(dy && g && B > 0 && C > 0 && T > 0 && (act == SET_ACT_NONE || (act == SET_ACT_RELU && y)),
                 "set_conv_epilogue_bwd");
-    if (T % 4 == 0 && set_aligned16(dy, y, mask) && set_aligned16(g, g, g))
-        hipLaunchKernelGGL(conv_epilogue_bwd_vec4_kernel, dim3(set_blocks((int64_t)B * C * T / 4, 256)), dim3(256), 0, (hipStream_t)stream, dy, y,
-                           mask, g, (int64_t)B * C * T / 4, (int64_t)C * T, T, act, alpha);
-    else
-        hipLaunchKernelGGL(conv_epilogue_bwd_kernel, dim3(set_blocks((int64_t)B * C * T, 256)), dim3(256), 0,
-                           (hipStream_t)stream, dy, y, mask, g, B, C, T, act, alpha);
-    return set_check_launch("set_conv_epilogue_bwd");
+    const bool vec_ok = T % 4 == 0 && set_aligned16(dy, y, mask) && set_aligned16(g, g, g);
+    return ew_launch(ConvEpilogueBwd{dy, y, mask, g, (int64_t)C * T, T, act, alpha}, (int64_t)B * C * T, vec_ok, stream, "set_conv_epilogue_bwd");
 }
 extern "C" int set_act_fwd(const float *z, float *y, int64_t n, int32_t act, float p, void *stream) {
     SET_REQUIRE(z && y && n > 0, "set_act_fwd");
-    if (n % 4 == 0 && set_aligned16(z, y, y))
-        hipLaunchKernelGGL(act_fwd_vec4_kernel, dim3(set_blocks(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, z, y, n / 4, act, p);
-    else
-        hipLaunchKernelGGL(act_fwd_kernel, dim3(set_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, z, y, n, act, p);
-    return set_check_launch("set_act_fwd");
+    return ew_launch(ActFwd{z, y, act, p}, n, n % 4 == 0 && set_aligned16(z, y, y), stream, "set_act_fwd");
 }
 extern "C" int set_act_bwd(const float *z, const float *dy, float *dz, int64_t n, int32_t act, float p, void *stream) {
     SET_REQUIRE(z && dy && dz && n > 0, "set_act_bwd");
-    if (n % 4 == 0 && set_aligned16(z, dy, dz))
-        hipLaunchKernelGGL(act_bwd_vec4_kernel, dim3(set_blocks(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, z, dy, dz, n / 4, act, p, 0, 1.0f);
-    else
-        hipLaunchKernelGGL(act_bwd_kernel, dim3(set_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, z, dy, dz, n, act, p);
-    return set_check_launch("set_act_bwd");
+    return ew_launch(ActBwd{z, dy, dz, act, p, false, 1.0f}, n, n % 4 == 0 && set_aligned16(z, dy, dz), stream, "set_act_bwd");
 }
 extern "C" int set_act_bwd_scaled(const float *z, const float *dy, float *dz, int64_t n, int32_t act, float p, float scale, void *stream) {
     SET_REQUIRE(z && dy && dz && n > 0, "set_act_bwd_scaled");
-    if (n % 4 == 0 && set_aligned16(z, dy, dz))
-        hipLaunchKernelGGL(act_bwd_vec4_kernel, dim3(set_blocks(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, z, dy, dz, n / 4, act, p, 1, scale);
-    else
-        hipLaunchKernelGGL(act_bwd_scaled_kernel, dim3(set_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, z, dy, dz, n, act, p, scale);
-    return set_check_launch("set_act_bwd_scaled");
+    return ew_launch(ActBwd{z, dy, dz, act, p, true, scale}, n, n % 4 == 0 && set_aligned16(z, dy, dz), stream, "set_act_bwd_scaled");
 }
 extern "C" int set_gate_bwd(const float *y, const float *dz, float *dy, int32_t B, int32_t C, int32_t T, void *stream) {
     SET_REQUIRE(y && dz && dy && B > 0 && C > 0 && T > 0, "set_gate_bwd");
     const int64_t CT = (int64_t)C * T;
-    if (CT % 4 == 0 && set_aligned16(y, dz, dy))
-        hipLaunchKernelGGL(gate_bwd_vec4_kernel, dim3(set_blocks(B * CT / 4, 256)), dim3(256), 0, (hipStream_t)stream, y, dz, dy, B * CT / 4,
-                           CT / 4, CT);
-    else
-        hipLaunchKernelGGL(gate_bwd_kernel, dim3(set_blocks((int64_t)B * C * T, 256)), dim3(256), 0, (hipStream_t)stream, y,
-                           dz, dy, B, C, T);
-    return set_check_launch("set_gate_bwd");
+    return ew_launch(GateBwd{y, dz, dy, CT}, B * CT, CT % 4 == 0 && set_aligned16(y, dz, dy), stream, "set_gate_bwd");
 }
 extern "C" int set_res_skip_bwd(const float *dx_out, const float *dskip, float *dx, float *d_o, int32_t B, int32_t C,
                                 int32_t T, void *stream) {
     SET_REQUIRE(dx_out && dskip && dx && d_o && B > 0 && C > 0 && T > 0, "set_res_skip_bwd");
     const int64_t CT = (int64_t)C * T;
-    if (CT % 4 == 0 && set_aligned16(dx_out, dskip, dx) && set_aligned16(d_o, d_o, d_o))
-        hipLaunchKernelGGL(res_skip_bwd_vec4_kernel, dim3(set_blocks(B * CT / 4, 256)), dim3(256), 0, (hipStream_t)stream, dx_out, dskip, dx,
-                           d_o, B * CT / 4, CT / 4, CT);
-    else
-        hipLaunchKernelGGL(res_skip_bwd_kernel, dim3(set_blocks((int64_t)B * C * T, 256)), dim3(256), 0, (hipStream_t)stream,
-                       dx_out, dskip, dx, d_o, B, C, T);
-    return set_check_launch("set_res_skip_bwd");
+    const bool vec_ok = CT % 4 == 0 && set_aligned16(dx_out, dskip, dx) && set_aligned16(d_o, d_o, d_o);
+    return ew_launch(ResSkipBwd{dx_out, dskip, dx, d_o, CT}, B * CT, vec_ok, stream, "set_res_skip_bwd");
 }
 extern "C" int64_t set_layernorm_ch_bwd_scratch(int32_t B, int32_t C, int32_t T) {
     return (int64_t)B * ((T + 15) / 16) * 2 * C;  // one row of 2 C partial sums per block; the 16-frame block shape has the most blocks

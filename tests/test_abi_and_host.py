@@ -141,7 +141,8 @@ def test_training_reductions_have_no_atomic_twin():
     pkg = os.path.join(ROOT, "speech-editing-toolkit_amd")
     src = _strip_comments(open(os.path.join(pkg, "csrc", "train.hip")).read())
     heads = list(re.finditer(r"__global__\s+void\s+(?:__launch_bounds__\([^)]*\)\s*)?(\w+)\s*\(([^)]*)\)\s*\{", src))
-    assert len(heads) == src.count("__global__") and len(heads) >= 30  # every kernel's signature was parsed
+    # every kernel's signature was parsed (25 kernels since the elementwise pairs became ops of csrc/elementwise.h's one template)
+    assert len(heads) == src.count("__global__") and len(heads) >= 25
     atomic = set()
     for m, nxt in zip(heads, heads[1:] + [None]):
         assert "nullptr" not in m.group(2), m.group(1)  # no defaulted pointer parameter

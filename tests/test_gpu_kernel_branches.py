@@ -596,13 +596,19 @@ def test_add_chan_mask_and_conv_epilogue_bwd_paths(dev, B, C, T, off):
         _check(L.set_conv_epilogue_bwd(_p(xd), _p(yd), _p(md), _p(gr), B, C, T, 1, 0.75, _s()), "set_conv_epilogue_bwd")  # relu
         gn = _shifted(torch.zeros(B, C, T), o, dev)
         _check(L.set_conv_epilogue_bwd(_p(xd), None, None, _p(gn), B, C, T, 0, 1.0 / 3.0, _s()), "set_conv_epilogue_bwd")
+        gm = _shifted(torch.zeros(B, C, T), o, dev)
+        _check(L.set_conv_epilogue_bwd(_p(xd), None, _p(md), _p(gm), B, C, T, 0, 0.75, _s()), "set_conv_epilogue_bwd")  # mask alone
+        gy = _shifted(torch.zeros(B, C, T), o, dev)
+        _check(L.set_conv_epilogue_bwd(_p(xd), _p(yd), None, _p(gy), B, C, T, 1, 1.0, _s()), "set_conv_epilogue_bwd")  # relu alone
         torch.cuda.synchronize()
-        res[o] = [t.cpu() for t in (out, out2, gr, gn)]
+        res[o] = [t.cpu() for t in (out, out2, gr, gn, gm, gy)]
     for a, b in zip(res[off], res[1]):
         assert torch.equal(a, b)
     xx, mm = x.double(), mask.double()[:, None]
-    want = [(xx + add.double()[:, :, None]) * mm, xx * mm, xx * mm * (y.double() > 0) * 0.75, xx * (1.0 / 3.0)]
-    bounds = [2 * U * (xx.abs() + add.double().abs()[:, :, None]) * mm, U * xx.abs() * mm, 3 * U * xx.abs() * 0.75, 2 * U * xx.abs() / 3.0]
+    want = [(xx + add.double()[:, :, None]) * mm, xx * mm, xx * mm * (y.double() > 0) * 0.75, xx * (1.0 / 3.0),
+            xx * mm * 0.75, xx * (y.double() > 0)]
+    bounds = [2 * U * (xx.abs() + add.double().abs()[:, :, None]) * mm, U * xx.abs() * mm, 3 * U * xx.abs() * 0.75, 2 * U * xx.abs() / 3.0,
+              3 * U * xx.abs() * 0.75, U * xx.abs()]
     for got, w_, b_ in zip(res[off], want, bounds):
         assert bool(((got.double() - w_).abs() <= b_ + 1e-30).all())
 

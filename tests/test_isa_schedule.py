@@ -126,6 +126,44 @@ def test_epilogue_stores_do_not_serialise(src, compiled):
     assert seen == set(STORE_GUARD[src]), (seen, STORE_GUARD[src])
 
 
+EW_VEC4 = {  # file -> {op of an ew_kernel<4, Op> instantiation (csrc/elementwise.h): VGPRs of the hand-written _vec4 kernel it replaced}
+    "train.hip": {"ConvEpilogueBwd": 19, "ActFwd": 22, "ActBwd": 26, "GateBwd": 27, "ResSkipBwd": 30},
+    "glue.hip": {"AddChanMask": 20},
+}
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
+@pytest.mark.parametrize("src", sorted(EW_VEC4))
+def test_elementwise_vec4_instantiations_keep_16_byte_accesses(src, compiled):
+    """Both widths of an elementwise op come from one run<W>(), so the device test that compares them no longer notices a W = 4
+    instantiation that the compiler lowered to four 4-byte accesses: every one must load and store dwordx4, use no scratch and stay within
+    4 VGPRs of the kernel it replaced (counts of that kernel from -Rpass-analysis=kernel-resource-usage at the commit before the template)."""
+    import re
+    lines, remarks = compiled[src]
+    usage, cur = {}, None
+    for line in remarks.split("\n"):
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            cur = usage.setdefault(m.group(1), {})
+        for key, pat in (("VGPRs", r" VGPRs: (\d+)"), ("Scratch", r" ScratchSize \[bytes/lane\]: (\d+)")):
+            m = re.search(pat, line)
+            if m:
+                cur[key] = int(m.group(1))
+    seen = set()
+    for name, body in isa_scan.kernels(lines):
+        m = re.search(r"ew_kernelILi4ENS_\d+([A-Za-z]+?)EEE", name)
+        if m is None:
+            continue
+        op = m.group(1)
+        seen.add(op)
+        text = [b.strip() for b in body]
+        assert any(t.startswith(("global_load_dwordx4", "buffer_load_dwordx4")) for t in text), name
+        assert any(t.startswith(("global_store_dwordx4", "buffer_store_dwordx4")) for t in text), name
+        assert usage[name]["Scratch"] == 0, (name, usage[name])
+        assert usage[name]["VGPRs"] <= EW_VEC4[src][op] + 4, (name, usage[name], EW_VEC4[src][op])
+    assert seen == set(EW_VEC4[src]), (seen, set(EW_VEC4[src]))
+
+
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_no_wide_store_has_its_data_registers_rewritten_by_the_next_instruction(compiled):
     """Round 5: the run-to-run differences of the fp32 training step came from
