@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SET_AMD_ABI_VERSION 4
+#define SET_AMD_ABI_VERSION 5
 
 /* error codes */
 #define SET_OK 0
@@ -627,30 +627,25 @@ int set_step_proj_bwd_dw(const float *h, const float *g, float *dw, int64_t dw_l
 int64_t set_packed_conv_weight_bf16_size(int32_t Cout, int32_t Cin, int32_t K);
 int set_pack_conv_weight_bf16(const float *w, void *wp, int32_t Cout, int32_t Cin, int32_t K, int64_t w_base,
                               int64_t w_sco, int64_t w_sci, int64_t w_stap, void *stream);
-/* All bf16 images of a model in ONE launch (after an optimizer step).  descs_dev: n descriptors IN DEVICE MEMORY, sorted by
- * `start` = index of the image's first element in the concatenated element space [0, total); per image the layout of
- * set_pack_conv_weight_bf16 (CoutP = Cout rounded up to 128, CinP = Cin rounded up to 32). */
-typedef struct SetPackBf16Desc {
+/* Every weight image of the three layouts below in ONE launch (after an optimizer step, instead of one pack launch per image).
+ * descs_dev: n descriptors IN DEVICE MEMORY, sorted by `start` = index of the image's first element in the concatenated element
+ * space [0, total); the kinds may be mixed (elements are 4 bytes for the fp32 kinds, 2 for bf16; `start` counts elements).
+ * The caller sets w, wp, w_base .. w_stap, Cout, Cin, K and `start`; set_fill_pack_desc (host) fills kind and the layout fields --
+ * it is the one place that holds the padding rules of the images -- and returns the image's element count, which is what the
+ * set_packed_conv_weight*_size entries return (-1: bad arguments).  `dil` matters to SET_IMG_F32_BIG only. */
+#define SET_IMG_F32 0     /* fp32 small-tile: the image of set_pack_conv_weight (SET_IMPL_MFMA) */
+#define SET_IMG_F32_BIG 1 /* fp32 big-tile: the image of set_pack_conv_weight_v2 (SET_IMPL_MFMA2) */
+#define SET_IMG_BF16 2    /* bf16: the image of set_pack_conv_weight_bf16 (SET_IMPL_BF16) */
+typedef struct SetPackDesc {
     const float *w;
     void *wp;
     int64_t w_base, w_sco, w_sci, w_stap, start;
-    int32_t Cout, Cin, K, CoutP, CinP, pad_;
-} SetPackBf16Desc;
-int64_t set_sizeof_pack_bf16_desc(void);
-int set_pack_conv_weights_bf16_batch(const SetPackBf16Desc *descs_dev, int32_t n, int64_t total, void *stream);
-/* The same for the fp32 images (training in the reference's default precision, egs/spec_denoiser.yaml:4): every image of
- * set_pack_conv_weight (kind 0) / set_pack_conv_weight_v2 (kind 1) a step used, re-packed in ONE launch after the optimizer step.
- * The caller sets w, wp, w_base .. w_stap, Cout, Cin, K and `start`; set_fill_pack_f32_desc (host) fills kind and the layout
- * fields and returns the image's element count (-1: bad arguments).  The table lives on the device. */
-typedef struct SetPackF32Desc {
-    const float *w;
-    float *wp;
-    int64_t w_base, w_sco, w_sci, w_stap, start;
-    int32_t Cout, Cin, K, CinP, kind, RB, ch_max, pad_;
-} SetPackF32Desc;
-int64_t set_sizeof_pack_f32_desc(void);
-int64_t set_fill_pack_f32_desc(SetPackF32Desc *d, int32_t kind, int32_t dil);
-int set_pack_conv_weights_f32_batch(const SetPackF32Desc *descs_dev, int32_t n, int64_t total, void *stream);
+    int32_t Cout, Cin, K, kind;
+    int32_t CinP, CoutP, RB, ch_max; /* padded channels / rows; big-tile: rows per block / 128, channels per LDS chunk */
+} SetPackDesc;
+int64_t set_sizeof_pack_desc(void);
+int64_t set_fill_pack_desc(SetPackDesc *d, int32_t kind, int32_t dil);
+int set_pack_conv_weights_batch(const SetPackDesc *descs_dev, int32_t n, int64_t total, void *stream);
 
 /* Reductions of the training path.  Every sum that feeds a loss or a gradient is ordered: the entry points below write one
  * partial result per block / slice into `scratch` and combine them in a fixed order, so the result is bit-identical from

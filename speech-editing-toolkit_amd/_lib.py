@@ -17,7 +17,7 @@ INCLUDE = os.path.join(_ROOT, "include")
 LIB_PATH = os.path.join(_PKG, "libset_amd.so")
 # measurement only (tools/build_exp.sh): load an experimental build of the library instead; never built or rebuilt from here
 _LIB_OVERRIDE = os.environ.get("SET_AMD_LIB")
-SOURCES = ["conv1d.hip", "conv_x2.hip", "resblock_x2.hip", "glue.hip", "diffnet.hip", "diffnet_x3.hip", "boundary.hip", "diffusion_ops.hip", "diffusion_loop.hip",
+SOURCES = ["conv1d.hip", "weight_image.hip", "conv_x2.hip", "resblock_x2.hip", "glue.hip", "diffnet.hip", "diffnet_x3.hip", "boundary.hip", "diffusion_ops.hip", "diffusion_loop.hip",
            "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip", "melspec.hip", "mcd.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
@@ -140,20 +140,15 @@ class SetResblockPairArgs(C.Structure):
     ]
 
 
-class SetPackBf16Desc(C.Structure):
+IMG_F32, IMG_F32_BIG, IMG_BF16 = 0, 1, 2  # SetPackDesc.kind: the three packed conv-weight layouts (SET_IMG_*)
+
+
+class SetPackDesc(C.Structure):
     _fields_ = [
         ("w", C.c_void_p), ("wp", C.c_void_p),
         ("w_base", C.c_int64), ("w_sco", C.c_int64), ("w_sci", C.c_int64), ("w_stap", C.c_int64), ("start", C.c_int64),
-        ("Cout", C.c_int32), ("Cin", C.c_int32), ("K", C.c_int32), ("CoutP", C.c_int32), ("CinP", C.c_int32), ("pad_", C.c_int32),
-    ]
-
-
-class SetPackF32Desc(C.Structure):
-    _fields_ = [
-        ("w", C.c_void_p), ("wp", C.c_void_p),
-        ("w_base", C.c_int64), ("w_sco", C.c_int64), ("w_sci", C.c_int64), ("w_stap", C.c_int64), ("start", C.c_int64),
-        ("Cout", C.c_int32), ("Cin", C.c_int32), ("K", C.c_int32), ("CinP", C.c_int32), ("kind", C.c_int32), ("RB", C.c_int32),
-        ("ch_max", C.c_int32), ("pad_", C.c_int32),
+        ("Cout", C.c_int32), ("Cin", C.c_int32), ("K", C.c_int32), ("kind", C.c_int32),
+        ("CinP", C.c_int32), ("CoutP", C.c_int32), ("RB", C.c_int32), ("ch_max", C.c_int32),
     ]
 
 
@@ -284,11 +279,9 @@ SIGNATURES = {
                                                _I32, _V, _I64, _V]),
     "set_packed_conv_weight_bf16_size": (_I64, [_I32, _I32, _I32]),
     "set_pack_conv_weight_bf16": (C.c_int, [_V, _V, _I32, _I32, _I32, _I64, _I64, _I64, _I64, _V]),
-    "set_sizeof_pack_bf16_desc": (_I64, []),
-    "set_pack_conv_weights_bf16_batch": (C.c_int, [_V, _I32, _I64, _V]),
-    "set_sizeof_pack_f32_desc": (_I64, []),
-    "set_fill_pack_f32_desc": (_I64, [C.POINTER(SetPackF32Desc), _I32, _I32]),
-    "set_pack_conv_weights_f32_batch": (C.c_int, [_V, _I32, _I64, _V]),
+    "set_sizeof_pack_desc": (_I64, []),
+    "set_fill_pack_desc": (_I64, [C.POINTER(SetPackDesc), _I32, _I32]),
+    "set_pack_conv_weights_batch": (C.c_int, [_V, _I32, _I64, _V]),
     "set_channel_sum_det": (C.c_int, [_V, _V, _I32, _I32, _I32, _V, _V]),
     "set_weighted_sum_det": (C.c_int, [_V, _V, _V, _I64, _I64, _V, _V]),
     "set_sumsq_det": (C.c_int, [_V, _V, _I64, _V, _V]),
@@ -445,8 +438,7 @@ def lib():
     assert L.set_sizeof_bmm_args() == C.sizeof(SetBmmArgs), "SetBmmArgs ABI mismatch"
     assert L.set_sizeof_resblock_pair_args() == C.sizeof(SetResblockPairArgs), "SetResblockPairArgs ABI mismatch"
     assert L.set_sizeof_attn_args() == C.sizeof(SetAttnArgs), "SetAttnArgs ABI mismatch"
-    assert L.set_sizeof_pack_bf16_desc() == C.sizeof(SetPackBf16Desc), "SetPackBf16Desc ABI mismatch"
-    assert L.set_sizeof_pack_f32_desc() == C.sizeof(SetPackF32Desc), "SetPackF32Desc ABI mismatch"
+    assert L.set_sizeof_pack_desc() == C.sizeof(SetPackDesc), "SetPackDesc ABI mismatch"
     assert L.set_sizeof_attn_bwd_args() == C.sizeof(SetAttnBwdArgs), "SetAttnBwdArgs ABI mismatch"
     assert L.set_sizeof_diffnet_layer_bf16_args() == C.sizeof(SetDiffnetLayerBf16Args), "SetDiffnetLayerBf16Args ABI mismatch"
     assert L.set_sizeof_diffnet_layers_bf16_args() == C.sizeof(SetDiffnetLayersBf16Args), "SetDiffnetLayersBf16Args ABI mismatch"

@@ -22,9 +22,6 @@
 
 #include "common.h"
 
-typedef __bf16 af_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned af_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned af_u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -32,9 +29,6 @@ constexpr int AF_KT = 32;  // keys per tile
 
 __device__ __forceinline__ unsigned af_pk(float lo, float hi) {
     return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)lo) | ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)hi) << 16);
-}
-__device__ __forceinline__ f32x16 af_mma16(af_u32x4 a, af_u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(af_bf16x8, a), __builtin_bit_cast(af_bf16x8, b), c, 0, 0, 0);
 }
 __device__ __forceinline__ float af_xor32(float v) { return __shfl_xor(v, 32, 64); }
 // key of accumulator register r of a lane in half `h` (32x32 MFMA output layout)
@@ -87,7 +81,7 @@ __device__ __forceinline__ void af_commit_dk(const float (&reg)[D * AF_KT / NT],
 // bf16: k-step j <-> d = 16 j + 8 half + e.  `mul` scales the values (the attention's q scaling).
 template <int D, bool BF16> struct AfFrag {
     float f[BF16 ? 1 : D / 2];
-    af_u32x4 b[BF16 ? D / 16 : 1];
+    u32x4_t b[BF16 ? D / 16 : 1];
 };
 template <int D, bool BF16>
 __device__ __forceinline__ void af_load_frag(AfFrag<D, BF16> &o, rsrc_t src, int cs, int t, int half, float mul) {
@@ -116,9 +110,9 @@ __device__ __forceinline__ void af_gemm_kd(f32x16 &acc, const unsigned char *ks,
     if constexpr (BF16) {
 #pragma unroll
         for (int j = 0; j < D / 16; ++j) {
-            const af_u32x4 a = *reinterpret_cast<const af_u32x4 *>(ks + l31 * AfTile<D, true>::KROW + (16 * j + 8 * half) * 2);
-            if (j & 1) a1 = af_mma16(a, fr.b[j], a1);
-            else acc = af_mma16(a, fr.b[j], acc);
+            const u32x4_t a = *reinterpret_cast<const u32x4_t *>(ks + l31 * AfTile<D, true>::KROW + (16 * j + 8 * half) * 2);
+            if (j & 1) a1 = mfma_bf16(a, fr.b[j], a1);
+            else acc = mfma_bf16(a, fr.b[j], acc);
         }
     } else {
 #pragma unroll
@@ -138,7 +132,7 @@ __device__ __forceinline__ void af_gemm_kd(f32x16 &acc, const unsigned char *ks,
 template <int D, bool BF16>
 __device__ __forceinline__ void af_gemm_dk(f32x16 (&acc)[D / 32], const unsigned char *vs, const f32x16 &p, int l31, int half) {
     if constexpr (BF16) {
-        af_u32x4 pb[2];
+        u32x4_t pb[2];
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -148,11 +142,11 @@ __device__ __forceinline__ void af_gemm_dk(f32x16 (&acc)[D / 32], const unsigned
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const unsigned char *row = vs + (32 * rb + l31) * AfTile<D, true>::VROW;
-                const af_u32x2 lo = *reinterpret_cast<const af_u32x2 *>(row + (16 * j + 4 * half) * 2);
-                const af_u32x2 hi = *reinterpret_cast<const af_u32x2 *>(row + (16 * j + 8 + 4 * half) * 2);
-                af_u32x4 a;
+                const u32x2_t lo = *reinterpret_cast<const u32x2_t *>(row + (16 * j + 4 * half) * 2);
+                const u32x2_t hi = *reinterpret_cast<const u32x2_t *>(row + (16 * j + 8 + 4 * half) * 2);
+                u32x4_t a;
                 a[0] = lo[0]; a[1] = lo[1]; a[2] = hi[0]; a[3] = hi[1];
-                acc[rb] = af_mma16(a, pb[j], acc[rb]);
+                acc[rb] = mfma_bf16(a, pb[j], acc[rb]);
             }
     } else {
 #pragma unroll

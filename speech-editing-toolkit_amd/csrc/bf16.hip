@@ -16,13 +16,9 @@
 // the SAME lane -> k map, so the contraction is right for any permutation of k the hardware applies inside an instruction.
 #include <stdlib.h>
 
-#include "common.h"
+#include "weight_image.h"
 #include "phase_probe.h"
-#include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -32,72 +28,6 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
     v[0] = (__bf16)lo;
     v[1] = (__bf16)hi;
     return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ unsigned short bf16_bits(float x) {
-    return __builtin_bit_cast(unsigned short, (__bf16)x);
-}
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
-static inline int round_up_i(int x, int m) { return (x + m - 1) / m * m; }
-
-// prologue with the code resolved at compile time: inside the staging loops a run-time `switch (pro)` per element turns
-// into a scalar branch tree (+ an IEEE division sequence) per element -- measured 7.5 us per 32-channel stage against
-// 0.3 us of MFMA work.  The callers switch ONCE per stage and instantiate the loop per code.
-template <int PRO>
-__device__ __forceinline__ float pro_c(float v, float p) {
-    if constexpr (PRO == SET_PRO_LRELU) return v > 0.0f ? v : v * p;
-    else if constexpr (PRO == SET_PRO_DIV) return v / p;
-    else return v;
-}
-template <int N> using ic = std::integral_constant<int, N>;
-
-// =====================================================================================================================
-// packed bf16 weight image:  wp[tap][chunk][row][32]   (row < CoutP = Cout rounded to 128, chunk < CinP/32, zero padded)
-// One (tap, chunk, 64..128-row block) is a contiguous run of 64-byte rows: a block copies it to LDS with 16-byte units.
-// =====================================================================================================================
-__global__ void __launch_bounds__(256) pack_conv_weight_bf16_kernel(const float *w, unsigned short *wp, int Cout, int Cin, int K,
-                                                                    int CoutP, int CinP, int64_t total, int64_t w_base,
-                                                                    int64_t w_sco, int64_t w_sci, int64_t w_stap) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int kk = (int)(idx & 31);
-    int64_t r = idx >> 5;
-    const int row = (int)(r % CoutP);
-    r /= CoutP;
-    const int nchunk = CinP / 32;
-    const int chunk = (int)(r % nchunk);
-    const int tap = (int)(r / nchunk);
-    const int ci = chunk * 32 + kk;
-    float v = 0.0f;
-    if (row < Cout && ci < Cin) v = w[w_base + (int64_t)row * w_sco + (int64_t)ci * w_sci + (int64_t)tap * w_stap];
-    wp[idx] = bf16_bits(v);
-}
-
-// every registered bf16 image in ONE launch (after the optimizer step: ~100 - 170 tiny pack launches per training step
-// otherwise): element idx of the concatenated image space -> its descriptor by binary search over `start`
-__global__ void __launch_bounds__(256) pack_conv_weights_bf16_batch_kernel(const SetPackBf16Desc *d, int n, int64_t total) {
-    const int64_t gidx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (gidx >= total) return;
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (d[mid].start <= gidx) lo = mid; else hi = mid - 1;
-    }
-    const SetPackBf16Desc e = d[lo];
-    const int64_t idx = gidx - e.start;
-    const int kk = (int)(idx & 31);
-    int64_t r = idx >> 5;
-    const int row = (int)(r % e.CoutP);
-    r /= e.CoutP;
-    const int nchunk = e.CinP / 32;
-    const int chunk = (int)(r % nchunk);
-    const int tap = (int)(r / nchunk);
-    const int ci = chunk * 32 + kk;
-    float v = 0.0f;
-    if (row < e.Cout && ci < e.Cin) v = e.w[e.w_base + (int64_t)row * e.w_sco + (int64_t)ci * e.w_sci + (int64_t)tap * e.w_stap];
-    reinterpret_cast<unsigned short *>(e.wp)[idx] = bf16_bits(v);
 }
 
 // ---- epilogue (fp32) of the bf16 conv kernels: v = act((acc + bias) * alpha) + res ; * mask ; (+ previous output, / out_div) ----
@@ -228,7 +158,7 @@ __global__ void __launch_bounds__(256, 2) conv1d_bf16_kernel(SetConv1dArgs a, in
 
     // ---- staging registers (one stage ahead) ----
     float pv[NPASS][CPT], pa[ADD ? CPT : 1];  // (dead under VEC)
-    u32x4 au[AU_MAX];
+    u32x4_t au[AU_MAX];
     // VEC: unit u = tid + 256 j -> frame quad u >> 3 (frames F0 + 4 (u >> 3) .., F0 = t0 + lo rounded down to a multiple of 4), channel
     // quad u & 7 of the 32-channel chunk; NQ quads cover the R rows of the tile
     constexpr int VQMAX = (64 * WN + 16 + 3) / 4 + 1, VJ = (VQMAX * 8 + 255) / 256;
@@ -291,9 +221,9 @@ __global__ void __launch_bounds__(256, 2) conv1d_bf16_kernel(SetConv1dArgs a, in
                     // own wait, made the commit phase a third of a stage, profiles/r06_conv_phase_probe.log)
                     const int row = 4 * q + e - vsh;
                     const int rw = (q < vNQ && row >= 0 && row < R) ? row : R;
-                    u32x2 w;
+                    u32x2_t w;
                     w[0] = pack_bf16(x[0], x[1]); w[1] = pack_bf16(x[2], x[3]);
-                    *reinterpret_cast<u32x2 *>(Bs + rw * ROWB + cq * 8) = w;
+                    *reinterpret_cast<u32x2_t *>(Bs + rw * ROWB + cq * 8) = w;
                 }
             }
             return;
@@ -314,10 +244,10 @@ __global__ void __launch_bounds__(256, 2) conv1d_bf16_kernel(SetConv1dArgs a, in
             if (row < R) {
 #pragma unroll
                 for (int q = 0; q < CPT / 8; ++q) {
-                    u32x4 u;
+                    u32x4_t u;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) u[e] = pack_bf16(x[8 * q + 2 * e], x[8 * q + 2 * e + 1]);
-                    *reinterpret_cast<u32x4 *>(Bs + row * ROWB + (scg * CPT + 8 * q) * 2) = u;
+                    *reinterpret_cast<u32x4_t *>(Bs + row * ROWB + (scg * CPT + 8 * q) * 2) = u;
                 }
             }
         }
@@ -332,7 +262,7 @@ __global__ void __launch_bounds__(256, 2) conv1d_bf16_kernel(SetConv1dArgs a, in
             const int part = u & 3, row = (u >> 2) % MB, h = ((u >> 2) / MB) % (KCH / 32), tl = (u >> 2) / (MB * (KCH / 32));
             const int ch32 = min(c0 / 32 + h, nchunk32 - 1);
             const int64_t e = ((((int64_t)(tg0 + tl) * nchunk32 + ch32) * CoutP + r0 + row) * 32 + part * 8);
-            au[q] = *reinterpret_cast<const u32x4 *>(wimg + e);
+            au[q] = *reinterpret_cast<const u32x4_t *>(wimg + e);
         }
     };
     auto commit_a = [&](int c0, int tgn) {
@@ -342,9 +272,9 @@ __global__ void __launch_bounds__(256, 2) conv1d_bf16_kernel(SetConv1dArgs a, in
             const int u = tid + 256 * q;
             if (u < units) {
                 const int part = u & 3, row = (u >> 2) % MB, h = ((u >> 2) / MB) % (KCH / 32), tl = (u >> 2) / (MB * (KCH / 32));
-                u32x4 v = au[q];
-                if (c0 + 32 * h >= CinP) v = (u32x4){0u, 0u, 0u, 0u};  // KCH = 64 over an odd number of 32-channel chunks
-                *reinterpret_cast<u32x4 *>(As + (tl * MB + row) * ROWB + h * 64 + part * 16) = v;
+                u32x4_t v = au[q];
+                if (c0 + 32 * h >= CinP) v = (u32x4_t){0u, 0u, 0u, 0u};  // KCH = 64 over an odd number of 32-channel chunks
+                *reinterpret_cast<u32x4_t *>(As + (tl * MB + row) * ROWB + h * 64 + part * 16) = v;
             }
         }
     };
@@ -381,10 +311,10 @@ __global__ void __launch_bounds__(256, 2) conv1d_bf16_kernel(SetConv1dArgs a, in
             const unsigned char *bp = Bs + (wn * 64 + l31 + off) * ROWB + half * 16;
 #pragma unroll
             for (int ks = 0; ks < KCH / 16; ++ks) {
-                const u32x4 a0 = *reinterpret_cast<const u32x4 *>(ap + ks * 32);
-                const u32x4 a1 = *reinterpret_cast<const u32x4 *>(ap + 32 * ROWB + ks * 32);
-                const u32x4 b0 = *reinterpret_cast<const u32x4 *>(bp + ks * 32);
-                const u32x4 b1 = *reinterpret_cast<const u32x4 *>(bp + 32 * ROWB + ks * 32);
+                const u32x4_t a0 = *reinterpret_cast<const u32x4_t *>(ap + ks * 32);
+                const u32x4_t a1 = *reinterpret_cast<const u32x4_t *>(ap + 32 * ROWB + ks * 32);
+                const u32x4_t b0 = *reinterpret_cast<const u32x4_t *>(bp + ks * 32);
+                const u32x4_t b1 = *reinterpret_cast<const u32x4_t *>(bp + 32 * ROWB + ks * 32);
                 acc[0][0] = mfma_bf16(a0, b0, acc[0][0]);
                 acc[0][1] = mfma_bf16(a0, b1, acc[0][1]);
                 acc[1][0] = mfma_bf16(a1, b0, acc[1][0]);
@@ -449,12 +379,12 @@ __global__ void __launch_bounds__(256, 2) conv1x1_oneshot_bf16_kernel(SetConv1dA
         return (unsigned)(((min(ks >> 1, nchunk32 - 1) * CoutP + r0 + wm * 64 + i * 32 + l31) * 32 + (ks & 1) * 16 + half * 8) * 2);
     };
     constexpr int RING = NKS < 4 ? NKS : 4;
-    u32x4 A[RING][2];
+    u32x4_t A[RING][2];
     auto commit = [&](auto PROC, int c0) __attribute__((always_inline)) {
         constexpr int kPro = decltype(PROC)::value;
 #pragma unroll
         for (int q = 0; q < CPT / 8; ++q) {
-            u32x4 u;
+            u32x4_t u;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float v0 = pro_c<kPro>(pv[8 * q + 2 * e], a.pro_param), v1 = pro_c<kPro>(pv[8 * q + 2 * e + 1], a.pro_param);
@@ -462,7 +392,7 @@ __global__ void __launch_bounds__(256, 2) conv1x1_oneshot_bf16_kernel(SetConv1dA
                 v1 = (tv && c0 + scg * CPT + 8 * q + 2 * e + 1 < a.Cin) ? v1 : 0.0f;
                 u[e] = pack_bf16(v0, v1);
             }
-            *reinterpret_cast<u32x4 *>(Bs + sf * ROWB + (scg * CPT + 8 * q) * 2) = u;
+            *reinterpret_cast<u32x4_t *>(Bs + sf * ROWB + (scg * CPT + 8 * q) * 2) = u;
         }
     };
 
@@ -489,8 +419,8 @@ __global__ void __launch_bounds__(256, 2) conv1x1_oneshot_bf16_kernel(SetConv1dA
         if (c + 1 < nchunks) issue(c0 + CINP);  // the next chunk's loads fly under this chunk's MFMAs
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks) {  // pinned k-step order (round 4): B reads | MFMAs straight from the ring slot | refill of that slot
-            const u32x4 b0 = *reinterpret_cast<const u32x4 *>(bp + ks * 32);
-            const u32x4 b1 = *reinterpret_cast<const u32x4 *>(bp + 32 * ROWB + ks * 32);
+            const u32x4_t b0 = *reinterpret_cast<const u32x4_t *>(bp + ks * 32);
+            const u32x4_t b1 = *reinterpret_cast<const u32x4_t *>(bp + 32 * ROWB + ks * 32);
             acc[0][0] = mfma_bf16(A[ks % RING][0], b0, acc[0][0]);
             acc[0][1] = mfma_bf16(A[ks % RING][0], b1, acc[0][1]);
             acc[1][0] = mfma_bf16(A[ks % RING][1], b0, acc[1][0]);
@@ -507,12 +437,12 @@ __global__ void __launch_bounds__(256, 2) conv1x1_oneshot_bf16_kernel(SetConv1dA
 
 template <int CINP>
 static int launch_conv1x1_oneshot(const SetConv1dArgs &a, hipStream_t s) {
-    const int CoutP = round_up_i(a.Cout, 128);
+    const int CoutP = set_round_up(a.Cout, BF16_IMG_ROWS);
     const size_t lds = (size_t)128 * (CINP * 2 + 16);
     static SetDeviceOnce lds_once;
     if (int rc = set_lds_optin(lds_once, 96 * 1024, "conv 1x1 attr", conv1x1_oneshot_bf16_kernel<CINP>)) return rc;
     dim3 grid((a.T_iter + 127) / 128, (a.Cout + 127) / 128, a.B), block(256);
-    hipLaunchKernelGGL((conv1x1_oneshot_bf16_kernel<CINP>), grid, block, lds, s, a, CoutP, round_up_i(a.Cin, 32) / 32);
+    hipLaunchKernelGGL((conv1x1_oneshot_bf16_kernel<CINP>), grid, block, lds, s, a, CoutP, set_round_up(a.Cin, BF16_IMG_CH) / 32);
     return set_check_launch("set_conv1d(bf16, 1x1)");
 }
 
@@ -525,7 +455,7 @@ static int launch_conv_bf16(const SetConv1dArgs &a, int lo, int halo, hipStream_
         if (env && al && halo <= 16) return launch_conv_bf16<WM, WN, KCH, TGM, HALO, ADD, true>(a, lo, halo, s);
     }
     constexpr int MB = 64 * WM, NB = 64 * WN, ROWB = KCH * 2 + 16, BF_TG_MAX = TGM;
-    const int CinP = round_up_i(a.Cin, 32), CoutP = round_up_i(a.Cout, 128);
+    const int CinP = set_round_up(a.Cin, BF16_IMG_CH), CoutP = set_round_up(a.Cout, BF16_IMG_ROWS);
     const size_t lds = (size_t)BF_TG_MAX * MB * ROWB + (size_t)(NB + halo + (VEC ? 1 : 0)) * ROWB;  // (VEC: one spare row for the masked-out writes)
     static SetDeviceOnce lds_once;  // (96 KiB: two blocks per CU)
     if (int rc = set_lds_optin(lds_once, 96 * 1024, "conv bf16 attr", conv1d_bf16_kernel<WM, WN, KCH, TGM, HALO, ADD, VEC>)) return rc;
@@ -571,8 +501,8 @@ __device__ __forceinline__ unsigned buf_load_raw16(rsrc_t r, unsigned voff, unsi
 __device__ __forceinline__ unsigned q4_row(int c, int T) { return (unsigned)((c >> 2) * T) * 8u + (unsigned)(c & 3) * 2u; }
 // 8 frames x 4 channels (four 16-byte units of 2 frames x 4 channels, consecutive in memory) -> channel c's 8 frames as one 16-byte row piece
 template <int N>
-__device__ __forceinline__ u32x4 q4_channel(const unsigned (&u)[N], int c) {
-    u32x4 o;
+__device__ __forceinline__ u32x4_t q4_channel(const unsigned (&u)[N], int c) {
+    u32x4_t o;
 #pragma unroll
     for (int k = 0; k < 4; ++k)  // unit k: dwords {f0: c0 c1 | c2 c3, f1: c0 c1 | c2 c3}
         o[k] = __builtin_amdgcn_perm(u[4 * k + 2 + (c >> 1)], u[4 * k + (c >> 1)], (c & 1) ? 0x07060302u : 0x05040100u);
@@ -634,14 +564,14 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_bf16_kernel(WgradBf16Args
             const unsigned vo = (unsigned)(min((co0 >> 2) + urow, (a.Cout >> 2) - 1) * a.T + min(t0 + 8 * ucol, a.T - 8)) * 8u;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const u32x4 v = (u32x4)__builtin_amdgcn_raw_buffer_load_b128(d_g, (int)(vo + 16u * q), 0, 0);
+                const u32x4_t v = (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(d_g, (int)(vo + 16u * q), 0, 0);
                 gv[4 * q] = v[0]; gv[4 * q + 1] = v[1]; gv[4 * q + 2] = v[2]; gv[4 * q + 3] = v[3];
             }
         } else if constexpr (fastg) {  // fp32: 16 bytes = 4 frames
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const unsigned vo = (unsigned)(min(co0 + urow4 + 16 * q, a.Cout - 1) * a.T + min(t0 + 4 * ucol4, a.T - 4)) * 4u;
-                const u32x4 v = (u32x4)__builtin_amdgcn_raw_buffer_load_b128(d_g, (int)vo, 0, 0);
+                const u32x4_t v = (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(d_g, (int)vo, 0, 0);
                 gv[4 * q] = v[0]; gv[4 * q + 1] = v[1]; gv[4 * q + 2] = v[2]; gv[4 * q + 3] = v[3];
             }
         } else {
@@ -655,7 +585,7 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_bf16_kernel(WgradBf16Args
             const unsigned vo = (unsigned)(min((ci0 >> 2) + urow, (a.Cin >> 2) - 1) * a.T_in + min(t0 + 8 * ucol, a.T_in - 8)) * 8u;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const u32x4 v = (u32x4)__builtin_amdgcn_raw_buffer_load_b128(d_x, (int)(vo + 16u * q), 0, 0);
+                const u32x4_t v = (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(d_x, (int)(vo + 16u * q), 0, 0);
                 xv[4 * q] = v[0]; xv[4 * q + 1] = v[1]; xv[4 * q + 2] = v[2]; xv[4 * q + 3] = v[3];
             }
         } else if constexpr (fastx) {  // fp32: 16 bytes = 4 frames; the per-channel add of the unit's row rides along (dummy address without one)
@@ -663,7 +593,7 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_bf16_kernel(WgradBf16Args
             for (int q = 0; q < 8; ++q) {
                 const int cic = min(ci0 + urow4 + 16 * q, a.Cin - 1);
                 const unsigned vo = (unsigned)(cic * a.T_in + min(t0 + 4 * ucol4, a.T_in - 4)) * 4u;
-                const u32x4 v = (u32x4)__builtin_amdgcn_raw_buffer_load_b128(d_x, (int)vo, 0, 0);
+                const u32x4_t v = (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(d_x, (int)vo, 0, 0);
                 xv[4 * q] = v[0]; xv[4 * q + 1] = v[1]; xv[4 * q + 2] = v[2]; xv[4 * q + 3] = v[3];
                 av[q] = buf_load(d_a, (unsigned)cic * 4u, 0u);
             }
@@ -686,10 +616,10 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_bf16_kernel(WgradBf16Args
             for (int c = 0; c < 4; ++c) {  // the 8 frames of channel 4 urow + c, cut out of the thread's 8 frames x 4 channels
                 const int row = 4 * urow + c;
                 const bool ok = t0 + 8 * ucol < a.T && co0 + row < a.Cout;  // T % 8 == 0, Cout % 4 == 0: entirely inside or outside
-                const u32x4 w = q4_channel(gv, c);
-                u32x4 v;
+                const u32x4_t w = q4_channel(gv, c);
+                u32x4_t v;
                 v[0] = ok ? w[0] : 0u; v[1] = ok ? w[1] : 0u; v[2] = ok ? w[2] : 0u; v[3] = ok ? w[3] : 0u;
-                *reinterpret_cast<u32x4 *>(Gs + row * WGB_ROWB + ucol * 16) = v;
+                *reinterpret_cast<u32x4_t *>(Gs + row * WGB_ROWB + ucol * 16) = v;
             }
         } else if constexpr (fastg) {
 #pragma unroll
@@ -698,11 +628,11 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_bf16_kernel(WgradBf16Args
                 const bool ok = t0 + 4 * ucol4 < a.T && co0 + row < a.Cout;  // T % 4 == 0
                 unsigned short h[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) h[e] = bf16_bits(__builtin_bit_cast(float, gv[4 * q + e]));
-                u32x2 w;
+                for (int e = 0; e < 4; ++e) h[e] = f2bf(__builtin_bit_cast(float, gv[4 * q + e]));
+                u32x2_t w;
                 w[0] = ok ? ((unsigned)h[0] | ((unsigned)h[1] << 16)) : 0u;
                 w[1] = ok ? ((unsigned)h[2] | ((unsigned)h[3] << 16)) : 0u;
-                *reinterpret_cast<u32x2 *>(Gs + row * WGB_ROWB + ucol4 * 8) = w;
+                *reinterpret_cast<u32x2_t *>(Gs + row * WGB_ROWB + ucol4 * 8) = w;
             }
         }
         if constexpr (fastx && XB16) {
@@ -710,10 +640,10 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_bf16_kernel(WgradBf16Args
             for (int c = 0; c < 4; ++c) {
                 const int row = 4 * urow + c;
                 const bool ok = t0 + 8 * ucol < a.T && t0 + 8 * ucol < a.T_in && ci0 + row < a.Cin;
-                const u32x4 w = q4_channel(xv, c);
-                u32x4 v;
+                const u32x4_t w = q4_channel(xv, c);
+                u32x4_t v;
                 v[0] = ok ? w[0] : 0u; v[1] = ok ? w[1] : 0u; v[2] = ok ? w[2] : 0u; v[3] = ok ? w[3] : 0u;
-                *reinterpret_cast<u32x4 *>(Xs + row * WGB_ROWB + ucol * 16) = v;
+                *reinterpret_cast<u32x4_t *>(Xs + row * WGB_ROWB + ucol * 16) = v;
             }
         } else if constexpr (fastx) {
 #pragma unroll
@@ -724,12 +654,12 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_bf16_kernel(WgradBf16Args
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float xf = __builtin_bit_cast(float, xv[4 * q + e]);
-                    h[e] = bf16_bits(pro_c<kPro>(has_add ? xf + av[q] : xf, a.pro_param));  // same arithmetic as the element-wise path
+                    h[e] = f2bf(pro_c<kPro>(has_add ? xf + av[q] : xf, a.pro_param));  // same arithmetic as the element-wise path
                 }
-                u32x2 w;
+                u32x2_t w;
                 w[0] = ok ? ((unsigned)h[0] | ((unsigned)h[1] << 16)) : 0u;
                 w[1] = ok ? ((unsigned)h[2] | ((unsigned)h[3] << 16)) : 0u;
-                *reinterpret_cast<u32x2 *>(Xs + row * WGB_ROWB + ucol4 * 8) = w;
+                *reinterpret_cast<u32x2_t *>(Xs + row * WGB_ROWB + ucol4 * 8) = w;
             }
         }
         if constexpr (!fastg || !fastx) {
@@ -738,11 +668,11 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_bf16_kernel(WgradBf16Args
                 const int row = sr0 + 4 * j;
                 unsigned short gb, xb;
                 if constexpr (GB16) gb = (unsigned short)gv[j];
-                else gb = bf16_bits(__builtin_bit_cast(float, gv[j]));
+                else gb = f2bf(__builtin_bit_cast(float, gv[j]));
                 if constexpr (XB16) xb = (unsigned short)xv[j];
                 else {
                     const float xf = __builtin_bit_cast(float, xv[j]);
-                    xb = bf16_bits(pro_c<kPro>(has_add ? xf + av[j] : xf, a.pro_param));  // unconditional, then select
+                    xb = f2bf(pro_c<kPro>(has_add ? xf + av[j] : xf, a.pro_param));  // unconditional, then select
                 }
                 if constexpr (!fastg) *reinterpret_cast<unsigned short *>(Gs + row * WGB_ROWB + sk * 2) = (tv && co0 + row < a.Cout) ? gb : (unsigned short)0;
                 if constexpr (!fastx) *reinterpret_cast<unsigned short *>(Xs + row * WGB_ROWB + sk * 2) = (tiv && ci0 + row < a.Cin) ? xb : (unsigned short)0;
@@ -763,10 +693,10 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_bf16_kernel(WgradBf16Args
         const unsigned char *bp = Xs + (wn * 64 + l31) * WGB_ROWB + half * 16;
 #pragma unroll
         for (int ks = 0; ks < WGB_KT / 16; ++ks) {
-            const u32x4 a0 = *reinterpret_cast<const u32x4 *>(ap + ks * 32);
-            const u32x4 a1 = *reinterpret_cast<const u32x4 *>(ap + 32 * WGB_ROWB + ks * 32);
-            const u32x4 b0 = *reinterpret_cast<const u32x4 *>(bp + ks * 32);
-            const u32x4 b1 = *reinterpret_cast<const u32x4 *>(bp + 32 * WGB_ROWB + ks * 32);
+            const u32x4_t a0 = *reinterpret_cast<const u32x4_t *>(ap + ks * 32);
+            const u32x4_t a1 = *reinterpret_cast<const u32x4_t *>(ap + 32 * WGB_ROWB + ks * 32);
+            const u32x4_t b0 = *reinterpret_cast<const u32x4_t *>(bp + ks * 32);
+            const u32x4_t b1 = *reinterpret_cast<const u32x4_t *>(bp + 32 * WGB_ROWB + ks * 32);
             acc[0][0] = mfma_bf16(a0, b0, acc[0][0]);
             acc[0][1] = mfma_bf16(a0, b1, acc[0][1]);
             acc[1][0] = mfma_bf16(a1, b0, acc[1][0]);
@@ -839,7 +769,7 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad3_bf16_kernel(WgradBf16Arg
             const unsigned vo = (unsigned)(min((co0 >> 2) + urow, (a.Cout >> 2) - 1) * a.T + min(t0 + 8 * ucol, a.T - 8)) * 8u;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const u32x4 v = (u32x4)__builtin_amdgcn_raw_buffer_load_b128(d_g, (int)(vo + 16u * q), 0, 0);
+                const u32x4_t v = (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(d_g, (int)(vo + 16u * q), 0, 0);
                 gv[4 * q] = v[0]; gv[4 * q + 1] = v[1]; gv[4 * q + 2] = v[2]; gv[4 * q + 3] = v[3];
             }
         } else {
@@ -867,10 +797,10 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad3_bf16_kernel(WgradBf16Arg
             for (int c = 0; c < 4; ++c) {
                 const int row = 4 * urow + c;
                 const bool ok = t0 + 8 * ucol < a.T && co0 + row < a.Cout;
-                const u32x4 w = q4_channel(gv, c);
-                u32x4 v;
+                const u32x4_t w = q4_channel(gv, c);
+                u32x4_t v;
                 v[0] = ok ? w[0] : 0u; v[1] = ok ? w[1] : 0u; v[2] = ok ? w[2] : 0u; v[3] = ok ? w[3] : 0u;
-                *reinterpret_cast<u32x4 *>(Gs + row * WGB_ROWB + ucol * 16) = v;
+                *reinterpret_cast<u32x4_t *>(Gs + row * WGB_ROWB + ucol * 16) = v;
             }
         } else {
 #pragma unroll
@@ -878,7 +808,7 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad3_bf16_kernel(WgradBf16Arg
                 const int row = sr0 + 4 * j;
                 unsigned short gb;
                 if constexpr (GB16) gb = (unsigned short)gv[j];
-                else gb = bf16_bits(__builtin_bit_cast(float, gv[j]));
+                else gb = f2bf(__builtin_bit_cast(float, gv[j]));
                 *reinterpret_cast<unsigned short *>(Gs + row * WGB_ROWB + sk * 2) = (tv && co0 + row < a.Cout) ? gb : (unsigned short)0;
             }
         }
@@ -887,8 +817,8 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad3_bf16_kernel(WgradBf16Arg
             const int row = sr0 + 4 * j;
             const bool cv = ci0 + row < a.Cin;
             const float ad = has_add ? av[j] : 0.0f;
-            const unsigned short ba = (va && cv) ? bf16_bits(xa[j] + ad) : (unsigned short)0;
-            const unsigned short bb = (vb && cv) ? bf16_bits(xb[j] + ad) : (unsigned short)0;
+            const unsigned short ba = (va && cv) ? f2bf(xa[j] + ad) : (unsigned short)0;
+            const unsigned short bb = (vb && cv) ? f2bf(xb[j] + ad) : (unsigned short)0;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 // value at tile offset q (= sk or 64 + sk, frame t0 - pad + q) is column q - k dil of copy k
@@ -908,11 +838,11 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad3_bf16_kernel(WgradBf16Arg
         const unsigned char *ap = Gs + (wm * 64 + l31) * WGB_ROWB + half * 16;
 #pragma unroll
         for (int ks = 0; ks < WGB_KT / 16; ++ks) {
-            const u32x4 a0 = *reinterpret_cast<const u32x4 *>(ap + ks * 32);
-            const u32x4 a1 = *reinterpret_cast<const u32x4 *>(ap + 32 * WGB_ROWB + ks * 32);
+            const u32x4_t a0 = *reinterpret_cast<const u32x4_t *>(ap + ks * 32);
+            const u32x4_t a1 = *reinterpret_cast<const u32x4_t *>(ap + 32 * WGB_ROWB + ks * 32);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                const u32x4 bk = *reinterpret_cast<const u32x4 *>(Xs + (k * 64 + wn * 32 + l31) * WGB_ROWB + half * 16 + ks * 32);
+                const u32x4_t bk = *reinterpret_cast<const u32x4_t *>(Xs + (k * 64 + wn * 32 + l31) * WGB_ROWB + half * 16 + ks * 32);
                 acc[k][0] = mfma_bf16(a0, bk, acc[k][0]);
                 acc[k][1] = mfma_bf16(a1, bk, acc[k][1]);
             }
@@ -947,13 +877,13 @@ constexpr int WGT_XF = WGB_KT + 16;         // frames of an X row: chunk + 8 hal
 constexpr int WGT_XROWB = WGT_XF * 2 + 16;  // 176 bytes: conflict-free 16-byte reads (44 dwords per row)
 
 template <int O>
-__device__ __forceinline__ u32x4 wgt_window(const u32x4 (&W)[3]) {  // 8 bf16 starting at element O of the 24 in W
+__device__ __forceinline__ u32x4_t wgt_window(const u32x4_t (&W)[3]) {  // 8 bf16 starting at element O of the 24 in W
     unsigned w[12];
 #pragma unroll
     for (int g = 0; g < 3; ++g)
 #pragma unroll
         for (int e = 0; e < 4; ++e) w[4 * g + e] = W[g][e];
-    u32x4 o;
+    u32x4_t o;
     if constexpr (O % 2 == 0) {
 #pragma unroll
         for (int d = 0; d < 4; ++d) o[d] = w[O / 2 + d];
@@ -965,7 +895,7 @@ __device__ __forceinline__ u32x4 wgt_window(const u32x4 (&W)[3]) {  // 8 bf16 st
 }
 
 template <int K, int PAD, int TAP = 0>
-__device__ __forceinline__ void wgt_taps(f32x16 (&acc)[K], u32x4 av, const u32x4 (&W)[3]) {
+__device__ __forceinline__ void wgt_taps(f32x16 (&acc)[K], u32x4_t av, const u32x4_t (&W)[3]) {
     if constexpr (TAP < K) {
         acc[TAP] = mfma_bf16(av, wgt_window<8 + TAP - PAD>(W), acc[TAP]);
         wgt_taps<K, PAD, TAP + 1>(acc, av, W);
@@ -1016,8 +946,8 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_taps_bf16_kernel(WgradBf1
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int row = wave + 4 * j;
-            const unsigned short gb = bf16_bits(__builtin_bit_cast(float, gv[j]));
-            const unsigned short xb = bf16_bits(pro_c<kPro>(__builtin_bit_cast(float, xv[j]), a.pro_param));
+            const unsigned short gb = f2bf(__builtin_bit_cast(float, gv[j]));
+            const unsigned short xb = f2bf(pro_c<kPro>(__builtin_bit_cast(float, xv[j]), a.pro_param));
             *reinterpret_cast<unsigned short *>(Gs + row * WGB_ROWB + lane * 2) = (tv && co0 + row < a.Cout) ? gb : (unsigned short)0;
             *reinterpret_cast<unsigned short *>(Xs + row * WGT_XROWB + lane * 2) = (xvld && ci0 + row < a.Cin) ? xb : (unsigned short)0;
         }
@@ -1025,13 +955,12 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_taps_bf16_kernel(WgradBf1
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int ti = t0 + 56 + ef + e;
-            const unsigned short xb = bf16_bits(pro_c<kPro>(__builtin_bit_cast(float, xe[e]), a.pro_param));
+            const unsigned short xb = f2bf(pro_c<kPro>(__builtin_bit_cast(float, xe[e]), a.pro_param));
             q[e] = (ti >= 0 && ti < a.T_in && ci0 + er < a.Cin) ? xb : (unsigned short)0;
         }
-        typedef unsigned wgt_u32x2 __attribute__((ext_vector_type(2)));
-        wgt_u32x2 u;
+        u32x2_t u;
         u[0] = (unsigned)q[0] | ((unsigned)q[1] << 16); u[1] = (unsigned)q[2] | ((unsigned)q[3] << 16);
-        *reinterpret_cast<wgt_u32x2 *>(Xs + er * WGT_XROWB + (64 + ef) * 2) = u;
+        *reinterpret_cast<u32x2_t *>(Xs + er * WGT_XROWB + (64 + ef) * 2) = u;
     };
     if (c_begin < c_end) issue(c_begin);
     for (int ch = c_begin; ch < c_end; ++ch) {
@@ -1049,10 +978,10 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad_taps_bf16_kernel(WgradBf1
         const unsigned char *bp = Xs + (wn * 32 + l31) * WGT_XROWB + half * 16;
 #pragma unroll
         for (int ks = 0; ks < WGB_KT / 16; ++ks) {
-            const u32x4 av = *reinterpret_cast<const u32x4 *>(ap + ks * 32);
-            u32x4 W[3];
+            const u32x4_t av = *reinterpret_cast<const u32x4_t *>(ap + ks * 32);
+            u32x4_t W[3];
 #pragma unroll
-            for (int g = 0; g < 3; ++g) W[g] = *reinterpret_cast<const u32x4 *>(bp + ks * 32 + g * 16);
+            for (int g = 0; g < 3; ++g) W[g] = *reinterpret_cast<const u32x4_t *>(bp + ks * 32 + g * 16);
             wgt_taps<K, PAD>(acc, av, W);
         }
     }
@@ -1112,7 +1041,7 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad3u_bf16_kernel(WgradBf16Ar
 #pragma unroll
     for (int q = 0; q < XQ; ++q) { const int u = tid + 256 * q; xr[q] = u / XU_ROW; xc[q] = u - xr[q] * XU_ROW; }
     unsigned gv[16];
-    u32x4 xv[XQ];
+    u32x4_t xv[XQ];
     float av[XQ];
     auto issue = [&](int ch) {
         const int b = ch / a.n_chunks_t, t0 = (ch % a.n_chunks_t) * WGB_KT;
@@ -1122,14 +1051,14 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad3u_bf16_kernel(WgradBf16Ar
         const unsigned vog = (unsigned)(min((co0 >> 2) + urow, (a.Cout >> 2) - 1) * a.T + min(t0 + 8 * ucol, a.T - 8)) * 8u;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {  // (quad-interleaved G: channel quad urow, 8 frames ucol = four consecutive 16-byte units)
-            const u32x4 v = (u32x4)__builtin_amdgcn_raw_buffer_load_b128(d_g, (int)(vog + 16u * q), 0, 0);
+            const u32x4_t v = (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(d_g, (int)(vog + 16u * q), 0, 0);
             gv[4 * q] = v[0]; gv[4 * q + 1] = v[1]; gv[4 * q + 2] = v[2]; gv[4 * q + 3] = v[3];
         }
 #pragma unroll
         for (int q = 0; q < XQ; ++q) {
             const int cic = min(ci0 + xr[q], a.Cin - 1);
             const unsigned vo = (unsigned)(cic * a.T_in + min(max(t0 - 8 + 4 * xc[q], 0), a.T_in - 4)) * 4u;
-            xv[q] = (u32x4)__builtin_amdgcn_raw_buffer_load_b128(d_x, (int)vo, 0, 0);
+            xv[q] = (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(d_x, (int)vo, 0, 0);
             av[q] = buf_load(d_a, (unsigned)cic * 4u, 0u);
         }
     };
@@ -1139,11 +1068,11 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad3u_bf16_kernel(WgradBf16Ar
         for (int c = 0; c < 4; ++c) {
             const int row = 4 * urow + c;
             const bool ok = t0 + 8 * ucol < a.T && co0 + row < a.Cout;  // T % 8 == 0, Cout % 4 == 0: entirely inside or outside
-            const u32x4 w = q4_channel(gv, c);
-            u32x4 v;
+            const u32x4_t w = q4_channel(gv, c);
+            u32x4_t v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = ok ? w[e] : 0u;
-            *reinterpret_cast<u32x4 *>(Gs + row * WGB_ROWB + ucol * 16) = v;
+            *reinterpret_cast<u32x4_t *>(Gs + row * WGB_ROWB + ucol * 16) = v;
         }
 #pragma unroll
         for (int q = 0; q < XQ; ++q) {
@@ -1154,12 +1083,12 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad3u_bf16_kernel(WgradBf16Ar
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const unsigned bits = xv[q][e];  // (a scalar copy first: __builtin_bit_cast of a vector-element lvalue reads element 0)
-                h[e] = bf16_bits(__builtin_bit_cast(float, bits) + ad);  // the 3-copy kernel's arithmetic
+                h[e] = f2bf(__builtin_bit_cast(float, bits) + ad);  // the 3-copy kernel's arithmetic
             }
-            u32x2 w;
+            u32x2_t w;
             w[0] = ok ? ((unsigned)h[0] | ((unsigned)h[1] << 16)) : 0u;
             w[1] = ok ? ((unsigned)h[2] | ((unsigned)h[3] << 16)) : 0u;
-            *reinterpret_cast<u32x2 *>(Xs + xr[q] * WGT_XROWB + xc[q] * 8) = w;
+            *reinterpret_cast<u32x2_t *>(Xs + xr[q] * WGT_XROWB + xc[q] * 8) = w;
         }
     };
     if (c_begin < c_end) issue(c_begin);
@@ -1174,12 +1103,12 @@ __global__ void __launch_bounds__(256, 2) conv1d_wgrad3u_bf16_kernel(WgradBf16Ar
         const unsigned char *bp = Xs + (wn * 32 + l31) * WGT_XROWB + half * 16;
 #pragma unroll
         for (int ks = 0; ks < WGB_KT / 16; ++ks) {
-            const u32x4 a0 = *reinterpret_cast<const u32x4 *>(ap + ks * 32);
-            const u32x4 a1 = *reinterpret_cast<const u32x4 *>(ap + 32 * WGB_ROWB + ks * 32);
-            u32x4 W[3];
+            const u32x4_t a0 = *reinterpret_cast<const u32x4_t *>(ap + ks * 32);
+            const u32x4_t a1 = *reinterpret_cast<const u32x4_t *>(ap + 32 * WGB_ROWB + ks * 32);
+            u32x4_t W[3];
 #pragma unroll
-            for (int g = 0; g < 3; ++g) W[g] = *reinterpret_cast<const u32x4 *>(bp + ks * 32 + g * 16);
-            const u32x4 b0 = wgt_window<8 - DIL>(W), b1 = W[1], b2 = wgt_window<8 + DIL>(W);
+            for (int g = 0; g < 3; ++g) W[g] = *reinterpret_cast<const u32x4_t *>(bp + ks * 32 + g * 16);
+            const u32x4_t b0 = wgt_window<8 - DIL>(W), b1 = W[1], b2 = wgt_window<8 + DIL>(W);
             acc[0][0] = mfma_bf16(a0, b0, acc[0][0]);
             acc[0][1] = mfma_bf16(a1, b0, acc[0][1]);
             acc[1][0] = mfma_bf16(a0, b1, acc[1][0]);
@@ -1226,29 +1155,6 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float *partial,
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------------
-extern "C" int64_t set_packed_conv_weight_bf16_size(int32_t Cout, int32_t Cin, int32_t K) {
-    return (int64_t)round_up_i(Cout, 128) * K * round_up_i(Cin, 32);  // number of bf16 elements
-}
-
-extern "C" int set_pack_conv_weight_bf16(const float *w, void *wp, int32_t Cout, int32_t Cin, int32_t K, int64_t w_base,
-                                         int64_t w_sco, int64_t w_sci, int64_t w_stap, void *stream) {
-    SET_REQUIRE(w && wp && Cout > 0 && Cin > 0 && K > 0, "set_pack_conv_weight_bf16");
-    const int64_t total = set_packed_conv_weight_bf16_size(Cout, Cin, K);
-    hipLaunchKernelGGL(pack_conv_weight_bf16_kernel, dim3(set_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       reinterpret_cast<unsigned short *>(wp), Cout, Cin, K, round_up_i(Cout, 128), round_up_i(Cin, 32), total,
-                       w_base, w_sco, w_sci, w_stap);
-    return set_check_launch("set_pack_conv_weight_bf16");
-}
-
-extern "C" int64_t set_sizeof_pack_bf16_desc(void) { return (int64_t)sizeof(SetPackBf16Desc); }
-
-extern "C" int set_pack_conv_weights_bf16_batch(const SetPackBf16Desc *descs_dev, int32_t n, int64_t total, void *stream) {
-    SET_REQUIRE(descs_dev && n > 0 && total > 0, "set_pack_conv_weights_bf16_batch");
-    hipLaunchKernelGGL(pack_conv_weights_bf16_batch_kernel, dim3(set_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, descs_dev,
-                       n, total);
-    return set_check_launch("set_pack_conv_weights_bf16_batch");
-}
-
 // called by set_conv1d (conv1d.hip) for impl == SET_IMPL_BF16
 int set_conv1d_bf16_dispatch(const SetConv1dArgs &a, hipStream_t s) {
     if (a.out_stride != 1 || a.out_off != 0)
@@ -1258,7 +1164,7 @@ int set_conv1d_bf16_dispatch(const SetConv1dArgs &a, hipStream_t s) {
     const int halo = (o_first < o_last ? o_last : o_first) - lo;
     if (halo > 128) return set_fail(SET_E_UNSUPPORTED, "set_conv1d(bf16)", "receptive field > 128");
     const int64_t cs = a.res && a.res_cs > a.out_cs ? a.res_cs : a.out_cs;
-    if (((int64_t)round_up_i(a.Cout, 128) * cs + a.T_out) * 4 >= ((int64_t)1 << 31) ||
+    if (((int64_t)set_round_up(a.Cout, BF16_IMG_ROWS) * cs + a.T_out) * 4 >= ((int64_t)1 << 31) ||
         ((int64_t)a.Cin * a.in_cs + a.T_in) * 4 >= ((int64_t)1 << 31))
         return set_fail(SET_E_UNSUPPORTED, "set_conv1d(bf16)", "one batch slice of in / out / res exceeds 2 GiB");
     // 64-row blocks waste less than 128-row ones on 129 .. 192 rows -- but they read the input once more, and the 1x1 convs of
@@ -1266,7 +1172,7 @@ int set_conv1d_bf16_dispatch(const SetConv1dArgs &a, hipStream_t s) {
     // 56 -> 45 us (768 -> 192) with 128-row blocks; the 9-tap convs keep the 64-row ones (146 vs 149 us)
     const bool narrow = a.Cout <= 64 || (a.Cout > 128 && a.Cout <= 192 && a.K > 1);
     if (a.K == 1 && a.Cin > 32 && a.Cout > 64 && halo == 0 && !a.in_chan_add && a.pad == 0) {
-        const int cp = round_up_i(a.Cin, 32);
+        const int cp = set_round_up(a.Cin, BF16_IMG_CH);
         if (cp <= 64) return launch_conv1x1_oneshot<64>(a, s);
         if (cp <= 128) return launch_conv1x1_oneshot<128>(a, s);
         if (cp <= 192) return launch_conv1x1_oneshot<192>(a, s);

@@ -182,7 +182,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_kernel(BoundaryArgs a
 // the operand tiles live in LDS as [piece][frame][channel] fp16 (rows padded by 16 B), the weights come from the images of
 // set_pack_conv_weight_x2 (A-fragment order, straight from global memory), x0 / x' pass through an fp32 tile for the
 // posterior update exactly as above.  Used by the reverse loop whenever the layer stack runs on two-piece fp16 operands.
-// (operand types, bx_split / bx_mma / bx_gemm and the tile constants: csrc/boundary_x2.h)
+// (bx_split / bx_gemm and the tile constants: csrc/boundary_x2.h)
 struct BoundaryX2Args {
     BoundaryArgs g;
     const unsigned short *w_skip_x2, *w_outp_x2, *w_in_x2;
@@ -211,7 +211,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2A
             for (int u = 0; u < 16; ++u) v[u] = buf_load(rs, vo, (unsigned)(64 * cg + c0 + u) * T4);
 #pragma unroll
             for (int q8 = 0; q8 < 2; ++q8) {
-                bx_u32x4 u0, u1;
+                u32x4_t u0, u1;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     unsigned short p0[2], p1[2];
@@ -225,8 +225,8 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2A
                     u0[e] = (unsigned)p0[0] | ((unsigned)p0[1] << 16);
                     u1[e] = (unsigned)p1[0] | ((unsigned)p1[1] << 16);
                 }
-                *reinterpret_cast<bx_u32x4 *>(bl + f * BX_XR + (64 * cg + c0 + 8 * q8) * 2) = u0;
-                *reinterpret_cast<bx_u32x4 *>(bl + BX_PIECE + f * BX_XR + (64 * cg + c0 + 8 * q8) * 2) = u1;
+                *reinterpret_cast<u32x4_t *>(bl + f * BX_XR + (64 * cg + c0 + 8 * q8) * 2) = u0;
+                *reinterpret_cast<u32x4_t *>(bl + BX_PIECE + f * BX_XR + (64 * cg + c0 + 8 * q8) * 2) = u1;
             }
         }
     }
@@ -258,11 +258,11 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2A
                         bx_split(h, p0[e], p1[e]);
                     }
                     const unsigned off = (unsigned)((cb * 32 + l31) * BX_XR + (32 * (2 * w + i) + 8 * g + 4 * half) * 2);
-                    bx_u32x2 u;
+                    u32x2_t u;
                     u[0] = (unsigned)p0[0] | ((unsigned)p0[1] << 16); u[1] = (unsigned)p0[2] | ((unsigned)p0[3] << 16);
-                    *reinterpret_cast<bx_u32x2 *>(bl + off) = u;
+                    *reinterpret_cast<u32x2_t *>(bl + off) = u;
                     u[0] = (unsigned)p1[0] | ((unsigned)p1[1] << 16); u[1] = (unsigned)p1[2] | ((unsigned)p1[3] << 16);
-                    *reinterpret_cast<bx_u32x2 *>(bl + BX_PIECE + off) = u;
+                    *reinterpret_cast<u32x2_t *>(bl + BX_PIECE + off) = u;
                 }
     }
     __syncthreads();
@@ -332,7 +332,7 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2A
         const int f = lane, cg = w;
 #pragma unroll
         for (int q8 = 0; q8 < 3; ++q8) {
-            bx_u32x4 u0, u1;
+            u32x4_t u0, u1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 unsigned short p0[2], p1[2];
@@ -345,8 +345,8 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2A
                 u0[e] = (unsigned)p0[0] | ((unsigned)p0[1] << 16);
                 u1[e] = (unsigned)p1[0] | ((unsigned)p1[1] << 16);
             }
-            *reinterpret_cast<bx_u32x4 *>(xp + f * BX_PR + (24 * cg + 8 * q8) * 2) = u0;
-            *reinterpret_cast<bx_u32x4 *>(xp + XP_PIECE + f * BX_PR + (24 * cg + 8 * q8) * 2) = u1;
+            *reinterpret_cast<u32x4_t *>(xp + f * BX_PR + (24 * cg + 8 * q8) * 2) = u0;
+            *reinterpret_cast<u32x4_t *>(xp + XP_PIECE + f * BX_PR + (24 * cg + 8 * q8) * 2) = u1;
         }
     }
     if (!(amax < 32768.0f) && ax.err_flag) __hip_atomic_store(ax.err_flag, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -7,9 +7,6 @@
 namespace {
 
 constexpr int BX_DC = 256;             // residual channels
-typedef _Float16 bx_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned bx_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned bx_u32x2 __attribute__((ext_vector_type(2)));
 constexpr int BX_XR = BX_DC * 2 + 16;     // bytes per row of the s / h tiles [frame][256]
 constexpr int BX_PR = 96 * 2 + 16;     // ... of the x' tile [frame][96]
 constexpr int BX_PIECE = 64 * BX_XR;   // one piece of a [64][256] tile
@@ -18,9 +15,6 @@ __device__ __forceinline__ void bx_split(float v, unsigned short &p0, unsigned s
     const _Float16 h0 = (_Float16)v;
     p0 = __builtin_bit_cast(unsigned short, h0);
     p1 = __builtin_bit_cast(unsigned short, (_Float16)(v - (float)h0));
-}
-__device__ __forceinline__ f32x16 bx_mma(bx_u32x4 a, bx_u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(bx_f16x8, a), __builtin_bit_cast(bx_f16x8, b), c, 0, 0, 0);
 }
 // acc[NRB][2] += W[32 (rb0 + i) .. ][16 ks ..] * B over nks k-steps; image [rb32][ng16][piece][lane][8] (K = 1 tap);
 // B piece q of (ks, cb) at lds + q * piece_bytes + bfrag(ks, cb)
@@ -33,21 +27,21 @@ __device__ __forceinline__ void bx_gemm(f32x16 (&acc)[NRB][2], rsrc_t img, unsig
     // Same products in the same order per accumulator: bit-identical.
     constexpr int PF = 4;
     auto a_load = [&](int ks, int i, int q) {
-        return (bx_u32x4)__builtin_amdgcn_raw_buffer_load_b128(img, (int)lane16, (int)((((rb0 + i) * ng16 + ks) * 2 + q) * 1024), 0);
+        return (u32x4_t)__builtin_amdgcn_raw_buffer_load_b128(img, (int)lane16, (int)((((rb0 + i) * ng16 + ks) * 2 + q) * 1024), 0);
     };
-    bx_u32x4 A[PF][NRB][2];
+    u32x4_t A[PF][NRB][2];
 #pragma unroll
     for (int p = 0; p < PF; ++p)
 #pragma unroll
         for (int i = 0; i < NRB; ++i)
 #pragma unroll
             for (int q = 0; q < 2; ++q) A[p][i][q] = a_load(min(p, nks - 1), i, q);
-    bx_u32x4 Bv[2][2];
+    u32x4_t Bv[2][2];
 #pragma unroll
     for (int cb = 0; cb < 2; ++cb) {
         const unsigned bo = bfrag(0, cb);
-        Bv[cb][0] = *reinterpret_cast<const bx_u32x4 *>(lds + bo);
-        Bv[cb][1] = *reinterpret_cast<const bx_u32x4 *>(lds + piece_bytes + bo);
+        Bv[cb][0] = *reinterpret_cast<const u32x4_t *>(lds + bo);
+        Bv[cb][1] = *reinterpret_cast<const u32x4_t *>(lds + piece_bytes + bo);
     }
 #pragma unroll 1
     for (int kb = 0; kb < nks; kb += PF) {
@@ -55,20 +49,20 @@ __device__ __forceinline__ void bx_gemm(f32x16 (&acc)[NRB][2], rsrc_t img, unsig
         for (int p = 0; p < PF; ++p) {
             const int ks = kb + p;
             if (ks < nks) {  // (nks need not be a multiple of PF: the in-projection has 5 k-steps)
-                bx_u32x4 Bn[2][2];
+                u32x4_t Bn[2][2];
                 const int kq = min(ks + 1, nks - 1);
 #pragma unroll
                 for (int cb = 0; cb < 2; ++cb) {
                     const unsigned bo = bfrag(kq, cb);
-                    Bn[cb][0] = *reinterpret_cast<const bx_u32x4 *>(lds + bo);
-                    Bn[cb][1] = *reinterpret_cast<const bx_u32x4 *>(lds + piece_bytes + bo);
+                    Bn[cb][0] = *reinterpret_cast<const u32x4_t *>(lds + bo);
+                    Bn[cb][1] = *reinterpret_cast<const u32x4_t *>(lds + piece_bytes + bo);
                 }
 #pragma unroll
                 for (int t = 0; t < 3; ++t)  // a1 b0, a0 b1, a0 b0
 #pragma unroll
                     for (int i = 0; i < NRB; ++i)
 #pragma unroll
-                        for (int cb = 0; cb < 2; ++cb) acc[i][cb] = bx_mma(A[p][i][t == 0 ? 1 : 0], Bv[cb][t == 1 ? 1 : 0], acc[i][cb]);
+                        for (int cb = 0; cb < 2; ++cb) acc[i][cb] = mfma_f16(A[p][i][t == 0 ? 1 : 0], Bv[cb][t == 1 ? 1 : 0], acc[i][cb]);
                 const int kn = min(ks + PF, nks - 1);
 #pragma unroll
                 for (int i = 0; i < NRB; ++i) {

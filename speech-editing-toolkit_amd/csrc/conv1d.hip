@@ -2,11 +2,10 @@
 // (any shape; device-side cross-check) and an implicit-GEMM kernel on v_mfma_f32_32x32x2_f32.
 // Replaces every F.conv1d / nn.Linear / nn.ConvTranspose1d (polyphase) call on the hot path -- see
 // include/set_amd.h for the reference citations.
-#include "common.h"
+#include "weight_image.h"
 #ifndef SET_CONV_V2_STORE_HAZARD
 #define SET_CONV_V2_STORE_HAZARD 0
 #endif
-#include <type_traits>
 
 thread_local char g_set_err[512] = {0};
 
@@ -68,7 +67,6 @@ __global__ void __launch_bounds__(256) conv1d_naive_kernel(SetConv1dArgs a) {
 //   (prologue applied on the way in); A fragments come straight from the packed image in
 //   global memory (256 B coalesced per wave per k-step, L2 resident).
 // ------------------------------------------------------------------------------------------
-constexpr int KC = 16;  // input channels per LDS chunk (packed images pad Cin to a multiple of this)
 
 template <int WM, int WN>
 __global__ void __launch_bounds__(256, 4) conv1d_mfma_kernel(SetConv1dArgs a, int lo, int halo, int CinP, int RBn) {
@@ -250,9 +248,9 @@ __global__ void __launch_bounds__(256, 4) conv1d_mfma_kernel(SetConv1dArgs a, in
         column(ACT, acc1, 1);
     };
     switch (a.act) {
-        case SET_ACT_RELU: finish(std::integral_constant<int, SET_ACT_RELU>{}); break;
-        case SET_ACT_LRELU: finish(std::integral_constant<int, SET_ACT_LRELU>{}); break;
-        default: finish(std::integral_constant<int, SET_ACT_NONE>{}); break;
+        case SET_ACT_RELU: finish(ic<SET_ACT_RELU>{}); break;
+        case SET_ACT_LRELU: finish(ic<SET_ACT_LRELU>{}); break;
+        default: finish(ic<SET_ACT_NONE>{}); break;
     }
 }
 
@@ -265,7 +263,6 @@ __global__ void __launch_bounds__(256, 4) conv1d_mfma_kernel(SetConv1dArgs a, in
 //   k-step order inside a chunk: tap-major, channel pairs minor.
 // ------------------------------------------------------------------------------------------
 constexpr int V2_GS = 4;     // k-steps per operand group
-constexpr int V2_CH = 256;   // max channels per LDS chunk
 
 template <int RB>
 __global__ void __launch_bounds__(256, RB == 1 ? 4 : (RB == 2 ? 3 : 2)) conv1d_mfma_v2_kernel(SetConv1dArgs a, int lo, int halo, int CinP, int ch_max) {
@@ -415,9 +412,9 @@ __global__ void __launch_bounds__(256, RB == 1 ? 4 : (RB == 2 ? 3 : 2)) conv1d_m
                 }
             };
             switch (a.act) {
-                case SET_ACT_RELU: finish(std::integral_constant<int, SET_ACT_RELU>{}); break;
-                case SET_ACT_LRELU: finish(std::integral_constant<int, SET_ACT_LRELU>{}); break;
-                default: finish(std::integral_constant<int, SET_ACT_NONE>{}); break;
+                case SET_ACT_RELU: finish(ic<SET_ACT_RELU>{}); break;
+                case SET_ACT_LRELU: finish(ic<SET_ACT_LRELU>{}); break;
+                default: finish(ic<SET_ACT_NONE>{}); break;
             }
         } else {  // ragged tiles, unaligned shapes, transcendental activations: one frame per thread, the 32 rows of
                   // this wave in batches of 8 (a real loop: the activation switch is expanded 8 times, not 32)
@@ -445,67 +442,12 @@ __global__ void __launch_bounds__(256, RB == 1 ? 4 : (RB == 2 ? 3 : 2)) conv1d_m
             }
         }
     };
-    slice(std::integral_constant<int, 0>{});
-    if constexpr (RB > 1) slice(std::integral_constant<int, 1>{});
+    slice(ic<0>{});
+    if constexpr (RB > 1) slice(ic<1>{});
     if constexpr (RB > 2) {
-        slice(std::integral_constant<int, 2>{});
-        slice(std::integral_constant<int, 3>{});
+        slice(ic<2>{});
+        slice(ic<3>{});
     }
-}
-
-// packed image for v2:  wp[g][w][ks][lane][rb] = W[row][ci][tap],  row = g*128*RB + w*32*RB + rb*32 + (lane&31),
-// ks enumerates (chunk, tap, channel pair) in the kernel's consumption order, ci = chunk0 + 2*cp + (lane>>5)
-__global__ void __launch_bounds__(256) pack_conv_weight_v2_kernel(const float *w, float *wp, int Cout, int Cin, int K,
-                                                                  int CinP, int ch_max, int RB, int64_t total,
-                                                                  int64_t w_base, int64_t w_sco, int64_t w_sci,
-                                                                  int64_t w_stap) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int rb = (int)(idx % RB);
-    const int lane = (int)((idx / RB) & 63);
-    int64_t r = idx / RB / 64;
-    const int64_t ks_total = (int64_t)K * (CinP / 2);
-    int64_t ks = r % ks_total;
-    r /= ks_total;
-    const int wv = (int)(r & 3), g = (int)(r >> 2);
-    // decode ks -> (chunk, tap, cp)
-    int c0 = 0;
-    for (;;) {
-        const int CH = CinP - c0 < ch_max ? CinP - c0 : ch_max;
-        const int64_t per_chunk = (int64_t)K * (CH / 2);
-        if (ks < per_chunk) {
-            const int tap = (int)(ks / (CH / 2)), cp = (int)(ks % (CH / 2));
-            const int co = g * 128 * RB + wv * 32 * RB + rb * 32 + (lane & 31);
-            const int ci = c0 + 2 * cp + (lane >> 5);
-            float v = 0.0f;
-            if (co < Cout && ci < Cin) v = w[w_base + (int64_t)co * w_sco + (int64_t)ci * w_sci + (int64_t)tap * w_stap];
-            wp[idx] = v;
-            return;
-        }
-        ks -= per_chunk;
-        c0 += CH;
-    }
-}
-
-static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
-static inline int v2_rb(int Cout) { return Cout >= 384 ? 4 : (Cout >= 192 ? 2 : 1); }
-static inline int v2_ch_max(int halo) { return (64 + halo) * V2_CH * 4 > 96 * 1024 ? 128 : V2_CH; }
-
-extern "C" int64_t set_packed_conv_weight_v2_size(int32_t Cout, int32_t Cin, int32_t K) {
-    const int RB = v2_rb(Cout);
-    return (int64_t)round_up(Cout, 128 * RB) * K * round_up(Cin, 16);
-}
-
-extern "C" int set_pack_conv_weight_v2(const float *w, float *wp, int32_t Cout, int32_t Cin, int32_t K, int32_t dil,
-                                       int64_t w_base, int64_t w_sco, int64_t w_sci, int64_t w_stap, void *stream) {
-    SET_REQUIRE(w && wp && Cout > 0 && Cin > 0 && K > 0, "set_pack_conv_weight_v2");
-    const int RB = v2_rb(Cout);
-    const int halo = (K - 1) * (dil < 0 ? -dil : dil);
-    const int64_t total = set_packed_conv_weight_v2_size(Cout, Cin, K);
-    hipLaunchKernelGGL(pack_conv_weight_v2_kernel, dim3(set_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, w, wp,
-                       Cout, Cin, K, round_up(Cin, 16), v2_ch_max(halo), RB, total, w_base, w_sco, w_sci, w_stap);
-    return set_check_launch("set_pack_conv_weight_v2");
 }
 
 // the epilogues address out / res with 32-bit byte offsets relative to the batch slice
@@ -520,9 +462,9 @@ static int launch_conv_v2(const SetConv1dArgs &a, hipStream_t s) {
     const int halo = (o_first < o_last ? o_last : o_first) - lo;
     if (halo > 64) return set_fail(SET_E_UNSUPPORTED, "set_conv1d(mfma2)", "receptive field > 64");
     const int RB = v2_rb(a.Cout);
-    if (!epilogue_offsets_fit(a, round_up(a.Cout, 128 * RB)))
+    if (!epilogue_offsets_fit(a, set_round_up(a.Cout, 128 * RB)))
         return set_fail(SET_E_UNSUPPORTED, "set_conv1d(mfma2)", "one batch slice of out / res exceeds 2 GiB");
-    const int CinP = round_up(a.Cin, 16);
+    const int CinP = set_round_up(a.Cin, V2_CIN_PAD);
     const int ch_max = v2_ch_max(halo);
     const int ch = CinP < ch_max ? CinP : ch_max;
     size_t lds = (size_t)ch * (64 + halo) * sizeof(float);
@@ -535,112 +477,6 @@ static int launch_conv_v2(const SetConv1dArgs &a, hipStream_t s) {
     else if (RB == 2) hipLaunchKernelGGL(conv1d_mfma_v2_kernel<2>, grid, block, lds, s, a, lo, halo, CinP, ch_max);
     else hipLaunchKernelGGL(conv1d_mfma_v2_kernel<1>, grid, block, lds, s, a, lo, halo, CinP, ch_max);
     return set_check_launch("set_conv1d(mfma2)");
-}
-
-
-extern "C" int64_t set_packed_conv_weight_size(int32_t Cout, int32_t Cin, int32_t K) {
-    return (int64_t)round_up(Cout, 32) * K * round_up(Cin, KC);
-}
-
-__global__ void __launch_bounds__(256) pack_conv_weight_kernel(const float *w, float *wp, int Cout, int Cin, int K,
-                                                               int CinP, int64_t total, int64_t w_base, int64_t w_sco,
-                                                               int64_t w_sci, int64_t w_stap) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int lane = (int)(idx & 63);
-    int64_t r = idx >> 6;
-    const int cp_total = CinP / 2;
-    const int cp = (int)(r % cp_total);
-    r /= cp_total;
-    const int tap = (int)(r % K);
-    const int rb = (int)(r / K);
-    const int co = rb * 32 + (lane & 31);
-    const int ci = 2 * cp + (lane >> 5);
-    float v = 0.0f;
-    if (co < Cout && ci < Cin) v = w[w_base + (int64_t)co * w_sco + (int64_t)ci * w_sci + (int64_t)tap * w_stap];
-    wp[idx] = v;
-}
-
-extern "C" int set_pack_conv_weight(const float *w, float *wp, int32_t Cout, int32_t Cin, int32_t K, int64_t w_base,
-                                    int64_t w_sco, int64_t w_sci, int64_t w_stap, void *stream) {
-    SET_REQUIRE(w && wp && Cout > 0 && Cin > 0 && K > 0, "set_pack_conv_weight");
-    const int64_t total = set_packed_conv_weight_size(Cout, Cin, K);
-    hipLaunchKernelGGL(pack_conv_weight_kernel, dim3(set_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, w,
-                       wp, Cout, Cin, K, round_up(Cin, KC), total, w_base, w_sco, w_sci, w_stap);
-    return set_check_launch("set_pack_conv_weight");
-}
-
-// every fp32 weight image a training step uses in ONE launch (after the optimizer step: ~150 pack launches of ~5 us per fp32 training
-// step otherwise -- 1.1 ms of a 32 ms step on the compute stream): element gidx of the concatenated image space -> its descriptor by
-// binary search over `start`; kind 0 = the layout of pack_conv_weight_kernel, kind 1 = pack_conv_weight_v2_kernel.  Same values, same places.
-__global__ void __launch_bounds__(256) pack_conv_weights_f32_batch_kernel(const SetPackF32Desc *d, int n, int64_t total) {
-    const int64_t gidx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (gidx >= total) return;
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (d[mid].start <= gidx) lo = mid; else hi = mid - 1;
-    }
-    const SetPackF32Desc e = d[lo];
-    const int64_t idx = gidx - e.start;
-    int co, ci, tap;
-    if (e.kind == 0) {
-        const int lane = (int)(idx & 63);
-        int64_t r = idx >> 6;
-        const int cp_total = e.CinP / 2;
-        const int cp = (int)(r % cp_total);
-        r /= cp_total;
-        tap = (int)(r % e.K);
-        const int rb = (int)(r / e.K);
-        co = rb * 32 + (lane & 31);
-        ci = 2 * cp + (lane >> 5);
-    } else {
-        const int rb = (int)(idx % e.RB);
-        const int lane = (int)((idx / e.RB) & 63);
-        int64_t r = idx / e.RB / 64;
-        const int64_t ks_total = (int64_t)e.K * (e.CinP / 2);
-        int64_t ks = r % ks_total;
-        r /= ks_total;
-        const int wv = (int)(r & 3), g = (int)(r >> 2);
-        int c0 = 0;
-        for (;;) {  // ks -> (chunk, tap, channel pair), the kernel's consumption order
-            const int CH = e.CinP - c0 < e.ch_max ? e.CinP - c0 : e.ch_max;
-            const int64_t per_chunk = (int64_t)e.K * (CH / 2);
-            if (ks < per_chunk) {
-                tap = (int)(ks / (CH / 2));
-                ci = c0 + 2 * (int)(ks % (CH / 2)) + (lane >> 5);
-                break;
-            }
-            ks -= per_chunk;
-            c0 += CH;
-        }
-        co = g * 128 * e.RB + wv * 32 * e.RB + rb * 32 + (lane & 31);
-    }
-    float v = 0.0f;
-    if (co < e.Cout && ci < e.Cin) v = e.w[e.w_base + (int64_t)co * e.w_sco + (int64_t)ci * e.w_sci + (int64_t)tap * e.w_stap];
-    e.wp[idx] = v;
-}
-extern "C" int64_t set_sizeof_pack_f32_desc(void) { return (int64_t)sizeof(SetPackF32Desc); }
-// host side: the layout parameters of an image (CinP, RB, ch_max) and its element count from Cout / Cin / K (and |dil| for kind 1)
-extern "C" int64_t set_fill_pack_f32_desc(SetPackF32Desc *d, int32_t kind, int32_t dil) {
-    if (d == nullptr || (kind != 0 && kind != 1) || d->Cout <= 0 || d->Cin <= 0 || d->K <= 0) return -1;
-    d->kind = kind;
-    if (kind == 0) {
-        d->CinP = round_up(d->Cin, KC);
-        d->RB = 1;
-        d->ch_max = 0;
-        return set_packed_conv_weight_size(d->Cout, d->Cin, d->K);
-    }
-    d->CinP = round_up(d->Cin, 16);
-    d->RB = v2_rb(d->Cout);
-    d->ch_max = v2_ch_max((d->K - 1) * (dil < 0 ? -dil : dil));
-    return set_packed_conv_weight_v2_size(d->Cout, d->Cin, d->K);
-}
-extern "C" int set_pack_conv_weights_f32_batch(const SetPackF32Desc *descs_dev, int32_t n, int64_t total, void *stream) {
-    SET_REQUIRE(descs_dev && n > 0 && total > 0, "set_pack_conv_weights_f32_batch");
-    hipLaunchKernelGGL(pack_conv_weights_f32_batch_kernel, dim3(set_blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, descs_dev, n,
-                       total);
-    return set_check_launch("set_pack_conv_weights_f32_batch");
 }
 
 int set_conv1d_bf16_dispatch(const SetConv1dArgs &a, hipStream_t s);  // bf16.hip
@@ -739,27 +575,19 @@ extern "C" int set_conv1d(const SetConv1dArgs *args, void *stream) {
     const int hi = o_first < o_last ? o_last : o_first;
     const int halo = hi - lo;
     if (halo > 512) return set_fail(SET_E_UNSUPPORTED, "set_conv1d(mfma)", "receptive field > 512");
-    if (!epilogue_offsets_fit(a, round_up(a.Cout, 32)))
+    if (!epilogue_offsets_fit(a, set_round_up(a.Cout, 32)))
         return set_fail(SET_E_UNSUPPORTED, "set_conv1d(mfma)", "one batch slice of out / res exceeds 2 GiB");
-    const int CinP = round_up(a.Cin, KC);
+    const int CinP = set_round_up(a.Cin, KC);
     const int RBn = (a.Cout + 31) / 32;
-    dim3 block(256);
-    if (RBn >= 4) {
-        constexpr int WM = 4, WN = 1;
+    auto launch = [&](auto WM_, auto WN_) {  // block = WM x WN waves: tall layers stack the waves along the rows, flat ones along the frames
+        constexpr int WM = decltype(WM_)::value, WN = decltype(WN_)::value;
         dim3 grid((a.T_iter + 64 * WN - 1) / (64 * WN), (RBn + WM - 1) / WM, a.B);
         const size_t lds = (size_t)KC * (64 * WN + halo) * sizeof(float) * (halo <= 64 ? 2 : 1);  // two buffers when piped
-        hipLaunchKernelGGL((conv1d_mfma_kernel<WM, WN>), grid, block, lds, s, a, lo, halo, CinP, RBn);
-    } else if (RBn >= 2) {
-        constexpr int WM = 2, WN = 2;
-        dim3 grid((a.T_iter + 64 * WN - 1) / (64 * WN), (RBn + WM - 1) / WM, a.B);
-        const size_t lds = (size_t)KC * (64 * WN + halo) * sizeof(float) * (halo <= 64 ? 2 : 1);  // two buffers when piped
-        hipLaunchKernelGGL((conv1d_mfma_kernel<WM, WN>), grid, block, lds, s, a, lo, halo, CinP, RBn);
-    } else {
-        constexpr int WM = 1, WN = 4;
-        dim3 grid((a.T_iter + 64 * WN - 1) / (64 * WN), (RBn + WM - 1) / WM, a.B);
-        const size_t lds = (size_t)KC * (64 * WN + halo) * sizeof(float) * (halo <= 64 ? 2 : 1);  // two buffers when piped
-        hipLaunchKernelGGL((conv1d_mfma_kernel<WM, WN>), grid, block, lds, s, a, lo, halo, CinP, RBn);
-    }
+        hipLaunchKernelGGL((conv1d_mfma_kernel<WM, WN>), grid, dim3(256), lds, s, a, lo, halo, CinP, RBn);
+    };
+    if (RBn >= 4) launch(ic<4>{}, ic<1>{});
+    else if (RBn >= 2) launch(ic<2>{}, ic<2>{});
+    else launch(ic<1>{}, ic<4>{});
     return set_check_launch("set_conv1d(mfma)");
 }
 

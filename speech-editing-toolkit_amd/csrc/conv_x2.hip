@@ -14,12 +14,8 @@
 // polls (set_conv_x2_range_flag): the caller then repeats the forward on the fp32 kernels.
 #include <stdlib.h>
 
-#include <type_traits>
-
 #include "common.h"
 
-typedef _Float16 cx_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned cx_u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ int g_x2_range_flag = 0;
 
@@ -27,24 +23,6 @@ namespace {
 
 constexpr int CX_KCH = 32;               // channels per LDS chunk
 constexpr int CX_ROWB = CX_KCH * 2 + 16;  // bytes per LDS row
-
-template <int N> using cx_ic = std::integral_constant<int, N>;
-
-__device__ __forceinline__ unsigned short cx_f2h(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
-__device__ __forceinline__ float cx_h2f(unsigned short u) { return (float)__builtin_bit_cast(_Float16, u); }
-__device__ __forceinline__ f32x16 cx_mma(cx_u32x4 a, cx_u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(cx_f16x8, a), __builtin_bit_cast(cx_f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ cx_u32x4 cx_load_u4(rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
-}
-template <int PRO>
-__device__ __forceinline__ float cx_pro(float v, float p) {
-    if constexpr (PRO == SET_PRO_LRELU) return v > 0.0f ? v : v * p;
-    else if constexpr (PRO == SET_PRO_DIV) return v / p;
-    else return v;
-}
-static inline int cx_round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // image: [rb32 < CoutP/32][g16 < CinP/16][tap][piece][lane][8]; lane l holds row 32 rb32 + (l & 31), channel 16 g16 + 8 (l >> 5) + e
 // phases = u > 0 (all output phases of a ConvTranspose1d [Cin][Cout_t][kfull] in one image): row R = co * u + p, tap j ->
@@ -74,7 +52,7 @@ __global__ void __launch_bounds__(256) pack_conv_x2_kernel(const float *w, unsig
             v = scale * w[w_base + (int64_t)row * w_sco + (int64_t)ci * w_sci + (int64_t)tap * w_stap];
         }
     }
-    const unsigned short p0 = cx_f2h(v), p1 = cx_f2h(v - cx_h2f(p0));
+    const unsigned short p0 = f2h(v), p1 = f2h(v - h2f(p0));
     unsigned short *base = img + ((((int64_t)rb * ng16 + g16) * K + tap) * 2) * 512 + l * 8 + e;
     base[0] = p0;
     base[512] = p1;
@@ -142,7 +120,7 @@ __global__ void __launch_bounds__(256, 2) conv1d_x2_kernel(SetConv1dArgs a, int 
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int k = 2 * j + h;
-                        v[h] = cx_pro<kPro>(pv[p][k], a.pro_param);                  // unconditional, straight-line
+                        v[h] = pro_c<kPro>(pv[p][k], a.pro_param);                  // unconditional, straight-line
                         v[h] = (tv && c0 + scg * 16 + k < a.Cin) ? v[h] : 0.0f;      // select, no branch
                     }
                     amax = fmaxf(fmaxf(amax, fabsf(v[0])), fabsf(v[1]));
@@ -151,14 +129,14 @@ __global__ void __launch_bounds__(256, 2) conv1d_x2_kernel(SetConv1dArgs a, int 
                 if (row < R) {
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
-                        cx_u32x4 u0, u1;
+                        u32x4_t u0, u1;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             u0[e] = h0[4 * q + e];
                             u1[e] = h1[4 * q + e];
                         }
-                        *reinterpret_cast<cx_u32x4 *>(Bs + row * CX_ROWB + (scg * 16 + 8 * q) * 2) = u0;
-                        *reinterpret_cast<cx_u32x4 *>(Bs + piece_bytes + row * CX_ROWB + (scg * 16 + 8 * q) * 2) = u1;
+                        *reinterpret_cast<u32x4_t *>(Bs + row * CX_ROWB + (scg * 16 + 8 * q) * 2) = u0;
+                        *reinterpret_cast<u32x4_t *>(Bs + piece_bytes + row * CX_ROWB + (scg * 16 + 8 * q) * 2) = u1;
                     }
                 }
             }
@@ -173,12 +151,12 @@ __global__ void __launch_bounds__(256, 2) conv1d_x2_kernel(SetConv1dArgs a, int 
         const int rb = min(rb_first + i, CoutP / 32 - 1);  // (a wave fully outside CoutP re-reads the last block; never stored)
         return (unsigned)((((rb * ng16 + chunk * 2 + h) * K + tap) * 2 + piece) * 1024);
     };
-    cx_u32x4 A[2][RBW][2];
+    u32x4_t A[2][RBW][2];
     auto load_a = [&](int slot_h, int chunk, int tap) {
 #pragma unroll
         for (int i = 0; i < RBW; ++i)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) A[slot_h][i][q] = cx_load_u4(d_w, lane16, a_off(chunk, tap, slot_h, i, q));
+            for (int q = 0; q < 2; ++q) A[slot_h][i][q] = buf_load_u4(d_w, lane16, a_off(chunk, tap, slot_h, i, q));
     };
 
     issue_b(0);
@@ -187,9 +165,9 @@ __global__ void __launch_bounds__(256, 2) conv1d_x2_kernel(SetConv1dArgs a, int 
     for (int c = 0; c < nchunks; ++c) {
         __syncthreads();  // MFMAs of the previous chunk are done with the tile
         switch (a.pro) {
-            case SET_PRO_LRELU: commit_b(cx_ic<SET_PRO_LRELU>{}, c * CX_KCH); break;
-            case SET_PRO_DIV: commit_b(cx_ic<SET_PRO_DIV>{}, c * CX_KCH); break;
-            default: commit_b(cx_ic<SET_PRO_NONE>{}, c * CX_KCH); break;
+            case SET_PRO_LRELU: commit_b(ic<SET_PRO_LRELU>{}, c * CX_KCH); break;
+            case SET_PRO_DIV: commit_b(ic<SET_PRO_DIV>{}, c * CX_KCH); break;
+            default: commit_b(ic<SET_PRO_NONE>{}, c * CX_KCH); break;
         }
         __syncthreads();
         if (c + 1 < nchunks) issue_b((c + 1) * CX_KCH);
@@ -200,14 +178,14 @@ __global__ void __launch_bounds__(256, 2) conv1d_x2_kernel(SetConv1dArgs a, int 
             const int c_n = tap + 1 < K ? c : min(c + 1, nchunks - 1);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                cx_u32x4 Bv[NCB][2];
+                u32x4_t Bv[NCB][2];
 #pragma unroll
                 for (int j = 0; j < NCB; ++j) {
                     const unsigned bo = (unsigned)((wn * 32 * NCB + j * 32 + l31 + off) * CX_ROWB + (h * 16 + half * 8) * 2);
-                    Bv[j][0] = *reinterpret_cast<const cx_u32x4 *>(Bs + bo);
-                    Bv[j][1] = *reinterpret_cast<const cx_u32x4 *>(Bs + piece_bytes + bo);
+                    Bv[j][0] = *reinterpret_cast<const u32x4_t *>(Bs + bo);
+                    Bv[j][1] = *reinterpret_cast<const u32x4_t *>(Bs + piece_bytes + bo);
                 }
-                cx_u32x4 Ac[RBW][2];
+                u32x4_t Ac[RBW][2];
 #pragma unroll
                 for (int i = 0; i < RBW; ++i) {
                     Ac[i][0] = A[h][i][0];
@@ -221,7 +199,7 @@ __global__ void __launch_bounds__(256, 2) conv1d_x2_kernel(SetConv1dArgs a, int 
 #pragma unroll
                     for (int i = 0; i < RBW; ++i)
 #pragma unroll
-                        for (int j = 0; j < NCB; ++j) acc[i][j] = cx_mma(Ac[i][t == 0 ? 1 : 0], Bv[j][t == 1 ? 1 : 0], acc[i][j]);
+                        for (int j = 0; j < NCB; ++j) acc[i][j] = mfma_f16(Ac[i][t == 0 ? 1 : 0], Bv[j][t == 1 ? 1 : 0], acc[i][j]);
                 __builtin_amdgcn_s_setprio(0);
             }
         }
@@ -275,7 +253,6 @@ __global__ void __launch_bounds__(256, 2) conv1d_x2_kernel(SetConv1dArgs a, int 
                     } else if (ph_u == 2) {
                         // stride 2: registers 4 g + {0, 1} are the two phases of channel co at frame t -> one 8-byte store (a wave
                         // then writes 64 consecutive samples of a channel instead of every other one), {2, 3} those of co + 1
-                        typedef unsigned cx_u32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
                         for (int q = 0; q < 2; ++q) {
                             const int c = co + q;
@@ -285,7 +262,7 @@ __global__ void __launch_bounds__(256, 2) conv1d_x2_kernel(SetConv1dArgs a, int 
                             // masked by range, no branches (see conv_bf16_epilogue): the 8-byte store when both samples exist, else
                             // the one that does (only the first / last frame of an utterance takes the 4-byte forms)
                             const bool ok = t < a.T_iter && c < n_ch, both = n0 >= 0 && n0 + 1 < a.T_out;
-                            cx_u32x2 o;
+                            u32x2_t o;
                             o[0] = __builtin_bit_cast(unsigned, v0); o[1] = __builtin_bit_cast(unsigned, v1);
                             __builtin_amdgcn_raw_buffer_store_b64(o, d_o, (int)((ok && both) ? off : BUF_OOB), 0, 0);
                             if (__builtin_amdgcn_ballot_w64(ok && !both) != 0) {  // wave-uniform: some lane sits on an utterance edge
@@ -362,17 +339,17 @@ __global__ void __launch_bounds__(256, 2) conv1d_x2_kernel(SetConv1dArgs a, int 
         }
     };
     switch (a.act) {
-        case SET_ACT_NONE: finish(cx_ic<SET_ACT_NONE>{}); break;
-        case SET_ACT_RELU: finish(cx_ic<SET_ACT_RELU>{}); break;
-        case SET_ACT_LRELU: finish(cx_ic<SET_ACT_LRELU>{}); break;
-        default: finish(cx_ic<-1>{}); break;  // gelu / tanh / softplus / mish: run-time dev_act
+        case SET_ACT_NONE: finish(ic<SET_ACT_NONE>{}); break;
+        case SET_ACT_RELU: finish(ic<SET_ACT_RELU>{}); break;
+        case SET_ACT_LRELU: finish(ic<SET_ACT_LRELU>{}); break;
+        default: finish(ic<-1>{}); break;  // gelu / tanh / softplus / mish: run-time dev_act
     }
 }
 
 template <int WM, int WN, int RBW, int NCB, bool PHASES = false>
 int launch_conv_x2(const SetConv1dArgs &a, int lo, int halo, hipStream_t s, int ph_u = 0, int ph_pad = 0) {
     constexpr int MB = 32 * RBW * WM, NB = 32 * NCB * WN;
-    const int CinP = cx_round_up(a.Cin, CX_KCH), CoutP = cx_round_up(a.Cout, 32);
+    const int CinP = set_round_up(a.Cin, CX_KCH), CoutP = set_round_up(a.Cout, 32);
     const size_t lds = (size_t)2 * (NB + halo) * CX_ROWB;
     static SetDeviceOnce lds_once;
     if (int rc = set_lds_optin(lds_once, 96 * 1024, "conv x2 attr", conv1d_x2_kernel<WM, WN, RBW, NCB, PHASES>)) return rc;
@@ -385,13 +362,13 @@ int launch_conv_x2(const SetConv1dArgs &a, int lo, int halo, hipStream_t s, int 
 }  // namespace
 
 extern "C" int64_t set_packed_conv_weight_x2_size(int32_t Cout, int32_t Cin, int32_t K) {
-    return (int64_t)2 * (cx_round_up(Cout, 32) / 32) * (cx_round_up(Cin, CX_KCH) / 16) * K * 512 + 8;  // fp16 elements (+ 4 floats)
+    return (int64_t)2 * (set_round_up(Cout, 32) / 32) * (set_round_up(Cin, CX_KCH) / 16) * K * 512 + 8;  // fp16 elements (+ 4 floats)
 }
 
 static int pack_x2(const float *w, void *wp, int Cout, int Cin, int K, int64_t w_base, int64_t w_sco, int64_t w_sci, int64_t w_stap,
                    int scale_exp, int phases, int kfull, void *stream, const char *what) {
     SET_REQUIRE(w && wp && Cout > 0 && Cin > 0 && K > 0 && scale_exp >= -60 && scale_exp <= 60, what);
-    const int CoutP = cx_round_up(Cout, 32), CinP = cx_round_up(Cin, CX_KCH);
+    const int CoutP = set_round_up(Cout, 32), CinP = set_round_up(Cin, CX_KCH);
     const int64_t n = (int64_t)(CoutP / 32) * (CinP / 16) * K * 512;
     hipLaunchKernelGGL(pack_conv_x2_kernel, dim3(set_blocks(n, 256)), dim3(256), 0, (hipStream_t)stream, w,
                        reinterpret_cast<unsigned short *>(wp), Cout, Cin, K, CoutP, CinP, n, w_base, w_sco, w_sci, w_stap,
@@ -461,7 +438,7 @@ int set_conv1d_x2_dispatch(const SetConv1dArgs &a, hipStream_t s) {
     const int halo = (o_first < o_last ? o_last : o_first) - lo;
     if (halo > 128) return set_fail(SET_E_UNSUPPORTED, "set_conv1d(f16x2)", "receptive field > 128");
     const int64_t cs = a.res && a.res_cs > a.out_cs ? a.res_cs : a.out_cs;
-    if (((int64_t)cx_round_up(a.Cout, 32) * cs + a.T_out) * 4 >= ((int64_t)1 << 31) ||
+    if (((int64_t)set_round_up(a.Cout, 32) * cs + a.T_out) * 4 >= ((int64_t)1 << 31) ||
         ((int64_t)a.Cin * a.in_cs + a.T_in) * 4 >= ((int64_t)1 << 31))
         return set_fail(SET_E_UNSUPPORTED, "set_conv1d(f16x2)", "one batch slice of in / out / res exceeds 2 GiB");
     // wave tile 64 rows x 64 frames (4 accumulators): with 8 (2 x 4 blocks) the staging registers of the next chunk no

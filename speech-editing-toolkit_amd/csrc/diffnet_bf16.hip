@@ -65,7 +65,6 @@ __device__ __forceinline__ void buf_store_u16(unsigned short v, rsrc_t r, unsign
 // frames: 512 contiguous bytes per wave) instead of four 2-byte ones -- these kernels issued 192 (forward) / 384 (backward) 2-byte memory
 // instructions per lane, and the backward ran 65 instead of 85 us without them.  The weight-gradient loaders (bf16.hip) read the same layout
 // in 16-byte units (2 frames x 4 channels) and transpose 8 frames x 4 channels in registers (v_perm_b32).  Same values as before, another place.
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void buf_store_q4(u32x2_t v, rsrc_t r, unsigned voff, unsigned soff) {
     __builtin_amdgcn_raw_buffer_store_b64(v, r, (int)voff, (int)soff, 0);
 }
@@ -667,7 +666,6 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
     // probe builds: the phases of the layers m >= 1, waves 0 and 4 of block (1, 1) (layout: at SET_PHASE_PROBE_BUFFER above)
     const bool probe = g_bf16_phase_buf && blockIdx.x == 1 && blockIdx.y == 1;
     PhaseProbe<8> pp;
-    typedef unsigned lr_u32x2 __attribute__((ext_vector_type(2)));
     // SKEW: a static priority instead of the per-k-step toggles -- waves 0-3 win every arbitration against their SIMD partners 4-7
     if (SKEW && w < 4) __builtin_amdgcn_s_setprio(1);
     u32x4_t A1[PF1][2], A2[PF2][2];
@@ -721,9 +719,9 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
                 float z[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) z[e] = fsig(acc[0][cb][4 * g4 + e]) * ftanh(acc[1][cb][4 * g4 + e]);
-                lr_u32x2 u;
+                u32x2_t u;
                 u[0] = pack2(z[0], z[1]) & mT[cb]; u[1] = pack2(z[2], z[3]) & mT[cb];
-                *reinterpret_cast<lr_u32x2 *>(zs + (cb * 32 + l31) * XR + (row_g + 8 * g4 + 4 * half) * 2) = u;
+                *reinterpret_cast<u32x2_t *>(zs + (cb * 32 + l31) * XR + (row_g + 8 * g4 + 4 * half) * 2) = u;
             }
         // accumulators of GEMM 2: residual rows start at b_out + x, skip rows at b_out
 #pragma unroll
@@ -764,10 +762,10 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const int ch = row_g + 8 * g4 + 4 * half;
                     const f32x4 dv = *reinterpret_cast<const f32x4 *>(dnx + ch);
-                    lr_u32x2 u;
+                    u32x2_t u;
                     u[0] = pack2(xkeep[cb][4 * g4] + dv[0], xkeep[cb][4 * g4 + 1] + dv[1]) & mT[cb];
                     u[1] = pack2(xkeep[cb][4 * g4 + 2] + dv[2], xkeep[cb][4 * g4 + 3] + dv[3]) & mT[cb];
-                    *reinterpret_cast<lr_u32x2 *>(xs + (dn + cb * 32 + l31) * XR + ch * 2) = u;
+                    *reinterpret_cast<u32x2_t *>(xs + (dn + cb * 32 + l31) * XR + ch * 2) = u;
                 }
         } else {
 #pragma unroll
@@ -998,7 +996,6 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
 
     const bool probe = g_bf16_phase_buf && blockIdx.x == 1 && blockIdx.y == 1;
     PhaseProbe<8> pp;
-    typedef unsigned lt_u32x2 __attribute__((ext_vector_type(2)));
     if (SKEW && w < 4) __builtin_amdgcn_s_setprio(1);
     // old skip rows per column block: blocks < NSKR live in registers for the whole group, the others travel through the private copy per layer
     f32x16 sko[NCB];
@@ -1085,9 +1082,9 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
             for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
                 for (int g2 = 0; g2 < 2; ++g2) {
-                    lt_u32x2 u;
+                    u32x2_t u;
                     u[0] = zp[h][cb][g2][0]; u[1] = zp[h][cb][g2][1];
-                    *reinterpret_cast<lt_u32x2 *>(xs + (cb * 32 + l31) * XR + (row_g + 16 * h + 8 * g2 + 4 * half) * 2) = u;
+                    *reinterpret_cast<u32x2_t *>(xs + (cb * 32 + l31) * XR + (row_g + 16 * h + 8 * g2 + 4 * half) * 2) = u;
                 }
         if (!last) { bsh[((m + 1) & 1) * 1024 + tid] = nb1; bsh[((m + 1) & 1) * 1024 + 512 + tid] = nb2; }
         __builtin_amdgcn_sched_barrier(0);
@@ -1173,9 +1170,9 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
             for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
-                    lt_u32x2 u;
+                    u32x2_t u;
                     u[0] = xp[cb][g4][0]; u[1] = xp[cb][g4][1];
-                    *reinterpret_cast<lt_u32x2 *>(xs + (dn + cb * 32 + l31) * XR + (row_g + 8 * g4 + 4 * half) * 2) = u;
+                    *reinterpret_cast<u32x2_t *>(xs + (dn + cb * 32 + l31) * XR + (row_g + 8 * g4 + 4 * half) * 2) = u;
                 }
         } else {
 #pragma unroll

@@ -40,7 +40,6 @@
 #include "stack_queue.h"
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 
 // probe builds (-DSET_PHASE_PROBE=1): wave 0 of ONE block sums the s_memtime ticks of its phases and adds them to buf (the kernels ran
 // 1.788 -> 1.763 ms per 20-layer launch at B = 32, T = 800 once the shipped build lost its stamps, see phase_probe.h).
@@ -71,8 +70,6 @@ __device__ __forceinline__ void split3(float a, unsigned short &p0, unsigned sho
     p2 = f2bf(r1 - bf2f(p1));
 }
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned short f2h(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
-__device__ __forceinline__ float h2f(unsigned short u) { return (float)__builtin_bit_cast(_Float16, u); }
 
 struct SplitBf16x3 {
     static constexpr int NP = 3, NPROD = 6, MODE = 3, PF = 2, PF2 = 1;  // PF / PF2: A prefetch distance in k-steps (8- / 4-wave blocks)
@@ -649,7 +646,6 @@ int launch_x3(const SetDiffnetStackArgs &a, int n_cu, hipStream_t s) {
 // profiles/r06_x3w_no_a_stream_bound.log).  The kernel below replaced it on every shape (same box: B = 32 1.43 against 1.61 ms on 96-frame
 // tiles; 64-frame tiles B = 24 / 16 / 12: +5.3 / +3.7 / +3.1 % frames/s, profiles/r06_x3v_ab.log, r06_x3v_nb2_ab.log).
 // =====================================================================================================================
-typedef unsigned u32x2w_t __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 buf_load2(rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0));
@@ -992,10 +988,10 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
                 const unsigned off = (unsigned)((32 * nb + 2 * l15 + eo) * XR + (32 * w + 16 * m + 4 * kg) * 2);
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    u32x2w_t uu;
+                    u32x2_t uu;
                     uu[0] = plo[q];
                     uu[1] = phi[q];
-                    *reinterpret_cast<u32x2w_t *>(lds + q * xv_zpiece<NB>() + off) = uu;
+                    *reinterpret_cast<u32x2_t *>(lds + q * xv_zpiece<NB>() + off) = uu;
                 }
             }
     }

@@ -35,9 +35,6 @@
 #include "common.h"
 #include "phase_probe.h"
 
-typedef _Float16 rp_f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned rp_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned rp_u32x2 __attribute__((ext_vector_type(2)));
 
 // (device symbols do not link across translation units without -fgpu-rdc: this file keeps its own sticky range word, and
 // set_conv_x2_range_flag (csrc/conv_x2.hip) reads both through set_resblock_pair_range_flag_)
@@ -50,16 +47,6 @@ namespace {
 
 constexpr int RP_KCH = 32;                // channels per staged chunk of x
 constexpr int RP_ROWB = RP_KCH * 2 + 16;  // bytes per LDS row of a chunk
-
-__device__ __forceinline__ unsigned short rp_f2h(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
-__device__ __forceinline__ float rp_h2f(unsigned short u) { return (float)__builtin_bit_cast(_Float16, u); }
-__device__ __forceinline__ f32x16 rp_mma(rp_u32x4 a, rp_u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(rp_f16x8, a), __builtin_bit_cast(rp_f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ rp_u32x4 rp_load_u4(rsrc_t r, unsigned voff, unsigned soff) {
-    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
-}
-static inline int rp_round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 template <int WM, int WN, int RBW, int NCB>
 __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPairArgs a, int CP, int NV) {
@@ -141,14 +128,14 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
                 if (row < R1) {
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
-                        rp_u32x4 u0, u1;
+                        u32x4_t u0, u1;
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             u0[e] = q0[4 * q + e];
                             u1[e] = q1[4 * q + e];
                         }
-                        *reinterpret_cast<rp_u32x4 *>(Bs + row * RP_ROWB + (scg * 16 + 8 * q) * 2) = u0;
-                        *reinterpret_cast<rp_u32x4 *>(Bs + piece1 + row * RP_ROWB + (scg * 16 + 8 * q) * 2) = u1;
+                        *reinterpret_cast<u32x4_t *>(Bs + row * RP_ROWB + (scg * 16 + 8 * q) * 2) = u0;
+                        *reinterpret_cast<u32x4_t *>(Bs + piece1 + row * RP_ROWB + (scg * 16 + 8 * q) * 2) = u1;
                     }
                 }
             }
@@ -160,12 +147,12 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
         const int rb = min(rb_first + i, CP / 32 - 1);  // (a wave fully outside CP re-reads the last block; never stored)
         return (unsigned)((((rb * ng16 + chunk * 2 + h) * K + tap) * 2 + piece) * 1024);
     };
-    rp_u32x4 A[2][RBW][2];
+    u32x4_t A[2][RBW][2];
     auto load_a = [&](rsrc_t d_w, int slot_h, int chunk, int tap) {
 #pragma unroll
         for (int i = 0; i < RBW; ++i)
 #pragma unroll
-            for (int q = 0; q < 2; ++q) A[slot_h][i][q] = rp_load_u4(d_w, lane16, a_off(chunk, tap, slot_h, i, q));
+            for (int q = 0; q < 2; ++q) A[slot_h][i][q] = buf_load_u4(d_w, lane16, a_off(chunk, tap, slot_h, i, q));
     };
 
     // =========================== phase 1: t = W1 (*) lrelu(x) =====================================================
@@ -186,14 +173,14 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
                 const int c_n = tap + 1 < K ? c : min(c + 1, nchunks - 1);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    rp_u32x4 Bv[NCB][2];
+                    u32x4_t Bv[NCB][2];
 #pragma unroll
                     for (int j = 0; j < NCB; ++j) {
                         const unsigned bo = (unsigned)((wn * 32 * NCB + j * 32 + l31 + off) * RP_ROWB + (h * 16 + half * 8) * 2);
-                        Bv[j][0] = *reinterpret_cast<const rp_u32x4 *>(Bs + bo);
-                        Bv[j][1] = *reinterpret_cast<const rp_u32x4 *>(Bs + piece1 + bo);
+                        Bv[j][0] = *reinterpret_cast<const u32x4_t *>(Bs + bo);
+                        Bv[j][1] = *reinterpret_cast<const u32x4_t *>(Bs + piece1 + bo);
                     }
-                    rp_u32x4 Ac[RBW][2];
+                    u32x4_t Ac[RBW][2];
 #pragma unroll
                     for (int i = 0; i < RBW; ++i) {
                         Ac[i][0] = A[h][i][0];
@@ -206,7 +193,7 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
 #pragma unroll
                         for (int i = 0; i < RBW; ++i)
 #pragma unroll
-                            for (int j = 0; j < NCB; ++j) acc[i][j] = rp_mma(Ac[i][t == 0 ? 1 : 0], Bv[j][t == 1 ? 1 : 0], acc[i][j]);
+                            for (int j = 0; j < NCB; ++j) acc[i][j] = mfma_f16(Ac[i][t == 0 ? 1 : 0], Bv[j][t == 1 ? 1 : 0], acc[i][j]);
                     __builtin_amdgcn_s_setprio(0);
                 }
             }
@@ -250,9 +237,9 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
                 unsigned lo0, lo1, hi0, hi1;
                 split2_f16(v[0], v[1], lo0, lo1);
                 split2_f16(v[2], v[3], hi0, hi1);
-                const rp_u32x2 u0 = {lo0, hi0}, u1 = {lo1, hi1};
-                *reinterpret_cast<rp_u32x2 *>(Bs + off) = u0;
-                *reinterpret_cast<rp_u32x2 *>(Bs + piece2 + off) = u1;
+                const u32x2_t u0 = {lo0, hi0}, u1 = {lo1, hi1};
+                *reinterpret_cast<u32x2_t *>(Bs + off) = u0;
+                *reinterpret_cast<u32x2_t *>(Bs + piece2 + off) = u1;
             }
             acc[i][j] = (f32x16){0};
         }
@@ -268,14 +255,14 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
             const int c_n = tap + 1 < K ? c : min(c + 1, nchunks - 1);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
-                rp_u32x4 Bv[NCB][2];
+                u32x4_t Bv[NCB][2];
 #pragma unroll
                 for (int j = 0; j < NCB; ++j) {  // output column c needs t at columns c + tap - h2, i.e. rows c + tap
                     const unsigned bo = (unsigned)((wn * 32 * NCB + j * 32 + l31 + tap) * TROW + (c * RP_KCH + h * 16 + half * 8) * 2);
-                    Bv[j][0] = *reinterpret_cast<const rp_u32x4 *>(Bs + bo);
-                    Bv[j][1] = *reinterpret_cast<const rp_u32x4 *>(Bs + piece2 + bo);
+                    Bv[j][0] = *reinterpret_cast<const u32x4_t *>(Bs + bo);
+                    Bv[j][1] = *reinterpret_cast<const u32x4_t *>(Bs + piece2 + bo);
                 }
-                rp_u32x4 Ac[RBW][2];
+                u32x4_t Ac[RBW][2];
 #pragma unroll
                 for (int i = 0; i < RBW; ++i) {
                     Ac[i][0] = A[h][i][0];
@@ -288,7 +275,7 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
 #pragma unroll
                     for (int i = 0; i < RBW; ++i)
 #pragma unroll
-                        for (int j = 0; j < NCB; ++j) acc[i][j] = rp_mma(Ac[i][t == 0 ? 1 : 0], Bv[j][t == 1 ? 1 : 0], acc[i][j]);
+                        for (int j = 0; j < NCB; ++j) acc[i][j] = mfma_f16(Ac[i][t == 0 ? 1 : 0], Bv[j][t == 1 ? 1 : 0], acc[i][j]);
                 __builtin_amdgcn_s_setprio(0);
             }
         }
@@ -342,7 +329,7 @@ __global__ void __launch_bounds__(256, 2) resblock_pair_x2_kernel(SetResblockPai
 template <int WM, int WN, int RBW, int NCB>
 int launch_pair(const SetResblockPairArgs &a, hipStream_t s) {
     constexpr int NB = 32 * NCB * WN;
-    const int CP = rp_round_up(a.C, RP_KCH);
+    const int CP = set_round_up(a.C, RP_KCH);
     const int h2 = (a.K - 1) / 2, h1 = a.dil * h2;
     const int NV = NB - 2 * h2;
     const size_t lds1 = (size_t)2 * (NB + 2 * h1) * RP_ROWB, lds2 = (size_t)2 * (NB + 2 * h2) * (CP * 2 + 16);
@@ -389,8 +376,8 @@ extern "C" int set_resblock_pair_x2(const SetResblockPairArgs *args, void *strea
     if (set_resblock_pair_x2_supported(a.C, a.K, a.dil, a.T) != SET_OK)
         return set_fail(SET_E_UNSUPPORTED, "set_resblock_pair_x2", "shape outside the fused kernel (C in 16..256, odd K <= 15 (<= 5 above 128 channels), receptive field <= 128)");
     SET_REQUIRE(!(a.out_div != 0.0f && !a.accumulate), "set_resblock_pair_x2(out_div needs accumulate)");
-    if (((int64_t)rp_round_up(a.C, 32) * a.x_cs + a.T) * 4 >= ((int64_t)1 << 31) ||
-        ((int64_t)rp_round_up(a.C, 32) * a.out_cs + a.T) * 4 >= ((int64_t)1 << 31))
+    if (((int64_t)set_round_up(a.C, 32) * a.x_cs + a.T) * 4 >= ((int64_t)1 << 31) ||
+        ((int64_t)set_round_up(a.C, 32) * a.out_cs + a.T) * 4 >= ((int64_t)1 << 31))
         return set_fail(SET_E_UNSUPPORTED, "set_resblock_pair_x2", "one batch slice of x / out exceeds 2 GiB");
     hipStream_t s = (hipStream_t)stream;
     if (a.C > 128) return launch_pair<4, 1, 2, 2>(a, s);  // 256 rows x  64 frames

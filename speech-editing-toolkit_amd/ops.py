@@ -73,97 +73,73 @@ class CacheSlot:
 import weakref  # noqa: E402
 
 _BF16_IMAGES = weakref.WeakSet()   # ConvWeights that hold a bf16 image (training rows, compute dtype bf16)
-_BF16_BATCH = [None, None, 0]      # (signature, device descriptor table, total elements) of the last batch re-pack
-
-
-def repack_bf16_images():
-    """Re-round EVERY live bf16 weight image from its fp32 master weight in ONE launch and mark the images current for the
-    present weights epoch.  Called by the optimizer right after its step: the lazy per-weight check in `packed_bf16()` then
-    finds nothing to do, instead of launching 100 - 170 tiny pack kernels (and allocating as many tensors) per training step.
-    The descriptor table lives on the device and is rebuilt only when the set of images or their storage changes."""
-    cws = [cw for cw in _BF16_IMAGES if cw._img16.value is not None]
-    if not cws:
-        return 0
-    ws = [cw.raw() for cw in cws]
-    dev = ws[0].device
-    keep = [i for i, w in enumerate(ws) if w.device == dev and cws[i]._img16.value.device == dev]
-    cws, ws = [cws[i] for i in keep], [ws[i] for i in keep]
-    sig = tuple((id(cw), w.data_ptr(), cw._img16.value.data_ptr()) for cw, w in zip(cws, ws))
-    if _BF16_BATCH[0] != sig:
-        arr = (_lib.SetPackBf16Desc * len(cws))()
-        start = 0
-        for d, cw, w in zip(arr, cws, ws):
-            wp = cw._img16.value
-            d.w, d.wp = w.data_ptr(), wp.data_ptr()
-            d.w_base, d.w_sco, d.w_sci, d.w_stap, d.start = cw.base, cw.sco, cw.sci, cw.stap, start
-            d.Cout, d.Cin, d.K = cw.Cout, cw.Cin, cw.K
-            d.CoutP, d.CinP = (cw.Cout + 127) // 128 * 128, (cw.Cin + 31) // 32 * 32
-            assert wp.numel() == d.CoutP * d.K * d.CinP
-            start += wp.numel()
-        raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-        _BF16_BATCH[0], _BF16_BATCH[1], _BF16_BATCH[2] = sig, raw, start
-    check(_lib.lib().set_pack_conv_weights_bf16_batch(C.c_void_p(_BF16_BATCH[1].data_ptr()), len(cws), _BF16_BATCH[2], _stream()),
-          "set_pack_conv_weights_bf16_batch")
-    for cw, w in zip(cws, ws):
-        cw._img16.mark(weights_key((w,)))
-    return len(cws)
-
-
 _F32_IMAGES = weakref.WeakSet()    # ConvWeights that hold an fp32 image (set_pack_conv_weight / _v2)
-_F32_TABLES = collections.OrderedDict()  # signature -> (device descriptor table, total elements, pinned host copy): the last few batch re-packs
+_PACK_TABLES = collections.OrderedDict()  # signature -> (device descriptor table, total elements, pinned host copy): the last few re-packs
 
 
-def repack_f32_images():
-    """Re-pack every fp32 weight image USED since the last call from its master weight in ONE launch and mark it current for the
-    present weights epoch (called by the optimizer right after its step, like repack_bf16_images): the lazy check in `packed()` /
-    `packed_v2()` then finds nothing to do instead of launching ~150 pack kernels of ~5 us per fp32 training step (1.1 ms of the
-    compute stream's 32 ms at B = 32, T = 800).  An image that was not used stays stale and is re-packed when it is next asked for.
-    Same kernel arithmetic (a copy into the image layout): same bits."""
-    items = []  # (ConvWeight, kind: 0 = plain / 1 = big-tile, slot, image, dil, CacheSlot)
-    for cw in _F32_IMAGES:
-        if cw._used32 and cw._img32.value is not None:
-            items.append((cw, 0, None, cw._img32.value, 0, cw._img32))
-        for slot in cw._used2:
-            ent = cw._img2.get(slot)
-            if ent is not None:
-                items.append((cw, 1, slot, *ent.value, ent))
-        cw._used32 = False
-        cw._used2 = set()
+def _repack_images(items):
+    """Re-pack the images `items` -- (ConvWeight, _lib.IMG_* kind, slot, image, dil, CacheSlot) each -- from their master weights in ONE
+    launch and mark them current for the present weights epoch; returns how many.  Images on another device than the first are left to
+    the lazy path.  The descriptor table lives on the device and is built only when the set of images or their storage changes."""
     if not items:
         return 0
     ws = [it[0].raw() for it in items]
     dev = ws[0].device
     keep = [i for i, w in enumerate(ws) if w.device == dev and items[i][3].device == dev]
-    # a deterministic order (the WeakSet's iteration order changes with the set of live images) and a small cache of tables: bucketed
+    # a deterministic order (the WeakSets' iteration order changes with the set of live images) and a small cache of tables: bucketed
     # ragged batches alternate between a few sets of used images (packed() vs packed_v2() by T) -- each set's table is built and uploaded
-    # once, from pinned memory without a host sync (round-5 advisor item)
+    # once, from pinned memory without a host sync
     order = sorted(range(len(keep)), key=lambda j: (items[keep[j]][3].data_ptr(), items[keep[j]][1], str(items[keep[j]][2])))
     items, ws = [items[keep[j]] for j in order], [ws[keep[j]] for j in order]
     sig = tuple((id(it[0]), it[1], it[2], w.data_ptr(), it[3].data_ptr()) for it, w in zip(items, ws))
-    ent = _F32_TABLES.get(sig)
+    ent = _PACK_TABLES.get(sig)
     if ent is not None:
-        _F32_TABLES.move_to_end(sig)
+        _PACK_TABLES.move_to_end(sig)
     else:
-        arr = (_lib.SetPackF32Desc * len(items))()
+        arr = (_lib.SetPackDesc * len(items))()
         start = 0
         for d, (cw, kind, slot, wp, dil, _), w in zip(arr, items, ws):
             d.w, d.wp = w.data_ptr(), wp.data_ptr()
             d.w_base, d.w_sco, d.w_sci, d.w_stap, d.start = cw.base, cw.sco, cw.sci, cw.stap, start
             d.Cout, d.Cin, d.K = cw.Cout, cw.Cin, cw.K
-            n = _lib.lib().set_fill_pack_f32_desc(C.byref(d), kind, int(dil))
+            n = _lib.lib().set_fill_pack_desc(C.byref(d), kind, int(dil))
             assert n == wp.numel(), (n, wp.numel(), kind)
             start += n
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         if dev.type == "cuda":
             host = host.pin_memory()
-        ent = _F32_TABLES[sig] = (host.to(dev, non_blocking=True), start, host)
-        while len(_F32_TABLES) > 8:
-            _F32_TABLES.popitem(last=False)
-    check(_lib.lib().set_pack_conv_weights_f32_batch(C.c_void_p(ent[0].data_ptr()), len(items), ent[1], _stream()),
-          "set_pack_conv_weights_f32_batch")
+        ent = _PACK_TABLES[sig] = (host.to(dev, non_blocking=True), start, host)
+        while len(_PACK_TABLES) > 8:
+            _PACK_TABLES.popitem(last=False)
+    check(_lib.lib().set_pack_conv_weights_batch(C.c_void_p(ent[0].data_ptr()), len(items), ent[1], _stream()), "set_pack_conv_weights_batch")
     for it, w in zip(items, ws):
         it[5].mark(weights_key((w,)))
     return len(items)
+
+
+def repack_bf16_images():
+    """Re-round EVERY live bf16 weight image from its fp32 master weight in ONE launch.  Called by the optimizer right after its step:
+    the lazy per-weight check in `packed_bf16()` then finds nothing to do, instead of launching 100 - 170 tiny pack kernels (and
+    allocating as many tensors) per training step."""
+    return _repack_images([(cw, _lib.IMG_BF16, None, cw._img16.value, 0, cw._img16) for cw in _BF16_IMAGES if cw._img16.value is not None])
+
+
+def repack_f32_images():
+    """Re-pack every fp32 weight image USED since the last call in ONE launch (called by the optimizer right after its step, like
+    repack_bf16_images): the lazy check in `packed()` / `packed_v2()` then finds nothing to do instead of launching ~150 pack kernels of
+    ~5 us per fp32 training step (1.1 ms of the compute stream's 32 ms at B = 32, T = 800).  An image that was not used stays stale and
+    is re-packed when it is next asked for.  Same kernel arithmetic (a copy into the image layout): same bits."""
+    items = []
+    for cw in _F32_IMAGES:
+        if cw._used32 and cw._img32.value is not None:
+            items.append((cw, _lib.IMG_F32, None, cw._img32.value, 0, cw._img32))
+        for slot in cw._used2:
+            ent = cw._img2.get(slot)
+            if ent is not None:
+                items.append((cw, _lib.IMG_F32_BIG, slot, *ent.value, ent))
+        cw._used32 = False
+        cw._used2 = set()
+    return _repack_images(items)
 
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)

@@ -24,7 +24,7 @@ def test_header_symbols_exported(built_lib):
     assert names == set(_lib.SIGNATURES), names ^ set(_lib.SIGNATURES)
     for n in names:
         assert hasattr(built_lib, n), n
-    assert built_lib.set_abi_version() == 4
+    assert built_lib.set_abi_version() == 5
 
 
 def test_struct_mirror_sizes(built_lib):
@@ -32,6 +32,7 @@ def test_struct_mirror_sizes(built_lib):
     assert built_lib.set_sizeof_conv1d_args() == C.sizeof(_lib.SetConv1dArgs)
     assert built_lib.set_sizeof_diffnet_layer_args() == C.sizeof(_lib.SetDiffnetLayerArgs)
     assert built_lib.set_sizeof_diff_loop_args() == C.sizeof(_lib.SetDiffLoopArgs)
+    assert built_lib.set_sizeof_pack_desc() == C.sizeof(_lib.SetPackDesc) == 88
     assert built_lib.set_diffnet_w1p_size() == 512 * 768 and built_lib.set_diffnet_w2p_size() == 512 * 256
     assert built_lib.set_packed_conv_weight_size(80, 256, 1) == 96 * 256
     assert built_lib.set_packed_conv_weight_size(256, 80, 1) == 256 * 80
@@ -159,6 +160,30 @@ def test_training_reductions_have_no_atomic_twin():
         assert not removed.search(code), (fn, removed.findall(code))
     from set_amd import autograd_ops
     assert not hasattr(autograd_ops, "DETERMINISTIC_WGRAD")
+
+
+REMOVED_PACK_ENTRIES = ("SetPackBf16Desc", "SetPackF32Desc", "set_sizeof_pack_bf16_desc", "set_sizeof_pack_f32_desc", "set_fill_pack_f32_desc",
+                        "set_pack_conv_weights_bf16_batch", "set_pack_conv_weights_f32_batch", "pack_conv_weight_v2_kernel",
+                        "pack_conv_weight_bf16_kernel", "pack_conv_weights_f32_batch_kernel", "pack_conv_weights_bf16_batch_kernel")
+
+
+def test_conv_weight_images_have_one_pack_kernel():
+    """csrc/weight_image.hip holds the one kernel that writes the packed conv-weight images (per image and batched, all three layouts);
+    the two-piece fp16 image with its scale tail keeps its own (pack_conv_x2_kernel).  The retired kernels, descriptor structs and batch
+    entries are named nowhere in the sources, the header or the package."""
+    pkg = os.path.join(ROOT, "speech-editing-toolkit_amd")
+    csrc = [os.path.join(pkg, "csrc", f) for f in sorted(os.listdir(os.path.join(pkg, "csrc"))) if f.endswith((".hip", ".h"))]
+    packers = []
+    for fn in csrc:
+        code = _strip_comments(open(fn).read())
+        packers += [(os.path.basename(fn), name) for name in re.findall(r"__global__\s+void\s+(?:__launch_bounds__\([^)]*\)\s*)?(\w+)\s*\(", code)
+                    if re.search(r"pack_conv_(weight|x2)", name)]
+    assert sorted(packers) == [("conv_x2.hip", "pack_conv_x2_kernel"), ("weight_image.hip", "pack_conv_weight_kernel")], packers
+    removed = re.compile(r"\b(%s)\b" % "|".join(REMOVED_PACK_ENTRIES))
+    files = [os.path.join(ROOT, "include", "set_amd.h")] + csrc + [os.path.join(pkg, f) for f in sorted(os.listdir(pkg)) if f.endswith(".py")]
+    for fn in files:
+        code = _strip_comments(open(fn).read(), python=fn.endswith(".py"))
+        assert not removed.search(code), (fn, removed.findall(code))
 
 
 PROBE_FILES = ("diffnet_x3.hip", "diffnet.hip", "diffnet_bf16.hip", "bf16.hip", "resblock_x2.hip")

@@ -6,6 +6,7 @@ tests/test_gpu_conv_branches.py compares every fp32 conv / wgrad kernel branch w
 The module also pins what no kernel test can see: which kernel `auto` picks for every conv shape of the shipped configs
 (ops._pick_impl), the host-only image size functions, and the split-K slice plan of the fp32 weight gradient for the cases the
 GPU sweep runs (the hand-computed numbers of WGRAD_CASES against the library's own scratch size)."""
+import ctypes as C
 import math
 import os
 
@@ -411,12 +412,31 @@ def _up(x, m):
 @pytest.mark.parametrize("Cout", [1, 31, 32, 33, 127, 128, 130, 191, 192, 200, 383, 384, 400, 512, 513])
 @pytest.mark.parametrize("Cin", [1, 15, 16, 17, 200, 256, 300])
 def test_packed_image_sizes_follow_their_formula(built_lib, Cout, Cin):
+    from set_amd import _lib
     for K in (1, 3, 11):
         # v1: 32-row blocks x K x channels padded to the 16-channel LDS chunk
         assert built_lib.set_packed_conv_weight_size(Cout, Cin, K) == _up(Cout, 32) * K * _up(Cin, 16)
         # v2: 128 * RB rows per block, RB = 4 / 2 / 1 for Cout >= 384 / >= 192 / else
         RB = 4 if Cout >= 384 else (2 if Cout >= 192 else 1)
         assert built_lib.set_packed_conv_weight_v2_size(Cout, Cin, K) == _up(Cout, 128 * RB) * K * _up(Cin, 16)
+        # set_fill_pack_desc holds the same rules: the element counts of the _size entries, the bf16 image's 128 / 32 roundings, and below
+        # the big-tile image's channels per LDS chunk as ConvWeight.packed_v2 picks its slot
+        d = _lib.SetPackDesc(Cout=Cout, Cin=Cin, K=K)
+        assert built_lib.set_fill_pack_desc(C.byref(d), _lib.IMG_F32, 0) == built_lib.set_packed_conv_weight_size(Cout, Cin, K)
+        assert (d.kind, d.CoutP, d.CinP, d.RB) == (_lib.IMG_F32, _up(Cout, 32), _up(Cin, 16), 1)
+        assert built_lib.set_fill_pack_desc(C.byref(d), _lib.IMG_BF16, 0) == built_lib.set_packed_conv_weight_bf16_size(Cout, Cin, K)
+        assert (d.kind, d.CoutP, d.CinP) == (_lib.IMG_BF16, _up(Cout, 128), _up(Cin, 32))
+    for K, dils in ((2, range(-64, 65)), (3, (1, -32)), (11, (-6, 7))):  # K = 2: every halo 0 .. 64 the big-tile kernel takes, both signs
+        for dil in dils:
+            halo = (K - 1) * abs(dil)
+            d = _lib.SetPackDesc(Cout=Cout, Cin=Cin, K=K)
+            assert built_lib.set_fill_pack_desc(C.byref(d), _lib.IMG_F32_BIG, dil) == built_lib.set_packed_conv_weight_v2_size(Cout, Cin, K)
+            assert (d.kind, d.CoutP, d.CinP, d.RB) == (_lib.IMG_F32_BIG, _up(Cout, 128 * RB), _up(Cin, 16), RB)
+            assert d.ch_max == (128 if (64 + halo) * 256 * 4 > 96 * 1024 else 256), (K, dil)  # ConvWeight.packed_v2's slot
+    d = _lib.SetPackDesc(Cout=Cout, Cin=Cin, K=0)
+    assert built_lib.set_fill_pack_desc(C.byref(d), _lib.IMG_F32, 0) == -1 and built_lib.set_fill_pack_desc(None, 0, 0) == -1
+    d.K = 1
+    assert built_lib.set_fill_pack_desc(C.byref(d), 3, 0) == -1 and built_lib.set_fill_pack_desc(C.byref(d), -1, 0) == -1
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -105,7 +105,7 @@ def test_pack_kernel_writes_the_modelled_image_and_nothing_else(dev, case):
 
 def test_batch_pack_writes_the_same_images(dev):
     from set_amd import _lib
-    arr = (_lib.SetPackBf16Desc * len(PACK))()
+    arr = (_lib.SetPackDesc * len(PACK))()
     bufs, wants, keep, start = [], [], [], 0
     for d, case in zip(arr, PACK):
         Cout, Cin, K, _ = case
@@ -117,17 +117,60 @@ def test_batch_pack_writes_the_same_images(dev):
         buf = _u16(dev, np.full(size + 2 * GUARD, IMG_SENTINEL, dtype=np.uint16))
         d.w, d.wp = _p(wd), _p(buf, 2 * GUARD)
         d.w_base, d.w_sco, d.w_sci, d.w_stap, d.start = addr["base"], addr["sco"], addr["sci"], addr["stap"], start
-        d.Cout, d.Cin, d.K, d.CoutP, d.CinP = Cout, Cin, K, up(Cout, 128), up(Cin, 32)
+        d.Cout, d.Cin, d.K = Cout, Cin, K
+        assert _L().set_fill_pack_desc(C.byref(d), _lib.IMG_BF16, 0) == size and (d.CoutP, d.CinP) == (up(Cout, 128), up(Cin, 32))
         start += size
         bufs.append(buf)
         wants.append(want)
         keep.append((wd, store))
     raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
-    assert _L().set_pack_conv_weights_bf16_batch(C.c_void_p(_p(raw)), len(PACK), start, _s()) == 0
+    assert _L().set_pack_conv_weights_batch(C.c_void_p(_p(raw)), len(PACK), start, _s()) == 0
     torch.cuda.synchronize()
     for buf, want, (wd, store), case in zip(bufs, wants, keep, PACK):
         assert np.array_equal(buf.cpu().numpy().view(np.uint16), want), case
         assert torch.equal(wd.cpu(), store)
+
+
+def test_one_table_mixes_the_three_image_kinds(dev):
+    """set_pack_conv_weights_batch over ONE table that holds an fp32 small-tile, an fp32 big-tile and a bf16 image (4- and 2-byte elements
+    behind one `start` search, in elements): each image bit-equal to what its per-image entry writes, nothing written outside the images
+    (both go into poisoned buffers with guards on either side, compared whole)."""
+    from set_amd import _lib
+    L, g, guard = _L(), torch.Generator().manual_seed(9), 256  # guard bytes
+    bf = min((c for c in PACK if c[0] % 128 or c[1] % 32), key=lambda c: L.set_packed_conv_weight_bf16_size(*c[:3]))  # smallest ragged one
+    bf_store, bf_addr = pack_operands(bf, seed=2)
+    cases = [  # kind, Cout, Cin, K, dil, raw weight, addressing, bytes per element
+        (_lib.IMG_F32, 7, 20, 3, 0, torch.randn(7, 20, 3, generator=g), dict(base=0, sco=60, sci=3, stap=1), 4),
+        (_lib.IMG_F32_BIG, 130, 100, 3, -17, torch.randn(100, 130, 3, generator=g), dict(base=0, sco=3, sci=130 * 3, stap=1), 4),  # transposed
+        (_lib.IMG_BF16, bf[0], bf[1], bf[2], 0, bf_store, bf_addr, 2),
+    ]
+    arr = (_lib.SetPackDesc * len(cases))()
+    pairs, start = [], 0
+    for d, (kind, Cout, Cin, K, dil, w, addr, esz) in zip(arr, cases):
+        wd = w.to(dev)
+        d.w, d.w_base, d.w_sco, d.w_sci, d.w_stap, d.start = _p(wd), addr["base"], addr["sco"], addr["sci"], addr["stap"], start
+        d.Cout, d.Cin, d.K = Cout, Cin, K
+        n = L.set_fill_pack_desc(C.byref(d), kind, dil)
+        assert n > 0
+        got, ref = (torch.full((n * esz + 2 * guard,), 0x5A, dtype=torch.uint8, device=dev) for _ in range(2))
+        d.wp = _p(got, guard)
+        a = (addr["base"], addr["sco"], addr["sci"], addr["stap"], _s())
+        if kind == _lib.IMG_F32:
+            assert L.set_packed_conv_weight_size(Cout, Cin, K) == n and L.set_pack_conv_weight(_p(wd), _p(ref, guard), Cout, Cin, K, *a) == 0
+        elif kind == _lib.IMG_F32_BIG:
+            assert L.set_packed_conv_weight_v2_size(Cout, Cin, K) == n and L.set_pack_conv_weight_v2(_p(wd), _p(ref, guard), Cout, Cin, K, dil, *a) == 0
+        else:
+            assert L.set_packed_conv_weight_bf16_size(Cout, Cin, K) == n and L.set_pack_conv_weight_bf16(_p(wd), _p(ref, guard), Cout, Cin, K, *a) == 0
+        pairs.append((got, ref, n * esz, kind))
+        start += n
+    raw = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    assert L.set_pack_conv_weights_batch(C.c_void_p(_p(raw)), len(cases), start, _s()) == 0
+    torch.cuda.synchronize()
+    for got, ref, nbytes, kind in pairs:
+        for buf in (got, ref):  # guards untouched, the image written (a zero-padded image of nonzero weights is not the poison)
+            assert bool((buf[:guard] == 0x5A).all()) and bool((buf[guard + nbytes:] == 0x5A).all()), kind
+            assert not bool((buf[guard:guard + nbytes] == 0x5A).all()), kind
+        assert torch.equal(got, ref), kind
 
 
 # ------------------------------------------------------------------------------------------------------------------------

@@ -124,7 +124,7 @@ FWD = [
     _case("v2_rb4_ch256_one_chunk_ragged", NMV, 1, 48, 400, 5, 1, 64),
     # RB 1, Cout 130 (two row blocks, the second ragged); halo 34 > 32: ch_max 128, CinP 112: one chunk
     _case("v2_rb1_ch128_one_chunk_ragged", NMV, 1, 100, 130, 3, 17, 100, pro="lrelu"),
-    # RB 2, Cout 192; halo 50: ch_max 128, Cin 256: two 128-channel chunks (the decode loop of pack_conv_weight_v2_kernel and the
+    # RB 2, Cout 192; halo 50: ch_max 128, Cin 256: two 128-channel chunks (the decode loop of the big-tile image, img_f32_big_index, and the
     # kernel's walk with CH = 128)
     _case("v2_rb2_ch128_two_chunks", NMV, 1, 256, 192, 11, 5, 96, res=True),
     # RB 4, Cout 384; halo 64 exactly (the largest admitted): ch_max 128, CinP 304: chunks 128 + 128 + 48 (ragged third chunk)
@@ -390,8 +390,8 @@ def test_forward_inventory_is_complete():
 
 
 # ------------------------------------------------------------------------------------------------------------------------
-# the one-launch re-pack of the optimizer (pack_conv_weights_f32_batch_kernel) has its own copy of both image layouts and of the v2
-# chunk decode loop: same bits as set_pack_conv_weight / set_pack_conv_weight_v2 for the layouts the forward cases above validate
+# the one-launch re-pack of the optimizer (set_pack_conv_weights_batch: the pack kernel over a descriptor table on the device): same bits as
+# set_pack_conv_weight / set_pack_conv_weight_v2 (the same kernel, one descriptor by value) for the layouts the forward cases above validate
 # ------------------------------------------------------------------------------------------------------------------------
 REPACK = [
     # Cout, Cin, K, dil, wview

@@ -863,7 +863,7 @@ def test_gate_and_res_skip_backward_vector_and_scalar_forms(dev):
 
 @pytest.mark.parametrize("stack", ["per_op", "fused_stack"])
 def test_batched_fp32_image_repack_equals_the_per_image_packs_and_marks_them_current(dev, monkeypatch, stack):
-    """ops.repack_f32_images / set_pack_conv_weights_f32_batch and set_pack_diffnet_layers (round 5): after an fp32 optimizer step every weight
+    """ops.repack_f32_images / set_pack_conv_weights_batch and set_pack_diffnet_layers (round 5): after an fp32 optimizer step every weight
     image the step used has been re-packed by ONE launch (two for the DiffNet stack).  Each must equal, bit for bit, the image the
     one-launch-per-weight entry points (set_pack_conv_weight, set_pack_conv_weight_v2, set_pack_diffnet_layer(_wino)) make of the
     updated weight, and the next step must not pack anything again lazily."""

@@ -271,7 +271,7 @@ def test_entry_refuses_before_any_device_call(built_lib):
                  dict(reflect=1, pad=384, N=384, wav_bs=384, T=1), dict(table=20)):
         assert L.set_log_mel(C.byref(_args(_lib, **over)), None) == _lib.E_INVALID, over
     assert L.set_log_mel_table_size(1024, 352) == 2 * 352 * 1024 and L.set_log_mel_table_size(1024, 513) == 2 * 544 * 1024
-    assert L.set_abi_version() == 4
+    assert L.set_abi_version() == 5
 
 
 def test_no_cpu_fallback(M, shipped):
