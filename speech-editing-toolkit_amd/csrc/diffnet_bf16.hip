@@ -72,21 +72,20 @@ __device__ __forceinline__ u32x2_t buf_load_q4(rsrc_t r, unsigned voff, unsigned
     return __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, (int)soff, 0);
 }
 
-// acc[NRB][NCB] += A * B over `nks` k-steps.  A: image [ks][NRB][lane][8 bf16] at `img` (byte offsets), one b128 load
-// per (ks, rb), ring of PF k-steps.  B: bfrag(ks, cb) returns the LDS byte address of this lane's 16-byte fragment.
-template <int NRB, int NCB, typename BF>
-__device__ __forceinline__ void gemm_bf16(f32x16 (&acc)[NRB][NCB], rsrc_t img, unsigned lane16, int ks0, int nks,
-                                          const unsigned char *lds, BF bfrag) {
+// acc[NRB][NCB] += A * B over `nks` k-steps (a multiple of PF).  A: 1 KiB fragment blocks [lane][8 bf16] of a packed image at `img`, one b128
+// load per (ks, rb) at byte offset aoff(ks, rb), ring of PF k-steps.  B: bfrag(ks, cb) returns the LDS byte address of this lane's 16-byte fragment.
+template <int NRB, int NCB, typename AF, typename BF>
+__device__ __forceinline__ void gemm_bf16(f32x16 (&acc)[NRB][NCB], rsrc_t img, unsigned lane16, int nks, const unsigned char *lds,
+                                          AF aoff, BF bfrag) {
     u32x4_t A[PF][NRB];
 #pragma unroll
     for (int p = 0; p < PF; ++p)
 #pragma unroll
-        for (int rb = 0; rb < NRB; ++rb)
-            A[p][rb] = buf_load_u4(img, lane16, (unsigned)(((ks0 + min(p, nks - 1)) * NRB + rb) * 1024));
+        for (int rb = 0; rb < NRB; ++rb) A[p][rb] = buf_load_u4(img, lane16, aoff(min(p, nks - 1), rb));
     for (int kb = 0; kb < nks; kb += PF) {
 #pragma unroll
         for (int p = 0; p < PF; ++p) {
-            const int ks = kb + p;  // nks is a multiple of PF
+            const int ks = kb + p;
             u32x4_t Bv[NCB];
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) Bv[cb] = *reinterpret_cast<const u32x4_t *>(lds + bfrag(ks, cb));
@@ -101,7 +100,7 @@ __device__ __forceinline__ void gemm_bf16(f32x16 (&acc)[NRB][NCB], rsrc_t img, u
             __builtin_amdgcn_s_setprio(0);
             const int kn = min(ks + PF, nks - 1);  // tail: harmless re-load of the last k-step
 #pragma unroll
-            for (int rb = 0; rb < NRB; ++rb) A[p][rb] = buf_load_u4(img, lane16, (unsigned)(((ks0 + kn) * NRB + rb) * 1024));
+            for (int rb = 0; rb < NRB; ++rb) A[p][rb] = buf_load_u4(img, lane16, aoff(kn, rb));
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -174,44 +173,14 @@ __global__ void __launch_bounds__(256) pack_layer_bf16_kernel(const float *wdil,
 // =====================================================================================================================
 // forward
 // =====================================================================================================================
-// acc[NRB][NCB] += A * B with a caller-supplied A address: aoff(ks, rb) = byte offset of the 1 KiB fragment block
-template <int NRB, int NCB, int PFD = PF, typename AF, typename BF>
-__device__ __forceinline__ void gemm_bf16_a(f32x16 (&acc)[NRB][NCB], rsrc_t img, unsigned lane16, int nks, const unsigned char *lds,
-                                            AF aoff, BF bfrag) {
-    u32x4_t A[PFD][NRB];
-#pragma unroll
-    for (int p = 0; p < PFD; ++p)
-#pragma unroll
-        for (int rb = 0; rb < NRB; ++rb) A[p][rb] = buf_load_u4(img, lane16, aoff(min(p, nks - 1), rb));
-    for (int kb = 0; kb < nks; kb += PFD) {
-#pragma unroll
-        for (int p = 0; p < PFD; ++p) {
-            const int ks = kb + p;  // nks is a multiple of PFD
-            u32x4_t Bv[NCB];
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) Bv[cb] = *reinterpret_cast<const u32x4_t *>(lds + bfrag(ks, cb));
-            __builtin_amdgcn_sched_barrier(0);  // pinned order, see gemm_bf16
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int rb = 0; rb < NRB; ++rb)
-#pragma unroll
-                for (int cb = 0; cb < NCB; ++cb) acc[rb][cb] = mma16(A[p][rb], Bv[cb], acc[rb][cb]);
-            __builtin_amdgcn_s_setprio(0);
-            const int kn = min(ks + PFD, nks - 1);  // tail: harmless re-load of the last k-step
-#pragma unroll
-            for (int rb = 0; rb < NRB; ++rb) A[p][rb] = buf_load_u4(img, lane16, aoff(kn, rb));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-}
-
 // TRAIN: also store the pre-gate y and the gated z in bf16 (operands of the backward).
-// NT: frames per tile = 128: 8 waves, one 32-row gate block + its filter block per wave, one block per CU (120 KB of LDS).
-template <bool TRAIN, int NT>
-__global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDiffnetLayerBf16Args a) {
+// Tile = FNT = 128 frames: 8 waves, one 32-row gate block + its filter block per wave, one block per CU (120 KB of LDS).  (Round 3's 64-frame
+// tile on 4 waves with two gate blocks each -- two blocks per CU -- spilled registers and measured slower; the tile-width parameter and
+// its "virtual wave" indexing are gone.)
+template <bool TRAIN>
+__global__ void __launch_bounds__(512, 1) diffnet_layer_fwd_bf16_kernel(SetDiffnetLayerBf16Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    constexpr int NW = NT / 16;   // waves per block
-    constexpr int RBW = 8 / NW;   // 32-row gate blocks per wave (and as many filter blocks)
+    constexpr int NT = FNT;
     constexpr int NCB = NT / 32;  // 32-frame column blocks
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -232,11 +201,10 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
     const unsigned short *img = reinterpret_cast<const unsigned short *>(a.img);
     const rsrc_t rw1 = make_rsrc(img), rw2 = make_rsrc(img + OFF_W2B);
     const unsigned lane16 = 16u * (unsigned)lane;
-    // accumulator index rb = g * RBW + q: g = 0 gate / residual rows, 1 filter / skip rows; q-th 32-row block of the wave,
-    // i.e. block vw = RBW * w + q of the packed images ("virtual wave" of the 8-wave layout)
-    auto row0 = [&](int rb) { return ((rb / RBW) ? FC : 0) + 32 * (RBW * w + (rb % RBW)); };
-    auto aoff1 = [&](int ks, int rb) { return (unsigned)((((RBW * w + (rb % RBW)) * KS1 + ks) * 2 + rb / RBW) * 1024); };
-    auto aoff2 = [&](int ks, int rb) { return (unsigned)((((RBW * w + (rb % RBW)) * KS2 + ks) * 2 + rb / RBW) * 1024); };
+    // accumulator index rb: 0 gate / residual rows, 1 filter / skip rows of the wave's 32-row block
+    auto row0 = [&](int rb) { return (rb ? FC : 0) + 32 * w; };
+    auto aoff1 = [&](int ks, int rb) { return (unsigned)(((w * KS1 + ks) * 2 + rb) * 1024); };
+    auto aoff2 = [&](int ks, int rb) { return (unsigned)(((w * KS2 + ks) * 2 + rb) * 1024); };
 
     PhaseProbe<5> pp;
     pp.start(g_bf16_phase_buf && blockIdx.x == 1 && blockIdx.y == 1);
@@ -302,10 +270,9 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
         }
     }
     // ---- accumulators start at the biases (b_dil + b_cond): row of register r = row0(rb) + urow16(r) + 4 half
-    f32x16 acc[2 * RBW][NCB];
-    const unsigned lb = 16u * (unsigned)half;  // byte offset of the lane's 4-row group
+    f32x16 acc[2][NCB];
 #pragma unroll
-    for (int rb = 0; rb < 2 * RBW; ++rb)
+    for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
             const f32x4 bv = *reinterpret_cast<const f32x4 *>(bsh + row0(rb) + 8 * g4 + 4 * half);
@@ -318,17 +285,17 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
     pp.lap(0);
 
     // ---- GEMM 1: y = [Wcond | Wdil tap 0 | tap 1 | tap 2] x [cond ; x+d shifted]
-    gemm_bf16_a<2 * RBW, NCB>(acc, rw1, lane16, KS_C, lds, aoff1, [&](int ks, int cb) {
+    gemm_bf16<2, NCB>(acc, rw1, lane16, KS_C, lds, aoff1, [&](int ks, int cb) {
         return (unsigned)(XROWS * XR + (cb * 32 + l31) * CR + (ks * 16 + half * 8) * 2);
     });
-    gemm_bf16_a<2 * RBW, NCB>(acc, rw1, lane16, 3 * KS_T, lds, [&](int ks, int rb) { return aoff1(KS_C + ks, rb); },
+    gemm_bf16<2, NCB>(acc, rw1, lane16, 3 * KS_T, lds, [&](int ks, int rb) { return aoff1(KS_C + ks, rb); },
                               [&](int ks, int cb) {
         const int tap = ks >> 4, c0 = (ks & 15) * 16;
         return (unsigned)((cb * 32 + l31 + tap * d) * XR + (c0 + half * 8) * 2);
     });
 
     pp.lap(1);
-    // ---- gate (lane-local: rb < RBW gate rows, rb + RBW the matching filter rows); save y and z in bf16; z tile over the x tile
+    // ---- gate (lane-local: rb 0 gate rows, rb 1 the matching filter rows); save y and z in bf16; z tile over the x tile
     bool tv[NCB];
     unsigned vo4[NCB], vo2[NCB];
 #pragma unroll
@@ -339,91 +306,80 @@ __global__ void __launch_bounds__(NT * 4, 1) diffnet_layer_fwd_bf16_kernel(SetDi
         vo2[cb] = 8u * (unsigned)(half * T + min(t, T - 1));  // quad-interleaved bf16: channel quad + half, frame t
     }
     // residual rows of x for GEMM 2's accumulator start: issued here, consumed after the gate (hidden under it)
-    float xres[RBW][NCB][16];
+    float xres[NCB][16];
 #pragma unroll
-    for (int q = 0; q < RBW; ++q)
+    for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) xres[q][cb][r] = buf_load(rx, vo4[cb], (unsigned)(row0(q) + urow16(r)) * T4);
+        for (int r = 0; r < 16; ++r) xres[cb][r] = buf_load(rx, vo4[cb], (unsigned)(row0(0) + urow16(r)) * T4);
     __syncthreads();  // every wave is done reading the x tile
 #pragma unroll
-    for (int q = 0; q < RBW; ++q)
+    for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
+        for (int g4 = 0; g4 < 4; ++g4) {  // registers 4 g4 .. 4 g4 + 3 = channels row0(0) + 8 g4 + 4 half + (0 .. 3)
+            float yg[4], yf[4], z[4];
 #pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {  // registers 4 g4 .. 4 g4 + 3 = channels row0(q) + 8 g4 + 4 half + (0 .. 3)
-                float yg[4], yf[4], z[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    yg[e] = acc[q][cb][4 * g4 + e]; yf[e] = acc[RBW + q][cb][4 * g4 + e];
-                    z[e] = tv[cb] ? fsig(yg[e]) * ftanh(yf[e]) : 0.0f;
-                }
-                u32x2_t zq;
-                zq[0] = pack2(z[0], z[1]); zq[1] = pack2(z[2], z[3]);
-                if constexpr (TRAIN) {
-                    if (tv[cb]) {
-                        const unsigned so = (unsigned)(row0(q) + 8 * g4) * T2;
-                        u32x2_t gq, fq;
-                        gq[0] = pack2(yg[0], yg[1]); gq[1] = pack2(yg[2], yg[3]);
-                        fq[0] = pack2(yf[0], yf[1]); fq[1] = pack2(yf[2], yf[3]);
-                        buf_store_q4(gq, ry, vo2[cb], so);
-                        buf_store_q4(fq, ry, vo2[cb], so + (unsigned)FC * T2);
-                        buf_store_q4(zq, rz, vo2[cb], so);
-                    }
-                }
-                *reinterpret_cast<u32x2_t *>(xs + (cb * 32 + l31) * XR + (row0(q) + 8 * g4 + 4 * half) * 2) = zq;
+            for (int e = 0; e < 4; ++e) {
+                yg[e] = acc[0][cb][4 * g4 + e]; yf[e] = acc[1][cb][4 * g4 + e];
+                z[e] = tv[cb] ? fsig(yg[e]) * ftanh(yf[e]) : 0.0f;
             }
+            u32x2_t zq;
+            zq[0] = pack2(z[0], z[1]); zq[1] = pack2(z[2], z[3]);
+            if constexpr (TRAIN) {
+                if (tv[cb]) {
+                    const unsigned so = (unsigned)(row0(0) + 8 * g4) * T2;
+                    u32x2_t gq, fq;
+                    gq[0] = pack2(yg[0], yg[1]); gq[1] = pack2(yg[2], yg[3]);
+                    fq[0] = pack2(yf[0], yf[1]); fq[1] = pack2(yf[2], yf[3]);
+                    buf_store_q4(gq, ry, vo2[cb], so);
+                    buf_store_q4(fq, ry, vo2[cb], so + (unsigned)FC * T2);
+                    buf_store_q4(zq, rz, vo2[cb], so);
+                }
+            }
+            *reinterpret_cast<u32x2_t *>(xs + (cb * 32 + l31) * XR + (row0(0) + 8 * g4 + 4 * half) * 2) = zq;
+        }
     // ---- accumulators of GEMM 2: residual rows start at x + b_out, skip rows at b_out (the running skip sum is added in
     //      the epilogue, after the x' stores are in flight)
     const bool first = a.first != 0;
 #pragma unroll
-    for (int rb = 0; rb < 2 * RBW; ++rb)
+    for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
         for (int g4 = 0; g4 < 4; ++g4) {
             const f32x4 bv = *reinterpret_cast<const f32x4 *>(bsh + 2 * FC + row0(rb) + 8 * g4 + 4 * half);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
 #pragma unroll
-                for (int cb = 0; cb < NCB; ++cb) acc[rb][cb][4 * g4 + e] = rb < RBW ? bv[e] + xres[rb % RBW][cb][4 * g4 + e] : bv[e];
+                for (int cb = 0; cb < NCB; ++cb) acc[rb][cb][4 * g4 + e] = rb == 0 ? bv[e] + xres[cb][4 * g4 + e] : bv[e];
         }
     __syncthreads();
     pp.lap(2);
 
     // ---- GEMM 2: o = Wout z
-    gemm_bf16_a<2 * RBW, NCB>(acc, rw2, lane16, KS2, lds, aoff2, [&](int ks, int cb) {
+    gemm_bf16<2, NCB>(acc, rw2, lane16, KS2, lds, aoff2, [&](int ks, int cb) {
         return (unsigned)((cb * 32 + l31) * XR + (ks * 16 + half * 8) * 2);
     });
 
     pp.lap(3);
     // ---- epilogue: x' stores first (they need nothing), then the running skip sum is fetched and updated
 #pragma unroll
-    for (int q = 0; q < RBW; ++q)
+    for (int cb = 0; cb < NCB; ++cb) {
+        if (tv[cb]) {
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            if (tv[cb]) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) buf_store(acc[q][cb][r] * RSQRT2, rxo, vo4[cb], (unsigned)(row0(q) + urow16(r)) * T4);
-            }
+            for (int r = 0; r < 16; ++r) buf_store(acc[0][cb][r] * RSQRT2, rxo, vo4[cb], (unsigned)(row0(0) + urow16(r)) * T4);
         }
-    float sk[RBW][NCB][16];
+    }
+    float sk[NCB][16];
 #pragma unroll
-    for (int q = 0; q < RBW; ++q)
+    for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
+        for (int r = 0; r < 16; ++r) sk[cb][r] = buf_load(rsk, vo4[cb], (unsigned)(row0(0) + urow16(r)) * T4);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sk[q][cb][r] = buf_load(rsk, vo4[cb], (unsigned)(row0(q) + urow16(r)) * T4);
+    for (int cb = 0; cb < NCB; ++cb) {
+        if (tv[cb]) {
 #pragma unroll
-    for (int q = 0; q < RBW; ++q)
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-            if (tv[cb]) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    buf_store(first ? acc[RBW + q][cb][r] : acc[RBW + q][cb][r] + sk[q][cb][r], rsk, vo4[cb],
-                              (unsigned)(row0(q) + urow16(r)) * T4);
-            }
+            for (int r = 0; r < 16; ++r)
+                buf_store(first ? acc[1][cb][r] : acc[1][cb][r] + sk[cb][r], rsk, vo4[cb], (unsigned)(row0(0) + urow16(r)) * T4);
         }
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     pp.lap(4);
     pp.flush(g_bf16_phase_buf);
@@ -456,86 +412,159 @@ struct LayersArgs {
 //     its epilogue runs under the partner's GEMM 2;
 //   * barriers wait for LDS traffic only (s_waitcnt lgkmcnt(0); s_barrier): the A-fragment loads of the NEXT GEMM are issued
 //     BEFORE the barrier that opens it, so the L2 round trip of the first k-steps is spent waiting for the slowest wave anyway;
-//   * GEMM 1 is ONE 60-k-step stream (12 conditioner + 3 x 16 tap k-steps; the ring of PFD k-steps never drains between the
+//   * GEMM 1 is ONE 60-k-step stream (12 conditioner + 3 x 16 tap k-steps; the ring of 4 k-steps never drains between the
 //     conditioner and the taps);
 //   * the biases of every fused layer are staged in LDS once per launch (they were 96 dependent 4-byte L2 loads per wave and layer);
-//   * SKEW (template parameter, not instantiated in the shipped library): a static priority for waves 0-3 (wave w and w + 4 share a
-//     SIMD) instead of the per-k-step toggles.  Measured both ways round (priority to the older / to the younger half): the favoured
-//     half leaves GEMM 1 after 54 % of a layer and waits at the barrier, the other after 69 %; the layer takes the same time.
+//   * SKEW (a variant that is gone from the source): a static priority for waves 0-3 (wave w and w + 4 share a SIMD) instead of the
+//     per-k-step toggles.  Measured both ways round (priority to the older / to the younger half): the favoured half left GEMM 1 after
+//     54 % of a layer and waited at the barrier, the other after 69 %; the layer took the same time.
 // Same arithmetic per frame as diffnet_layer_fwd_bf16_kernel (same images, k order, accumulator start, rounding points): bit-identical.
 // =====================================================================================================================
-// acc[2][2] += A B over NKS k-steps in groups of 4; the ring A[4 D][2] holds k-steps 0 .. 4 D - 1 on entry (gemm_reg_prefetch) and is
-// refilled 4 D k-steps ahead (D = 1, 2 groups).  The schedule is pinned, one sched_barrier per k-step:
-//     ds_read B(k + 1)  |  4 MFMAs of k-step k  |  buffer_load A(k + 4 D) into the registers those MFMAs just read
+// acc[NRB][NCB] += A B over NKS k-steps in groups of 4, for both layer-group kernels; the ring A[4][NRB] holds k-steps 0 .. 3 on entry
+// (gemm_grp_prefetch) and is refilled 4 k-steps ahead.  The schedule is pinned, one sched_barrier per k-step:
+//     ds_read B(k + 1)  |  NRB NCB MFMAs of k-step k  |  buffer_load A(k + 4) into the registers those MFMAs just read
 // Left to itself the scheduler (a) fully unrolled: sank every A load to one MFMA pair in front of its use and spilled the hoisted SGPR
 // offsets of 120 loads; (b) as a loop: moved all refills of a group to the END of the group and waited for all of them (vmcnt(0))
 // at the top of the next -- an L2 round trip per 16 MFMAs.  The group loop is not unrolled (ring registers are loop-carried).
-// bgrp(kb) returns the LDS byte addresses of the lane's B fragments of k-step kb for the two column blocks; k-step kb + p is 32 p
-// bytes further (a group of 4 never straddles the conditioner / tap segments: 12 and 16 are multiples of 4).
-template <int NKS, int D, bool TOGGLE, typename BG>
-__device__ __forceinline__ void gemm_reg_run(f32x16 (&acc)[2][2], u32x4_t (&A)[4 * D][2], rsrc_t img, unsigned lane16, unsigned abase,
+// aoff(ks, rb): wave-uniform byte offset of the 1 KiB fragment block; avo: per-lane byte offset inside it.
+// bgrp(kb, b0, bs) returns the LDS byte address of the lane's B fragment of k-step kb for column block 0 and the stride to the next column
+// block; k-step kb + p is 32 p bytes further (a group of 4 never straddles the conditioner / tap segments: 12 and 16 are multiples of 4).
+// BDB: the B fragments of k-step k + 1 are read under the MFMAs of k-step k (4 NCB more registers); else each k-step reads its own.
+// (Measured and gone: a ring of two groups, 8 k-steps, with its two-slot drain -- within 0.5 % on the 64-frame kernel, profiles/r04_bf16_ab.log --
+// and a switch that dropped the per-k-step priority toggles for a static wave priority, see SKEW above.  What each operand stream of the
+// 128-frame layer costs -- weight refills, B-fragment reads, skip traffic -- was measured with builds that drop it, results wrong by
+// construction: profiles/r04_t128_exp.log.)
+template <int NRB, int NCB, int NKS, bool BDB, typename AO, typename BG>
+__device__ __forceinline__ void gemm_grp_run(f32x16 (&acc)[NRB][NCB], u32x4_t (&A)[4][NRB], rsrc_t img, unsigned avo, AO aoff,
                                              const unsigned char *lds, BG bgrp) {
-    // abase: byte offset of the wave's first fragment block (k-step 0, gate rows); k-step ks, row block rb at abase + (2 ks + rb) KiB
     constexpr int NG = NKS / 4;
-    static_assert(NKS % 4 == 0 && NG >= 2 * D && (D == 1 || D == 2), "gemm_reg_run");
-    u32x4_t Bq[2][2];  // B fragments of the current / the next k-step (parity of the k-step), [cb]
-    {
-        unsigned b0, b1;
-        bgrp(0, b0, b1);
-        Bq[0][0] = *reinterpret_cast<const u32x4_t *>(lds + b0);
-        Bq[0][1] = *reinterpret_cast<const u32x4_t *>(lds + b1);
+    static_assert(NKS % 4 == 0 && NG >= 2, "gemm_grp_run");
+    u32x4_t Bq[BDB ? 2 : 1][NCB];  // BDB: B fragments of the current / the next k-step (parity of the k-step)
+    if (BDB) {
+        unsigned b0, bs;
+        bgrp(0, b0, bs);
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) Bq[0][cb] = *reinterpret_cast<const u32x4_t *>(lds + b0 + cb * bs);
     }
-    auto group = [&](int kb, int slot, bool refill, bool more) {  // slot / refill / more: compile-time at every call site
-        unsigned b0, b1, n0 = 0, n1 = 0;
-        bgrp(kb, b0, b1);
-        if (more) bgrp(kb + 4, n0, n1);
+    auto group = [&](int kb, bool more) {  // more (another group follows: refill the ring, read its first B fragments): compile-time at both call sites
+        unsigned b0, bs, n0 = 0, ns = 0;
+        bgrp(kb, b0, bs);
+        if (BDB && more) bgrp(kb + 4, n0, ns);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            if (p < 3) {
-                Bq[(p + 1) & 1][0] = *reinterpret_cast<const u32x4_t *>(lds + b0 + 32 * (p + 1));
-                Bq[(p + 1) & 1][1] = *reinterpret_cast<const u32x4_t *>(lds + b1 + 32 * (p + 1));
+            if (!BDB) {
+#pragma unroll
+                for (int cb = 0; cb < NCB; ++cb) Bq[0][cb] = *reinterpret_cast<const u32x4_t *>(lds + b0 + cb * bs + 32 * p);
+            } else if (p < 3) {
+#pragma unroll
+                for (int cb = 0; cb < NCB; ++cb) Bq[(p + 1) & 1][cb] = *reinterpret_cast<const u32x4_t *>(lds + b0 + cb * bs + 32 * (p + 1));
             } else if (more) {
-                Bq[0][0] = *reinterpret_cast<const u32x4_t *>(lds + n0);
-                Bq[0][1] = *reinterpret_cast<const u32x4_t *>(lds + n1);
+#pragma unroll
+                for (int cb = 0; cb < NCB; ++cb) Bq[0][cb] = *reinterpret_cast<const u32x4_t *>(lds + n0 + cb * ns);
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (TOGGLE) __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int rb = 0; rb < 2; ++rb)
+            for (int rb = 0; rb < NRB; ++rb)
 #pragma unroll
-                for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = mma16(A[4 * slot + p][rb], Bq[p & 1][cb], acc[rb][cb]);
-            if (TOGGLE) __builtin_amdgcn_s_setprio(0);
-            if (refill) {
+                for (int cb = 0; cb < NCB; ++cb) acc[rb][cb] = mma16(A[p][rb], Bq[BDB ? (p & 1) : 0][cb], acc[rb][cb]);
+            __builtin_amdgcn_s_setprio(0);
+            if (more) {
 #pragma unroll
-                for (int rb = 0; rb < 2; ++rb)
-                    A[4 * slot + p][rb] = buf_load_u4(img, lane16, abase + (unsigned)((2 * (kb + p + 4 * D) + rb) * 1024));
+                for (int rb = 0; rb < NRB; ++rb) A[p][rb] = buf_load_u4(img, avo, aoff(kb + p + 4, rb));
             }
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    if constexpr (D == 1) {
 #pragma unroll 1
-        for (int g = 0; g < NG - 1; ++g) group(4 * g, 0, true, true);
-        group(4 * (NG - 1), 0, false, false);
-    } else {
-        constexpr int NR = NG - 2;          // groups that refill their slot
-        constexpr int NP = NR / 2;          // ... in pairs
-#pragma unroll 1
-        for (int g = 0; g < 2 * NP; g += 2) { group(4 * g, 0, true, true); group(4 * g + 4, 1, true, true); }
-        if constexpr (NR % 2) {             // (NG odd) one more refilling group: slot 0, then slots 1, 0 drain
-            group(4 * (NG - 3), 0, true, true); group(4 * (NG - 2), 1, false, true); group(4 * (NG - 1), 0, false, false);
-        } else {
-            group(4 * (NG - 2), 0, false, true); group(4 * (NG - 1), 1, false, false);
+    for (int g = 0; g < NG - 1; ++g) group(4 * g, true);
+    group(4 * (NG - 1), false);
+}
+template <int NRB, typename AO>
+__device__ __forceinline__ void gemm_grp_prefetch(u32x4_t (&A)[4][NRB], rsrc_t img, unsigned avo, AO aoff) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb) A[p][rb] = buf_load_u4(img, avo, aoff(p, rb));
+}
+// ---- the tile stager of the layer-group kernels (512 threads): thread (frame row f, channel group cg) writes
+//        xs row j <-> frame ts - d + j, j < NT + 2 d:  bf16(x + step offset dsh[channel]), zeros outside [0, T)   (row stride XR)
+//        cs row j <-> frame ts + j,     j < NT:        bf16(cond), zeros outside [0, T)                          (row stride CR)
+//      and a finite filler into the rows NT + 2 d .. xrows - 1 (layers with a larger dilation than layer 0's d address them).  The tile
+//      origin ts may be negative.  All loads of the main pass are in flight before the first is consumed, loads are unconditional on
+//      clamped addresses, selects after (as in diffnet_layer_fwd_bf16_kernel, where the choices are explained).  The caller writes dsh
+//      (the step offsets of layer 0); the block barrier in here orders those writes before their use.
+//      diffnet_layer_fwd_bf16_kernel keeps its own copy of these lines (no negative origin, no filler rows): a helper function is
+//      optimised on its own before it is inlined, and through this one the per-layer kernel came out with other instructions,
+//      one more VGPR and 12 SGPRs spilled to lanes (tools/isa_scan.py compare; profiles/diffnet_bf16_refactor.log).
+template <int NT>
+__device__ __forceinline__ void stage_tiles(unsigned char *xs, unsigned char *cs, const float *dsh, rsrc_t rx, rsrc_t rcd, int ts, int d,
+                                            int T, int xrows) {
+    constexpr int NTH = 512, NCG = NTH / NT, CPX = FC / NCG, CPC = FH / NCG;  // channel groups; channels of x / cond per thread
+    const unsigned T4 = 4u * (unsigned)T;
+    const int tid = threadIdx.x, f = tid % NT, cg = __builtin_amdgcn_readfirstlane(tid / NT);
+    const int t = ts - d + f;           // x row j = f
+    const bool tvx = t >= 0 && t < T;
+    const unsigned vox = 4u * (unsigned)min(max(t, 0), T - 1);
+    const int tcn = ts + f;             // cond row f
+    const bool tvc = tcn >= 0 && tcn < T;
+    const unsigned voc = 4u * (unsigned)min(max(tcn, 0), T - 1);
+    float vx[CPX], vc[CPC];
+#pragma unroll
+    for (int k = 0; k < CPX; ++k) vx[k] = buf_load(rx, vox, (unsigned)(CPX * cg + k) * T4);
+#pragma unroll
+    for (int k = 0; k < CPC; ++k) vc[k] = buf_load(rcd, voc, (unsigned)(CPC * cg + k) * T4);
+    for (int i = tid; i < (xrows - (NT + 2 * d)) * (XR / 16); i += NTH)
+        *reinterpret_cast<u32x4_t *>(xs + (NT + 2 * d) * XR + i * 16) = (u32x4_t){0u, 0u, 0u, 0u};
+    __syncthreads();  // dsh
+#pragma unroll
+    for (int q = 0; q < CPX / 8; ++q) {
+        const f32x4 d0 = *reinterpret_cast<const f32x4 *>(dsh + CPX * cg + 8 * q);
+        const f32x4 d1 = *reinterpret_cast<const f32x4 *>(dsh + CPX * cg + 8 * q + 4);
+        u32x4_t u;
+        u[0] = tvx ? pack2(vx[8 * q + 0] + d0[0], vx[8 * q + 1] + d0[1]) : 0u;
+        u[1] = tvx ? pack2(vx[8 * q + 2] + d0[2], vx[8 * q + 3] + d0[3]) : 0u;
+        u[2] = tvx ? pack2(vx[8 * q + 4] + d1[0], vx[8 * q + 5] + d1[1]) : 0u;
+        u[3] = tvx ? pack2(vx[8 * q + 6] + d1[2], vx[8 * q + 7] + d1[3]) : 0u;
+        *reinterpret_cast<u32x4_t *>(xs + f * XR + (CPX * cg + 8 * q) * 2) = u;
+    }
+#pragma unroll
+    for (int q = 0; q < CPC / 8; ++q) {
+        u32x4_t u;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) u[e] = tvc ? pack2(vc[8 * q + 2 * e], vc[8 * q + 2 * e + 1]) : 0u;
+        *reinterpret_cast<u32x4_t *>(cs + f * CR + (CPC * cg + 8 * q) * 2) = u;
+    }
+    // halo rows j = NT .. NT + 2d - 1: only the first 2d lanes of each channel group have one
+    if (f < 2 * d) {
+        const int j = NT + f, th = ts - d + j;
+        const bool tvh = th >= 0 && th < T;
+        const unsigned voh = 4u * (unsigned)min(max(th, 0), T - 1);
+        float vh[CPX];
+#pragma unroll
+        for (int k = 0; k < CPX; ++k) vh[k] = buf_load(rx, voh, (unsigned)(CPX * cg + k) * T4);
+#pragma unroll
+        for (int q = 0; q < CPX / 8; ++q) {
+            u32x4_t u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                u[e] = tvh ? pack2(vh[8 * q + 2 * e] + dsh[CPX * cg + 8 * q + 2 * e], vh[8 * q + 2 * e + 1] + dsh[CPX * cg + 8 * q + 2 * e + 1]) : 0u;
+            *reinterpret_cast<u32x4_t *>(xs + j * XR + (CPX * cg + 8 * q) * 2) = u;
         }
     }
 }
-template <int PFD>
-__device__ __forceinline__ void gemm_reg_prefetch(u32x4_t (&A)[PFD][2], rsrc_t img, unsigned lane16, unsigned abase) {
-#pragma unroll
-    for (int p = 0; p < PFD; ++p)
-#pragma unroll
-        for (int rb = 0; rb < 2; ++rb) A[p][rb] = buf_load_u4(img, lane16, abase + (unsigned)((2 * p + rb) * 1024));
+
+// LDS byte address b0 of the lane's GEMM 1 B fragment of k-step kb in column block 0 and the stride bs to the next column block: k-steps
+// < KS_C read the conditioner tile (lane base bc0), the others tap (kb - KS_C) / 16 of the x tile (lane base bx0, dx = dilation rows in bytes).
+// Branch-free (a select on the uniform kb compiled to branches inside the k loop, which made the wait-count pass give up on the ring:
+// vmcnt(0) at the top of every group)
+__device__ __forceinline__ void gemm1_b_addr(int kb, unsigned bc0, unsigned bx0, unsigned dx, unsigned &b0, unsigned &bs) {
+    const unsigned mc = (unsigned)((kb - KS_C) >> 31);  // all ones for the conditioner k-steps
+    const unsigned kt = (unsigned)(kb - KS_C) & 63u, tap = kt >> 4, c0 = (kt & 15u) * 32u;
+    b0 = (mc & (bc0 + (unsigned)kb * 32u)) | (~mc & (bx0 + tap * dx + c0));
+    bs = (mc & (32u * CR)) | (~mc & (32u * XR));
 }
+
 // pin a computed value where it is written in the source: an empty volatile asm that "modifies" the register.  Without it LLVM sinks a
 // pure computation to its first use -- e.g. the gate of pass 0, used only after the barrier behind pass 1, moved below pass 1 and kept
 // the 64 accumulators of pass 0 alive through it (92 spilled registers), and the packing of the next x tile moved behind its barrier
@@ -543,12 +572,10 @@ __device__ __forceinline__ void pin(unsigned &v) { asm volatile("" : "+v"(v)); }
 // LDS-only barrier: the waves exchange nothing but LDS tiles, and the A-fragment loads in flight must stay in flight
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <bool SKEW, int PF1>
 __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersArgs la) {
     const SetDiffnetLayersBf16Args &a = la.a;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    constexpr int NT = 64, NCB = 2, NTH = 512, NCG = NTH / NT, CPX = FC / NCG, CPC = FH / NCG;
-    constexpr int PF2 = 4;
+    constexpr int NT = 64, NCB = 2, NTH = 512;
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
@@ -568,7 +595,10 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
     const rsrc_t rsk = make_rsrc(a.skip + (int64_t)b * FC * T), rcd = make_rsrc(a.cond + (int64_t)b * FH * T);
     const unsigned lane16 = 16u * (unsigned)lane;
     const int row_g = 32 * w;                  // the wave's gate / residual rows [row_g, row_g + 32); filter / skip rows + 256
+    // A fragments: k-step ks, row block rb (0 gate / residual, 1 filter / skip rows) of the wave's part of w1b / w2b
     const unsigned ab1 = (unsigned)(w * KS1 * 2 * 1024), ab2 = (unsigned)(w * KS2 * 2 * 1024);
+    auto aoff1 = [=](int ks, int rb) { return ab1 + (unsigned)((2 * ks + rb) * 1024); };
+    auto aoff2 = [=](int ks, int rb) { return ab2 + (unsigned)((2 * ks + rb) * 1024); };
 
     // ---- stage: step offsets and biases of every fused layer, x + d_0 (halo d of layer 0), the conditioner tile
     {
@@ -581,57 +611,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
             bsh[m * 1024 + r] = a.b_dil[i] + a.b_cond[i];
             bsh[m * 1024 + 512 + r] = a.b_out[i];
         }
-        const int d = 1 << (a.l0 % a.dilation_cycle_length);
-        const int f = tid % NT, cg = __builtin_amdgcn_readfirstlane(tid / NT);  // cg 0 .. 7
-        const int t = ts - d + f;
-        const bool tvx = t >= 0 && t < T;
-        const unsigned vox = 4u * (unsigned)min(max(t, 0), T - 1);
-        const int tcn = ts + f;
-        const bool tvc = tcn >= 0 && tcn < T;
-        const unsigned voc = 4u * (unsigned)min(max(tcn, 0), T - 1);
-        float vx[CPX], vc[CPC];
-#pragma unroll
-        for (int k = 0; k < CPX; ++k) vx[k] = buf_load(rx, vox, (unsigned)(CPX * cg + k) * T4);
-#pragma unroll
-        for (int k = 0; k < CPC; ++k) vc[k] = buf_load(rcd, voc, (unsigned)(CPC * cg + k) * T4);
-        // rows beyond layer 0's tile (layers with a larger dilation address up to XROWS_MAX rows): finite filler
-        for (int i = tid; i < (XROWS_MAX - (NT + 2 * d)) * (XR / 16); i += NTH)
-            *reinterpret_cast<u32x4_t *>(xs + (NT + 2 * d) * XR + i * 16) = (u32x4_t){0u, 0u, 0u, 0u};
-        __syncthreads();  // dsh
-#pragma unroll
-        for (int q = 0; q < CPX / 8; ++q) {
-            const f32x4 d0 = *reinterpret_cast<const f32x4 *>(dsh + CPX * cg + 8 * q);
-            const f32x4 d1 = *reinterpret_cast<const f32x4 *>(dsh + CPX * cg + 8 * q + 4);
-            u32x4_t u;
-            u[0] = tvx ? pack2(vx[8 * q + 0] + d0[0], vx[8 * q + 1] + d0[1]) : 0u;
-            u[1] = tvx ? pack2(vx[8 * q + 2] + d0[2], vx[8 * q + 3] + d0[3]) : 0u;
-            u[2] = tvx ? pack2(vx[8 * q + 4] + d1[0], vx[8 * q + 5] + d1[1]) : 0u;
-            u[3] = tvx ? pack2(vx[8 * q + 6] + d1[2], vx[8 * q + 7] + d1[3]) : 0u;
-            *reinterpret_cast<u32x4_t *>(xs + f * XR + (CPX * cg + 8 * q) * 2) = u;
-        }
-#pragma unroll
-        for (int q = 0; q < CPC / 8; ++q) {
-            u32x4_t u;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u[e] = tvc ? pack2(vc[8 * q + 2 * e], vc[8 * q + 2 * e + 1]) : 0u;
-            *reinterpret_cast<u32x4_t *>(cs + f * CR + (CPC * cg + 8 * q) * 2) = u;
-        }
-        if (f < 2 * d) {
-            const int j = NT + f, th = ts - d + j;
-            const bool tvh = th >= 0 && th < T;
-            const unsigned voh = 4u * (unsigned)min(max(th, 0), T - 1);
-            float vh[CPX];
-#pragma unroll
-            for (int k = 0; k < CPX; ++k) vh[k] = buf_load(rx, voh, (unsigned)(CPX * cg + k) * T4);
-#pragma unroll
-            for (int q = 0; q < CPX / 8; ++q) {
-                u32x4_t u;
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    u[e] = tvh ? pack2(vh[8 * q + 2 * e] + dsh[CPX * cg + 8 * q + 2 * e], vh[8 * q + 2 * e + 1] + dsh[CPX * cg + 8 * q + 2 * e + 1]) : 0u;
-                *reinterpret_cast<u32x4_t *>(xs + j * XR + (CPX * cg + 8 * q) * 2) = u;
-            }
-        }
+        stage_tiles<NT>(xs, cs, dsh, rx, rcd, ts, 1 << (a.l0 % a.dilation_cycle_length), T, XROWS_MAX);
     }
     // per column block: frame of this lane, whether it lies inside the utterance, whether it is stored
     // (mT: all-ones / zero word ANDed onto the packed bf16 pairs -- a `frame inside T ? f(y) : 0` select compiled to one exec-mask
@@ -666,13 +646,8 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
     // probe builds: the phases of the layers m >= 1, waves 0 and 4 of block (1, 1) (layout: at SET_PHASE_PROBE_BUFFER above)
     const bool probe = g_bf16_phase_buf && blockIdx.x == 1 && blockIdx.y == 1;
     PhaseProbe<8> pp;
-    // SKEW: a static priority instead of the per-k-step toggles -- waves 0-3 win every arbitration against their SIMD partners 4-7
-    if (SKEW && w < 4) __builtin_amdgcn_s_setprio(1);
-    u32x4_t A1[PF1][2], A2[PF2][2];
-    {
-        const rsrc_t rw1 = make_rsrc(reinterpret_cast<const unsigned short *>(a.img));
-        gemm_reg_prefetch<PF1>(A1, rw1, lane16, ab1);
-    }
+    u32x4_t A1[4][2], A2[4][2];
+    gemm_grp_prefetch<2>(A1, make_rsrc(reinterpret_cast<const unsigned short *>(a.img)), lane16, aoff1);
     for (int m = 0; m < a.nl; ++m) {
         pp.start(probe && m >= 1, w & 4);  // waves 0 and 4 sample
         const int l = a.l0 + m, d = 1 << (l % a.dilation_cycle_length);
@@ -698,17 +673,10 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
         // ---- GEMM 1: y = [Wcond | Wdil tap 0 | tap 1 | tap 2] x [cond ; x + d shifted]
         {
             const unsigned dx = (unsigned)(d * XR);
-            auto bf1 = [&](int kb, unsigned &b0, unsigned &b1) {
-                // branch-free (a select on the uniform kb compiled to branches inside the k loop, which made the wait-count
-                // pass give up on the ring: vmcnt(0) at the top of every group)
-                const unsigned mc = (unsigned)((kb - KS_C) >> 31);  // all ones for the conditioner k-steps
-                const unsigned kt = (unsigned)(kb - KS_C) & 63u, tap = kt >> 4, c0 = (kt & 15u) * 32u;
-                b0 = (mc & (bc0 + (unsigned)kb * 32u)) | (~mc & (bx0 + tap * dx + c0));
-                b1 = b0 + ((mc & (32u * CR)) | (~mc & (32u * XR)));
-            };
-            gemm_reg_run<KS1, PF1 / 4, !SKEW>(acc, A1, rw1, lane16, ab1, lds, bf1);
+            auto bf1 = [&](int kb, unsigned &b0, unsigned &bs) { gemm1_b_addr(kb, bc0, bx0, dx, b0, bs); };
+            gemm_grp_run<2, NCB, KS1, true>(acc, A1, rw1, lane16, aoff1, lds, bf1);
         }
-        gemm_reg_prefetch<PF2>(A2, rw2, lane16, ab2);  // GEMM 2's first fragments travel under the gate
+        gemm_grp_prefetch<2>(A2, rw2, lane16, aoff2);  // GEMM 2's first fragments travel under the gate
         pp.lap(1);
 
         // ---- gate -> z tile (own LDS tile: no wave has to wait for the others to leave GEMM 1)
@@ -739,10 +707,10 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
 
         // ---- GEMM 2: o = Wout z  (z tile row j <-> frame ts + j)
         {
-            auto bf2 = [&](int kb, unsigned &b0, unsigned &b1) { b0 = bz0 + (unsigned)kb * 32u; b1 = b0 + 32u * XR; };
-            gemm_reg_run<KS2, PF2 / 4, !SKEW>(acc, A2, rw2, lane16, ab2, lds, bf2);
+            auto bf2 = [&](int kb, unsigned &b0, unsigned &bs) { b0 = bz0 + (unsigned)kb * 32u; bs = 32u * XR; };
+            gemm_grp_run<2, NCB, KS2, true>(acc, A2, rw2, lane16, aoff2, lds, bf2);
         }
-        if (!last) gemm_reg_prefetch<PF1>(A1, make_rsrc(img + N_IMG), lane16, ab1);  // the next layer's first fragments
+        if (!last) gemm_grp_prefetch<2>(A1, make_rsrc(img + N_IMG), lane16, aoff1);  // the next layer's first fragments
         pp.lap(3);
 
         // ---- epilogue: x' = (x + o_res) / sqrt 2 and the skip sum stay in registers; bf16(x' + d_next) -> the x tile
@@ -810,82 +778,11 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_reg_bf16_kernel(LayersA
 // Arithmetic per frame as diffnet_layer_fwd_bf16_kernel (same images, k order, accumulator start, rounding points, skip = old + (bias +
 // products)): x and the skip sum are bit-identical.
 // =====================================================================================================================
-// acc[NRB][4] += A B over NKS k-steps in groups of 4 with the pinned schedule of gemm_reg_run; ring A[4 D][NRB].
-// aoff(ks, rb): wave-uniform byte offset of the fragment block; avo: per-lane byte offset inside it.
-// (What each operand stream of the layer costs -- weight refills, B-fragment reads, skip traffic -- was measured with builds that drop it,
-// results wrong by construction: profiles/r04_t128_exp.log.)
-template <int NRB, int NKS, int D, bool TOGGLE, bool BDB, typename AO, typename BG>
-__device__ __forceinline__ void gemm_t128_run(f32x16 (&acc)[NRB][4], u32x4_t (&A)[4 * D][NRB], rsrc_t img, unsigned avo, AO aoff,
-                                              const unsigned char *lds, BG bgrp) {
-    // BDB: the B fragments of k-step k + 1 are read under the MFMAs of k-step k (16 more registers); else each k-step reads its own
-    constexpr int NG = NKS / 4;
-    static_assert(NKS % 4 == 0 && NG >= 2 * D && (D == 1 || D == 2), "gemm_t128_run");
-    u32x4_t Bq[BDB ? 2 : 1][4];
-    if (BDB) {
-        unsigned b0, bs;
-        bgrp(0, b0, bs);
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) Bq[0][cb] = *reinterpret_cast<const u32x4_t *>(lds + b0 + cb * bs);
-    }
-    auto group = [&](int kb, int slot, bool refill, bool more) {
-        unsigned b0, bs, n0 = 0, ns = 0;
-        bgrp(kb, b0, bs);
-        if (BDB && more) bgrp(kb + 4, n0, ns);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-            if (!BDB) {
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) Bq[0][cb] = *reinterpret_cast<const u32x4_t *>(lds + b0 + cb * bs + 32 * p);
-            } else if (p < 3) {
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) Bq[(p + 1) & 1][cb] = *reinterpret_cast<const u32x4_t *>(lds + b0 + cb * bs + 32 * (p + 1));
-            } else if (more) {
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) Bq[0][cb] = *reinterpret_cast<const u32x4_t *>(lds + n0 + cb * ns);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (TOGGLE) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int rb = 0; rb < NRB; ++rb)
-#pragma unroll
-                for (int cb = 0; cb < 4; ++cb) acc[rb][cb] = mma16(A[4 * slot + p][rb], Bq[BDB ? (p & 1) : 0][cb], acc[rb][cb]);
-            if (TOGGLE) __builtin_amdgcn_s_setprio(0);
-            if (refill) {
-#pragma unroll
-                for (int rb = 0; rb < NRB; ++rb) A[4 * slot + p][rb] = buf_load_u4(img, avo, aoff(kb + p + 4 * D, rb));
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    };
-    if constexpr (D == 1) {
-#pragma unroll 1
-        for (int g = 0; g < NG - 1; ++g) group(4 * g, 0, true, true);
-        group(4 * (NG - 1), 0, false, false);
-    } else {
-        constexpr int NR = NG - 2, NP = NR / 2;
-#pragma unroll 1
-        for (int g = 0; g < 2 * NP; g += 2) { group(4 * g, 0, true, true); group(4 * g + 4, 1, true, true); }
-        if constexpr (NR % 2) {
-            group(4 * (NG - 3), 0, true, true); group(4 * (NG - 2), 1, false, true); group(4 * (NG - 1), 0, false, false);
-        } else {
-            group(4 * (NG - 2), 0, false, true); group(4 * (NG - 1), 1, false, false);
-        }
-    }
-}
-template <int NRB, int PFD, typename AO>
-__device__ __forceinline__ void gemm_t128_prefetch(u32x4_t (&A)[PFD][NRB], rsrc_t img, unsigned avo, AO aoff) {
-#pragma unroll
-    for (int p = 0; p < PFD; ++p)
-#pragma unroll
-        for (int rb = 0; rb < NRB; ++rb) A[p][rb] = buf_load_u4(img, avo, aoff(p, rb));
-}
-
-template <bool SKEW, int NSKR>
 __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(LayersArgs la) {
     const SetDiffnetLayersBf16Args &a = la.a;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-    constexpr int NT = 128, NCB = 4, NTH = 512, NCG = NTH / NT, CPX = FC / NCG, CPC = FH / NCG;
-    constexpr int D1 = 1, D2 = 1;  // A ring depth in groups of 4 k-steps: GEMM 1 passes 4 k-steps x 1 fragment, GEMM 2 4 k-steps x 2
+    constexpr int NT = 128, NCB = 4, NTH = 512;
+    constexpr int NSKR = 1;  // column blocks whose old skip rows stay in registers for the whole group (measured 0 .. 4: at the launch)
     constexpr bool BDB1 = false, BDB2 = false;  // B fragments single-buffered (the SIMD partner covers the LDS latency; the registers go to the ring / the old skip rows)
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -923,56 +820,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
         }
         bsh[tid] = a.b_dil[tid] + a.b_cond[tid];
         bsh[512 + tid] = a.b_out[tid];
-        const int d = 1 << (a.l0 % a.dilation_cycle_length);
-        const int f = tid % NT, cg = __builtin_amdgcn_readfirstlane(tid / NT);  // cg 0 .. 3
-        const int t = ts - d + f;
-        const bool tvx = t >= 0 && t < T;
-        const unsigned vox = 4u * (unsigned)min(max(t, 0), T - 1);
-        const int tcn = ts + f;
-        const bool tvc = tcn >= 0 && tcn < T;
-        const unsigned voc = 4u * (unsigned)min(max(tcn, 0), T - 1);
-        float vx[CPX], vc[CPC];
-#pragma unroll
-        for (int k = 0; k < CPX; ++k) vx[k] = buf_load(rx, vox, (unsigned)(CPX * cg + k) * T4);
-#pragma unroll
-        for (int k = 0; k < CPC; ++k) vc[k] = buf_load(rcd, voc, (unsigned)(CPC * cg + k) * T4);
-        for (int i = tid; i < (XROWS_MAX - (NT + 2 * d)) * (XR / 16); i += NTH)
-            *reinterpret_cast<u32x4_t *>(xs + (NT + 2 * d) * XR + i * 16) = (u32x4_t){0u, 0u, 0u, 0u};
-        __syncthreads();  // dsh
-#pragma unroll
-        for (int q = 0; q < CPX / 8; ++q) {
-            const f32x4 d0 = *reinterpret_cast<const f32x4 *>(dsh + CPX * cg + 8 * q);
-            const f32x4 d1 = *reinterpret_cast<const f32x4 *>(dsh + CPX * cg + 8 * q + 4);
-            u32x4_t u;
-            u[0] = tvx ? pack2(vx[8 * q + 0] + d0[0], vx[8 * q + 1] + d0[1]) : 0u;
-            u[1] = tvx ? pack2(vx[8 * q + 2] + d0[2], vx[8 * q + 3] + d0[3]) : 0u;
-            u[2] = tvx ? pack2(vx[8 * q + 4] + d1[0], vx[8 * q + 5] + d1[1]) : 0u;
-            u[3] = tvx ? pack2(vx[8 * q + 6] + d1[2], vx[8 * q + 7] + d1[3]) : 0u;
-            *reinterpret_cast<u32x4_t *>(xs + f * XR + (CPX * cg + 8 * q) * 2) = u;
-        }
-#pragma unroll
-        for (int q = 0; q < CPC / 8; ++q) {
-            u32x4_t u;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u[e] = tvc ? pack2(vc[8 * q + 2 * e], vc[8 * q + 2 * e + 1]) : 0u;
-            *reinterpret_cast<u32x4_t *>(cs + f * CR + (CPC * cg + 8 * q) * 2) = u;
-        }
-        if (f < 2 * d) {
-            const int j = NT + f, th = ts - d + j;
-            const bool tvh = th >= 0 && th < T;
-            const unsigned voh = 4u * (unsigned)min(max(th, 0), T - 1);
-            float vh[CPX];
-#pragma unroll
-            for (int k = 0; k < CPX; ++k) vh[k] = buf_load(rx, voh, (unsigned)(CPX * cg + k) * T4);
-#pragma unroll
-            for (int q = 0; q < CPX / 8; ++q) {
-                u32x4_t u;
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    u[e] = tvh ? pack2(vh[8 * q + 2 * e] + dsh[CPX * cg + 8 * q + 2 * e], vh[8 * q + 2 * e + 1] + dsh[CPX * cg + 8 * q + 2 * e + 1]) : 0u;
-                *reinterpret_cast<u32x4_t *>(xs + j * XR + (CPX * cg + 8 * q) * 2) = u;
-            }
-        }
+        stage_tiles<NT>(xs, cs, dsh, rx, rcd, ts, 1 << (a.l0 % a.dilation_cycle_length), T, XROWS_MAX);
     }
     // per column block: frame of this lane; mT: all-ones inside the utterance (ANDed onto packed bf16 pairs); st: stored by this block
     bool st[NCB];
@@ -996,11 +844,10 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
 
     const bool probe = g_bf16_phase_buf && blockIdx.x == 1 && blockIdx.y == 1;
     PhaseProbe<8> pp;
-    if (SKEW && w < 4) __builtin_amdgcn_s_setprio(1);
     // old skip rows per column block: blocks < NSKR live in registers for the whole group, the others travel through the private copy per layer
     f32x16 sko[NCB];
-    u32x4_t A1[4 * D1][1], A2[4 * D2][1];
-    gemm_t128_prefetch<1, 4 * D1>(A1, make_rsrc(reinterpret_cast<const unsigned short *>(a.img)), avo1, aoff1h(0));
+    u32x4_t A1[4][1], A2[4][1];  // A rings: one group of 4 k-steps x 1 fragment block per pass
+    gemm_grp_prefetch<1>(A1, make_rsrc(reinterpret_cast<const unsigned short *>(a.img)), avo1, aoff1h(0));
     for (int m = 0; m < a.nl; ++m) {
         pp.start(probe && m >= 1, w & 4);  // waves 0 and 4 sample
         const int l = a.l0 + m, d = 1 << (l % a.dilation_cycle_length);
@@ -1012,12 +859,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
         float nb1 = 0.0f, nb2 = 0.0f;
         if (!last) { nb1 = a.b_dil[(m + 1) * 512 + tid] + a.b_cond[(m + 1) * 512 + tid]; nb2 = a.b_out[(m + 1) * 512 + tid]; }
         const unsigned dx = (unsigned)(d * XR);
-        auto bf1 = [&](int kb, unsigned &b0, unsigned &bs) {
-            const unsigned mc = (unsigned)((kb - KS_C) >> 31);  // all ones for the conditioner k-steps
-            const unsigned kt = (unsigned)(kb - KS_C) & 63u, tap = kt >> 4, c0 = (kt & 15u) * 32u;
-            b0 = (mc & (bc0 + (unsigned)kb * 32u)) | (~mc & (bx0 + tap * dx + c0));
-            bs = (mc & (32u * CR)) | (~mc & (32u * XR));
-        };
+        auto bf1 = [&](int kb, unsigned &b0, unsigned &bs) { gemm1_b_addr(kb, bc0, bx0, dx, b0, bs); };
         unsigned zp[2][NCB][2][2];  // packed gated z of both passes: [h][cb][g2][2 words = 4 channels]
         lds_barrier();  // B1: the x tile of this layer (staged above / written by the previous layer's epilogue) is complete
         pp.lap(0);
@@ -1033,8 +875,8 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
 #pragma unroll
                     for (int cb = 0; cb < NCB; ++cb) acc[0][cb][4 * g4 + e] = bv[e];
             }
-            gemm_t128_run<1, KS1, D1, !SKEW, BDB1>(acc, A1, rw1, avo1, aoff1h(h), lds, bf1);
-            if (h == 0) gemm_t128_prefetch<1, 4 * D1>(A1, rw1, avo1, aoff1h(1));  // pass 1's first fragments travel under the gate of pass 0
+            gemm_grp_run<1, NCB, KS1, BDB1>(acc, A1, rw1, avo1, aoff1h(h), lds, bf1);
+            if (h == 0) gemm_grp_prefetch<1>(A1, rw1, avo1, aoff1h(1));  // pass 1's first fragments travel under the gate of pass 0
             // ---- gate of the pass (lane-local: gate row in register r < 8, its filter row in register r + 8), packed, kept in registers
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb)
@@ -1053,7 +895,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
         // GEMM 2 runs in two passes as well: skip rows first, residual rows second.  The old skip rows (from the skip tensor for the first
         // layer of the group unless it is the first of the network, from the private copy afterwards) and the first weight fragments are
         // requested here: they travel while this wave waits for the others and through the skip pass
-        gemm_t128_prefetch<1, 4 * D2>(A2, rw2, lane16, aoff2r(1));
+        gemm_grp_prefetch<1>(A2, rw2, lane16, aoff2r(1));
         const bool sk_zero = a.first != 0 && m == 0;
         if (m == 0) {
 #pragma unroll
@@ -1103,8 +945,8 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
 #pragma unroll
                     for (int cb = 0; cb < NCB; ++cb) acc[0][cb][4 * g4 + e] = bv[e];
             }
-            gemm_t128_run<1, KS2, D2, !SKEW, BDB2>(acc, A2, rw2, lane16, aoff2r(1), lds, bf2);
-            gemm_t128_prefetch<1, 4 * D2>(A2, rw2, lane16, aoff2r(0));
+            gemm_grp_run<1, NCB, KS2, BDB2>(acc, A2, rw2, lane16, aoff2r(1), lds, bf2);
+            gemm_grp_prefetch<1>(A2, rw2, lane16, aoff2r(0));
             if (!last) {
 #pragma unroll
                 for (int cb = 0; cb < NSKR; ++cb)
@@ -1142,7 +984,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
 #pragma unroll
                 for (int cb = 0; cb < NCB; ++cb) accx[0][cb][4 * g4 + e] += bv[e];
         }
-        gemm_t128_run<1, KS2, D2, !SKEW, BDB2>(accx, A2, rw2, lane16, aoff2r(0), lds, bf2);
+        gemm_grp_run<1, NCB, KS2, BDB2>(accx, A2, rw2, lane16, aoff2r(0), lds, bf2);
         pp.lap(3);
 
         // ---- epilogue: x' = (x + o_res) / sqrt 2 stays in accx; the next layer's first weight fragments; bf16(x' + d_next) packed in
@@ -1152,7 +994,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_layers_t128_bf16_kernel(Layers
 #pragma unroll
             for (int r = 0; r < 16; ++r) accx[0][cb][r] *= RSQRT2;
         if (!last) {
-            gemm_t128_prefetch<1, 4 * D1>(A1, make_rsrc(img + N_IMG), avo1, aoff1h(0));  // the next layer's first fragments
+            gemm_grp_prefetch<1>(A1, make_rsrc(img + N_IMG), avo1, aoff1h(0));  // the next layer's first fragments
             const int dn = 1 << ((l + 1) % a.dilation_cycle_length);
             const float *dnx = dsh + (m + 1) * FC;
             unsigned xp[NCB][4][2];
@@ -1201,12 +1043,12 @@ __device__ __forceinline__ float half_sum(float v) {  // sum over the 32 lanes o
     return v;
 }
 
-// NT = frames per tile: 128 is what ships (one block per CU, 133 KB of LDS).  Measured in round 5 and not instantiated (profiles/r05_layer_bwd_probe.log):
-// NT = 64 as two blocks per CU (68 KB of LDS each, 120 registers, no spills) runs the same 86 - 88 us per launch -- the kernel is not
-// waiting for its own phases; builds without its 2-byte memory instructions (the bf16 d_o / dy stores, the y loads: 384 per lane) run 65 us,
-// and even that moves the training step by 0.15 ms only.
-template <int NT>
-__global__ void __launch_bounds__(512, NT == 128 ? 1 : 2) diffnet_layer_bwd_bf16_kernel(SetDiffnetLayerBf16BwdArgs a) {
+// Tile = FNT = 128 frames (one block per CU, 133 KB of LDS).  Measured in round 5 and gone with the tile-width parameter
+// (profiles/r05_layer_bwd_probe.log): 64 frames as two blocks per CU (68 KB of LDS each, 120 registers, no spills) ran the same 86 - 88 us per
+// launch -- the kernel is not waiting for its own phases; builds without its 2-byte memory instructions (the bf16 d_o / dy stores, the y loads:
+// 384 per lane) ran 65 us, and even that moved the training step by 0.15 ms only.
+__global__ void __launch_bounds__(512, 1) diffnet_layer_bwd_bf16_kernel(SetDiffnetLayerBf16BwdArgs a) {
+    constexpr int NT = FNT;
     constexpr int NCB = NT / 32;       // 32-frame column blocks
     constexpr int NCG = 512 / NT;      // channel groups of the staging pass (thread = frame x channel group)
     constexpr int CPG = 2 * FC / NCG;  // channels of d_o per staging thread
@@ -1231,6 +1073,7 @@ __global__ void __launch_bounds__(512, NT == 128 ? 1 : 2) diffnet_layer_bwd_bf16
     const rsrc_t rwt1 = make_rsrc(img + OFF_WT1 + (int64_t)w * 96 * 512);
     const rsrc_t rwtc = make_rsrc(img + OFF_WTC + (int64_t)min(w, 5) * 32 * 512);
     const unsigned lane16 = 16u * (unsigned)lane;
+    const auto aoff_ks = [](int ks, int) { return (unsigned)(ks * 1024); };  // the wave's images hold one fragment block per k-step
 
     // ---- stage d_o = [dx_out / sqrt2 ; dskip] as [frame][512] bf16 (+ its bf16 copy in HBM for the weight gradient)
     {
@@ -1275,7 +1118,7 @@ __global__ void __launch_bounds__(512, NT == 128 ? 1 : 2) diffnet_layer_bwd_bf16
     f32x16 dz[1][NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) dz[0][cb] = (f32x16){0};
-    gemm_bf16<1, NCB>(dz, rwt2, lane16, 0, 32, lds, [&](int ks, int cb) {
+    gemm_bf16<1, NCB>(dz, rwt2, lane16, 32, lds, aoff_ks, [&](int ks, int cb) {
         return (unsigned)((cb * 32 + l31 + d) * DR + (ks * 16 + half * 8) * 2);
     });
 
@@ -1353,12 +1196,12 @@ __global__ void __launch_bounds__(512, NT == 128 ? 1 : 2) diffnet_layer_bwd_bf16
     f32x16 dxd[1][NCB], dcn[1][NCB];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) { dxd[0][cb] = (f32x16){0}; dcn[0][cb] = (f32x16){0}; }
-    gemm_bf16<1, NCB>(dxd, rwt1, lane16, 0, 96, lds, [&](int ks, int cb) {
+    gemm_bf16<1, NCB>(dxd, rwt1, lane16, 96, lds, aoff_ks, [&](int ks, int cb) {
         const int tap = ks >> 5, c0 = (ks & 31) * 16;
         return (unsigned)((cb * 32 + l31 + (2 - tap) * d) * DR + (c0 + half * 8) * 2);
     });
     if (w < 6)
-        gemm_bf16<1, NCB>(dcn, rwtc, lane16, 0, 32, lds, [&](int ks, int cb) {
+        gemm_bf16<1, NCB>(dcn, rwtc, lane16, 32, lds, aoff_ks, [&](int ks, int cb) {
             return (unsigned)((cb * 32 + l31 + d) * DR + (ks * 16 + half * 8) * 2);
         });
 
@@ -1489,18 +1332,16 @@ extern "C" int set_diffnet_layer_fwd_bf16(const SetDiffnetLayerBf16Args *args, v
                     ((a.y16 != nullptr) == (a.z16 != nullptr)), "set_diffnet_layer_fwd_bf16");
     SET_REQUIRE(a.B > 0 && a.T > 0 && a.dil >= 1 && a.dil <= 8, "set_diffnet_layer_fwd_bf16");
     SET_REQUIRE((int64_t)2 * FC * a.T * 4 < ((int64_t)1 << 31), "set_diffnet_layer_fwd_bf16 (T too large)");
-    // tile: 128 frames, 8 waves, one block per CU (round 3's 64-frame / two-blocks-per-CU experiment spilled registers, measured
-    // slower, and is gone)
-    constexpr int tile = 128;
+    constexpr int tile = FNT;
     static SetDeviceOnce lds_once;
-    if (int rc = set_lds_optin(lds_once, 160 * 1024, "layer fwd bf16 attr", diffnet_layer_fwd_bf16_kernel<true, 128>,
-                               diffnet_layer_fwd_bf16_kernel<false, 128>))
+    if (int rc = set_lds_optin(lds_once, 160 * 1024, "layer fwd bf16 attr", diffnet_layer_fwd_bf16_kernel<true>,
+                               diffnet_layer_fwd_bf16_kernel<false>))
         return rc;
     const size_t ldsz = (size_t)(tile + 2 * a.dil) * XR + (size_t)tile * CR + 5 * FC * sizeof(float);  // tiles, step offsets, the two bias vectors
     dim3 grid((a.T + tile - 1) / tile, a.B);
     hipStream_t st = (hipStream_t)stream;
-    if (a.y16) hipLaunchKernelGGL((diffnet_layer_fwd_bf16_kernel<true, 128>), grid, dim3(512), ldsz, st, a);
-    else hipLaunchKernelGGL((diffnet_layer_fwd_bf16_kernel<false, 128>), grid, dim3(512), ldsz, st, a);
+    if (a.y16) hipLaunchKernelGGL(diffnet_layer_fwd_bf16_kernel<true>, grid, dim3(512), ldsz, st, a);
+    else hipLaunchKernelGGL(diffnet_layer_fwd_bf16_kernel<false>, grid, dim3(512), ldsz, st, a);
     return set_check_launch("set_diffnet_layer_fwd_bf16");
 }
 
@@ -1580,16 +1421,15 @@ extern "C" int set_diffnet_layers_fwd_bf16(const SetDiffnetLayersBf16Args *args,
                                    : (size_t)(128 + 2 * dmax) * XR + (size_t)128 * CR + (size_t)a.nl * FC * sizeof(float) + 2 * 1024 * sizeof(float);
     if (ldsz > 160 * 1024) return set_fail(SET_E_UNSUPPORTED, "set_diffnet_layers_fwd_bf16", "tiles do not fit LDS");
     static SetDeviceOnce lds_once;
-    if (int rc = set_lds_optin(lds_once, 160 * 1024, "layers bf16 attr", diffnet_layers_reg_bf16_kernel<false, 4>,
-                               diffnet_layers_t128_bf16_kernel<false, 1>))
+    if (int rc = set_lds_optin(lds_once, 160 * 1024, "layers bf16 attr", diffnet_layers_reg_bf16_kernel, diffnet_layers_t128_bf16_kernel))
         return rc;
     dim3 grid((a.T + la.nv - 1) / la.nv, a.B);
-    // Shipped instantiations only.  Measured in round 4 and left out (B = 32, T = 800, sustained us per layer; profiles/r04_bf16_ab.log):
+    // One form of each kernel.  Measured in round 4, left out and since removed from the source (B = 32, T = 800, sustained us per layer; profiles/r04_bf16_ab.log):
     // 128-frame shape with 0 / 1 / 2 / 3 / 4 column blocks of the skip rows in registers 40.7 / 39.4 / 39.6 / 39.8 / 41.8 (21 / 45 / 67
     // spilled registers from 2 on); 64-frame shape with a static priority for one half of the waves instead of the k-step toggles and / or
     // a ring of 8 k-steps: within 0.5 % of the shipped one.
-    if (tile == 128) hipLaunchKernelGGL((diffnet_layers_t128_bf16_kernel<false, 1>), grid, dim3(512), ldsz, (hipStream_t)stream, la);
-    else hipLaunchKernelGGL((diffnet_layers_reg_bf16_kernel<false, 4>), grid, dim3(512), ldsz, (hipStream_t)stream, la);
+    if (tile == 128) hipLaunchKernelGGL(diffnet_layers_t128_bf16_kernel, grid, dim3(512), ldsz, (hipStream_t)stream, la);
+    else hipLaunchKernelGGL(diffnet_layers_reg_bf16_kernel, grid, dim3(512), ldsz, (hipStream_t)stream, la);
     return set_check_launch("set_diffnet_layers_fwd_bf16");
 }
 
@@ -1612,9 +1452,9 @@ extern "C" int set_diffnet_layer_bwd_bf16(const SetDiffnetLayerBf16BwdArgs *args
     SET_REQUIRE(nt - 2 * a.dil >= 32, "set_diffnet_layer_bwd_bf16 (dilation too large for the tile)");
     const size_t ldsz = (size_t)(nt + 2 * a.dil) * DR;
     static SetDeviceOnce lds_once;
-    if (int rc = set_lds_optin(lds_once, 160 * 1024, "layer bwd bf16 attr", diffnet_layer_bwd_bf16_kernel<128>)) return rc;
+    if (int rc = set_lds_optin(lds_once, 160 * 1024, "layer bwd bf16 attr", diffnet_layer_bwd_bf16_kernel)) return rc;
     dim3 grid(set_diffnet_layer_bwd_bf16_tiles(a.T, a.dil), a.B);
-    hipLaunchKernelGGL(diffnet_layer_bwd_bf16_kernel<128>, grid, dim3(512), ldsz, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(diffnet_layer_bwd_bf16_kernel, grid, dim3(512), ldsz, (hipStream_t)stream, a);
     return set_check_launch("set_diffnet_layer_bwd_bf16");
 }
 
