@@ -1389,11 +1389,14 @@ static int layers_balanced_nv(int T, int tile, int hh) { const int nv = tile - 2
 
 extern "C" int64_t set_diffnet_layers_bf16_scratch_floats(int32_t B, int32_t T, int32_t l0, int32_t nl, int32_t dcl) {
     // 128-frame tiles: a block's private copy of its skip rows (256 x 128 fp32) between the layers of a group; an upper bound over the
-    // first layers l0 of the groups of a network (so that one buffer serves every group); 64-frame tiles keep everything in registers
+    // first layers l0 of the groups of a network (so that one buffer serves every group); 64-frame tiles keep everything in registers.
+    // The bound runs over the first layers whose group the launch admits (128 - 2 H >= 32): with a dilation cycle of 4 a group of 14
+    // layers is admitted from l0 = 0 (H = 47, always on 128-frame tiles) and refused from l0 = 1 (H = 49); the refused ones used to
+    // shrink the answer to 64 floats, and the admitted launch then refused the buffer it had asked for.
     if (B < 1 || T < 1 || nl < 1 || dcl < 1 || l0 < 0) return 0;
-    int hmax = 0;
-    for (int s0 = 0; s0 < dcl; ++s0) { const int h = layers_halo(s0, nl, dcl); hmax = h > hmax ? h : hmax; }
-    if (128 - 2 * hmax < 32) return 64;
+    int hmax = -1;
+    for (int s0 = 0; s0 < dcl; ++s0) { const int h = layers_halo(s0, nl, dcl); if (128 - 2 * h >= 32 && h > hmax) hmax = h; }
+    if (hmax < 0) return 64;
     const int nv = layers_balanced_nv(T, 128, hmax);
     return (int64_t)B * ((T + nv - 1) / nv) * FC * 128;
 }
