@@ -890,6 +890,45 @@ int set_zero_fill_dist(const float *x, const float *y, const int64_t *len_x, con
 int set_mcd_finish(const float *num, const int32_t *steps, const int64_t *len_1, const int64_t *len_2, float *mcd, float *penalty,
                    int64_t *frames, int32_t B, int32_t T1, int32_t T2, void *stream);
 
+/* Short-time objective intelligibility (csrc/stoi.hip; eval/stoi.py `stoi(x, y, 22050, extended=False)` with eval/utils.py).  Four
+ * launches: x, y [B][in_bs >= N] fp32 -> d [B] fp32, valid [B] uint8.  Every `lengths` / `lens` is int64 [B] on the device or NULL (every
+ * row full) and is read clamped into [0, N]: no kernel leaves its buffers whatever the device holds.  No atomics anywhere: two runs agree bit
+ * for bit, and a row of a ragged batch equals the same pair run alone.  win [1024] fp32 is the SYMMETRIC Hann np.hanning(1026)[1:-1],
+ * float64 rounded once (not the periodic window of the log-mel).  Sizes follow from N alone: F_max = ceil((N - 1024) / 512) energy frames,
+ * rows of 512 (F_max + 1) compacted samples, T = 2 (F_max - 1) envelope frames.  N > 1024.
+ *
+ * set_stoi_select: a row of len samples has F = ceil((len - 1024) / 512) frames (0 when len <= 1024), frame f from sample 512 f.
+ *   e2[f] = sum_n fl(fl(w[n] x[512 f + n])^2) in fp32: lane l of a wave sums n = l, l + 64, ... ascending, then the butterfly 32, 16, .., 1;
+ *   nrm[b][f] = sqrtf(e2[f]) (nrm [B][F_max], written for f < F).  Frame f is kept iff nrm[f] + EPS > 0.01f (max_f nrm[f] + EPS) in fp32,
+ *   EPS = 2.220446e-16f: the reference's 20 log10(a + EPS) > 20 log10(m + EPS) - 40 in the linear domain (an all-zero row keeps every
+ *   frame, as the reference does).  kept [B][F_max] int32: kept[b][j] = the j-th kept frame, ascending, written for j < K[b]; K [B] int32.
+ *   One block per row, the scan in LDS.
+ * set_stoi_compact: the reference's `_overlap_and_add` of the kept windowed frames at hop 512, for x and for y with x's list.
+ *   sil [2 B][sil_bs >= 512 (F_max + 1)], row b = x's and row B + b = y's signal: for j = 0 .. K, r < 512
+ *     sil[512 j + r] = fl(fl(w[r] s[512 kept[j] + r]) + fl(w[r + 512] s[512 kept[j-1] + 512 + r])),
+ *   the first product +0.0 at j = K and the second at j = 0 (two separately rounded products, one rounded add: numpy float32 gives the
+ *   same bits).  Nothing at or beyond L = 512 (K + 1) is written.  sil_len [2 B] int64 = L of each row.  K and kept are read clamped.
+ * set_stoi_bands: sil [R][sil_bs >= N] with lens [R] -> tob [R][T][n_bands], T = ceil((N - 1024) / 256).  Row r has
+ *   T_r = ceil((len_r - 1024) / 256) frames (0 when len_r <= 1024; 2 (K - 1) for len = 512 (K + 1)), frame m from sample 256 m, no padding:
+ *     tob[m][i] = sqrtf(sum_bin basis[i][bin] (re^2 + im^2)),
+ *   the windowed DFT and the band sum both on v_mfma_f32_32x32x2_f32 by the kernel body of set_log_mel (csrc/dft_gemm.h), the spectrum kept
+ *   on chip; frames m >= T_r are written as +0.0.  table / basis are the images of set_log_mel (melspec.pack_dft_table over the window
+ *   above, melspec.pack_mel_basis of the 0/1 band matrix), 16-byte aligned.  n_fft = 1024, hop = 256, n_bands <= 32, else SET_E_UNSUPPORTED.
+ * set_stoi_score: tob [2 B][T][n_bands] (row b = x, row B + b = y) and lens [B] (compacted samples, as sil_len) -> d, valid.
+ *   T_b = ceil((len_b - 1024) / 256) clamped to T; J = T_b - 29 segments; T_b < 30: valid = 0, d = NaN.  Else, for every segment m and band i,
+ *   with the 30-vectors X = tob_x[m .. m+29][i], Y likewise: c = ||Y|| > 0 ? ||X|| / ||Y|| : 0; Y' = min(Y c, X (1 + 10^0.75)); both minus
+ *   their means; rho = <X, Y'> / (||X|| ||Y'||), 0 when a norm is 0; d = sum rho / (n_bands J), valid = 1.  Every segment is evaluated
+ *   directly, in double from the fp32 envelopes; a thread's sum and the block's tree depend on T_b only.  seg = 30, n_bands <= 32, else
+ *   SET_E_UNSUPPORTED.  T = 0 (tob may be NULL) marks every row invalid. */
+int set_stoi_select(const float *x, int64_t x_bs, const int64_t *lengths, const float *win, float *nrm, int32_t *kept, int32_t *K, int32_t B,
+                    int32_t N, int32_t n_frame, void *stream);
+int set_stoi_compact(const float *x, const float *y, int64_t in_bs, const float *win, const int32_t *kept, const int32_t *K, float *sil,
+                     int64_t sil_bs, int64_t *sil_len, int32_t B, int32_t N, int32_t n_frame, void *stream);
+int set_stoi_bands(const float *sil, int64_t sil_bs, const int64_t *lens, const float *table, const float *basis, float *tob, int32_t R,
+                   int32_t N, int32_t T, int32_t n_fft, int32_t hop, int32_t n_bands, int32_t bin_lo, int32_t nbins, void *stream);
+int set_stoi_score(const float *tob, const int64_t *lens, float *d, uint8_t *valid, int32_t B, int32_t T, int32_t n_bands, int32_t seg,
+                   void *stream);
+
 /* MFMA fragment-layout self test: runs a 32x32xK product through v_mfma_f32_32x32x2_f32 with the layout
  * this library assumes and returns the max abs error vs an in-kernel scalar reference via *max_err (HOST).
  * Synchronises.  Used by tests to pin the hardware layout assumption. */

@@ -100,10 +100,11 @@ def hann_padded(n_fft, win_length):
     return w
 
 
-def dft_table(n_fft, win_length, bin_lo, nbins):
+def dft_table(n_fft, win_length, bin_lo, nbins, window=None):
     """float32 [2, nbins, n_fft]: [0][f][n] = win[n] cos(2 pi (bin_lo + f) n / n_fft), [1][f][n] = -win[n] sin(...), each rounded once
-    from float64 (the angle is reduced exactly: (f n) mod n_fft in integers)."""
-    win = hann_padded(n_fft, win_length)
+    from float64 (the angle is reduced exactly: (f n) mod n_fft in integers).  win = hann_padded(n_fft, win_length), or `window`
+    (float64 [n_fft]) when one is given (metrics.stoi: the symmetric Hann)."""
+    win = hann_padded(n_fft, win_length) if window is None else np.asarray(window, dtype=np.float64).reshape(n_fft)
     f = np.arange(bin_lo, bin_lo + nbins, dtype=np.int64)[:, None]
     n = np.arange(n_fft, dtype=np.int64)[None, :]
     ang = 2.0 * np.pi * ((f * n) % n_fft).astype(np.float64) / n_fft

@@ -1,4 +1,7 @@
-"""Mel-cepstral distortion on the GPU (csrc/mcd.hip): mel -> MFCC -> exact DTW or zero fill -> (mcd, penalty, frames) per pair.
+"""Evaluation metrics on the GPU: mel-cepstral distortion (csrc/mcd.hip) and short-time objective intelligibility (csrc/stoi.hip; the
+second half of this file).
+
+Mel-cepstral distortion: mel -> MFCC -> exact DTW or zero fill -> (mcd, penalty, frames) per pair.
 
 After the reference's utils/eval/mcd.py `get_metrics_mels`, term by term:
 
@@ -136,3 +139,97 @@ def wav_mcd(wav_1, wav_2, hparams, len_1=None, len_2=None, **kw):
     mel_1, fr_1 = (fe(wav_1), None) if len_1 is None else fe(wav_1, len_1)
     mel_2, fr_2 = (fe(wav_2), None) if len_2 is None else fe(wav_2, len_2)
     return mel_mcd(mel_1, mel_2, fr_1, fr_2, **kw)
+
+
+# ---- short-time objective intelligibility (eval/stoi.py `stoi`, non-extended) --------------------------------------------------------------
+# Four launches (include/set_amd.h, the STOI block): frame energies and the list of frames within 40 dB of the loudest; the overlap-add of
+# the kept frames of both signals; third-octave band envelopes (the log-mel kernel's DFT GEMM with a power epilogue and a 0/1 band matrix);
+# the clipped, normalised correlation of every 30-frame segment.  FS = 22050 with no resampling; `extended=True` is not built (its
+# EPS * randn terms are not reproducible); utils/eval/stoi.py's NegSTOILoss is another quantity and is not built either.
+STOI_SR, STOI_NFFT, STOI_BANDS, STOI_MIN_FREQ = 22050, 1024, 15, 150
+_STOI_IMAGES = {}  # sr -> ops.CacheSlot of (window, packed DFT table, packed band matrix, nbins) on the device they were last used on
+
+
+def third_octave_bands(sr=STOI_SR, n_fft=STOI_NFFT, num_bands=STOI_BANDS, min_freq=STOI_MIN_FREQ):
+    """(obm float64 [num_bands, n_fft/2 + 1] of 0/1, edges int [num_bands, 2]): band k has the centre min_freq 2^(k/3) and covers the bins
+    [lo_k, hi_k), lo_k / hi_k = the bin whose frequency f_j = j sr / n_fft is nearest (first of equals) to min_freq 2^((2k -/+ 1)/6)
+    (eval/utils.py `thirdoct`, restated from the definition in float64)."""
+    f = np.linspace(0, sr, n_fft + 1)[:n_fft // 2 + 1]
+    k = np.arange(num_bands, dtype=np.float64)
+    lo_hz, hi_hz = min_freq * np.power(2.0, (2 * k - 1) / 6), min_freq * np.power(2.0, (2 * k + 1) / 6)
+    obm = np.zeros((num_bands, f.shape[0]), dtype=np.float64)
+    edges = np.zeros((num_bands, 2), dtype=np.int64)
+    for i in range(num_bands):
+        edges[i] = int(np.argmin(np.square(f - lo_hz[i]))), int(np.argmin(np.square(f - hi_hz[i])))
+        obm[i, edges[i, 0]:edges[i, 1]] = 1.0
+    return obm, edges
+
+
+def stoi_window():
+    """The symmetric Hann window np.hanning(1026)[1:-1] (matlab's hanning(1024)): float64."""
+    return np.hanning(STOI_NFFT + 2)[1:-1]
+
+
+def _stoi_images(sr, device):
+    from . import melspec
+
+    def build(_old):
+        obm, edges = third_octave_bands(sr)
+        nbins = int(edges[:, 1].max())  # bins [0, nbins): whole 32-bin chunks from bin_lo = 0
+        if not obm.any():
+            raise ValueError("stoi: no third-octave band lies below sr / 2 = %g Hz" % (sr / 2.0))
+        table = melspec.pack_dft_table(melspec.dft_table(STOI_NFFT, STOI_NFFT, 0, nbins, window=stoi_window()))
+        basis = melspec.pack_mel_basis(obm.astype(np.float32), 0, nbins)
+        win = stoi_window().astype(np.float32)
+        return tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in (win, table, basis)) + (nbins,)
+    return _STOI_IMAGES.setdefault(int(sr), ops.CacheSlot()).get((device,), build)
+
+
+def stoi(ref, deg, lengths=None, *, sr=STOI_SR, extended=False):
+    """eval/stoi.py `stoi(x, y, 22050, extended=False)` for a batch: ref, deg [B, N] (or [N]) fp32 on the GPU, `lengths` samples per pair ->
+    (d [B] fp32, valid [B] bool) on the device; nothing is synchronised or copied to the host.  A pair the reference returns None for
+    (fewer than 30 envelope frames after the silent frames are removed) has valid = False and d = NaN.  `sr` only selects the band matrix:
+    nothing is resampled."""
+    if extended:
+        raise NotImplementedError("stoi: extended=True is not built (its EPS * randn terms are not reproducible)")
+    ops._f(ref, "ref"), ops._f(deg, "deg")
+    single = ref.dim() == 1
+    if single:
+        ref, deg = ref[None], deg[None] if deg.dim() == 1 else deg
+    if ref.dim() != 2 or ref.shape != deg.shape or ref.device != deg.device:
+        raise ValueError("ref and deg must both be [B, N] (or [N]) on one device, got %s and %s" % (tuple(ref.shape), tuple(deg.shape)))
+    B, N = ref.shape
+    if N <= STOI_NFFT:
+        raise ValueError("stoi needs more than %d samples, got %d" % (STOI_NFFT, N))
+    lengths = _lengths(lengths, B, N, ref.device, "lengths", lo=0)
+    win, table, basis, nbins = _stoi_images(sr, ref.device)
+    kept, K, _ = ops.stoi_select(ref, win, lengths)
+    sil, sil_len = ops.stoi_compact(ref, deg, win, kept, K)
+    tob = ops.stoi_bands(sil, table, basis, sil_len, n_bands=STOI_BANDS, bin_lo=0, nbins=nbins)
+    d, valid = ops.stoi_score(tob, sil_len[:B])
+    return (d[0], valid[0]) if single else (d, valid)
+
+
+def wav_stoi(wav_ref, wav_gen, len_ref=None, len_gen=None):
+    """eval/stoi.py `cal_stoi` for a batch of waveform pairs ([B, N1] and [B, N2], or [N1] and [N2]; len_* in samples): each pair is cut
+    to the shorter of its two lengths, on the device, then `stoi`.  The reference's / 32768.1 is not applied: STOI is scale-invariant."""
+    ops._f(wav_ref, "wav_ref"), ops._f(wav_gen, "wav_gen")
+    single = wav_ref.dim() == 1 and wav_gen.dim() == 1
+    if single:
+        wav_ref, wav_gen = wav_ref[None], wav_gen[None]
+    if wav_ref.dim() != 2 or wav_gen.dim() != 2 or wav_ref.shape[0] != wav_gen.shape[0]:
+        raise ValueError("wav_ref and wav_gen must be [B, N1] and [B, N2], got %s and %s" % (tuple(wav_ref.shape), tuple(wav_gen.shape)))
+    B, N = wav_ref.shape[0], min(wav_ref.shape[1], wav_gen.shape[1])
+    len_ref = _lengths(len_ref, B, wav_ref.shape[1], wav_ref.device, "len_ref", lo=0)
+    len_gen = _lengths(len_gen, B, wav_gen.shape[1], wav_ref.device, "len_gen", lo=0)
+    lengths = None
+    if len_ref is not None or len_gen is not None:
+        full = torch.full((B,), N, dtype=torch.int64, device=wav_ref.device)
+        lengths = torch.minimum(full if len_ref is None else len_ref, full if len_gen is None else len_gen).clamp_(max=N)
+    d, valid = stoi(wav_ref[:, :N].contiguous(), wav_gen[:, :N].contiguous(), lengths)
+    return (d[0], valid[0]) if single else (d, valid)
+
+
+def stoi_mean(d, valid):
+    """The mean of d over the valid pairs (eval/stoi.py `cal_stoi_with_waves_batch`), a 0-dim tensor on the device; NaN when none is."""
+    return torch.where(valid, d, torch.zeros_like(d)).sum() / valid.sum()

@@ -655,6 +655,85 @@ def mcd_finish(num, steps, len_1, len_2, T1, T2):
     return mcd, penalty, frames
 
 
+STOI_FRAME, STOI_HOP, STOI_SEG = 1024, 256, 30
+
+
+def stoi_sizes(N):
+    """(F_max, S, T) of waveforms of N samples (include/set_amd.h, the STOI block): energy frames at hop 512, samples of a compacted row,
+    envelope frames at hop 256."""
+    f_max = -(-(int(N) - STOI_FRAME) // (STOI_FRAME // 2)) if N > STOI_FRAME else 0
+    return f_max, (STOI_FRAME // 2) * (f_max + 1), max(2 * (f_max - 1), 0)
+
+
+def _stoi_wave_args(x, win, what):
+    _f(x, "x"), _f(win, "win")
+    if x.dim() != 2 or x.shape[1] <= STOI_FRAME or win.shape != (STOI_FRAME,):
+        raise ValueError("%s: x must be [B,N] with N > %d and win [%d], got %s and %s" % (what, STOI_FRAME, STOI_FRAME, tuple(x.shape),
+                                                                                         tuple(win.shape)))
+    return x.shape[0], x.shape[1], stoi_sizes(x.shape[1])
+
+
+def stoi_select(x, win, lengths=None, nrm=None, kept=None, K=None):
+    """set_stoi_select: x [B,N] -> (kept [B,F_max] int32, K [B] int32, nrm [B,F_max] fp32): the frames of each row within 40 dB of its
+    loudest, ascending in kept[b, :K[b]], and the frame norms nrm[b, :F_b]; entries beyond are left as they were."""
+    B, N, (f_max, _, _) = _stoi_wave_args(x, win, "stoi_select")
+    _len_arg(lengths, B, "lengths")
+    nrm = _out_arg(nrm, (B, f_max), torch.float32, x, "nrm")
+    kept = _out_arg(kept, (B, f_max), torch.int32, x, "kept")
+    K = _out_arg(K, (B,), torch.int32, x, "K")
+    check(_lib.lib().set_stoi_select(_p(x), x.stride(0), _p(lengths), _p(win), _p(nrm), _p(kept), _p(K), B, N, STOI_FRAME, _stream()),
+          "set_stoi_select")
+    return kept, K, nrm
+
+
+def stoi_compact(x, y, win, kept, K, sil=None, sil_len=None):
+    """set_stoi_compact: the overlap-add of the kept windowed frames of x and of y (both by x's list) -> (sil [2B,S], sil_len [2B] int64);
+    row b is x's signal, row B + b is y's, and nothing at or beyond sil_len is written."""
+    B, N, (f_max, S, _) = _stoi_wave_args(x, win, "stoi_compact")
+    _f(y, "y"), _chk(kept, torch.int32, "kept"), _chk(K, torch.int32, "K")
+    if y.shape != x.shape or y.device != x.device or kept.shape != (B, f_max) or K.shape != (B,):
+        raise ValueError("stoi_compact: y must be %s, kept [%d,%d] and K [%d], got %s, %s and %s"
+                         % (tuple(x.shape), B, f_max, B, tuple(y.shape), tuple(kept.shape), tuple(K.shape)))
+    sil = _out_arg(sil, (2 * B, S), torch.float32, x, "sil")
+    sil_len = _out_arg(sil_len, (2 * B,), torch.int64, x, "sil_len")
+    check(_lib.lib().set_stoi_compact(_p(x), _p(y), x.stride(0), _p(win), _p(kept), _p(K), _p(sil), S, _p(sil_len), B, N, STOI_FRAME,
+                                      _stream()), "set_stoi_compact")
+    return sil, sil_len
+
+
+def stoi_bands(sil, table, basis, lens=None, *, n_bands, bin_lo, nbins, tob=None):
+    """set_stoi_bands: sil [R,S] -> band envelopes tob [R,T,n_bands], T = ceil((S - 1024) / 256); frames at or beyond a row's own count
+    (from `lens`, int64 [R] samples) are +0.0.  `table` / `basis`: the packed DFT table and band matrix (metrics.stoi prepares them).
+    S <= 1024 has no frame: an empty result and no launch."""
+    _f(sil, "sil"), _f(table, "table"), _f(basis, "basis")
+    if sil.dim() != 2:
+        raise ValueError("stoi_bands: sil must be [R,S], got %s" % (tuple(sil.shape),))
+    R, S = sil.shape
+    _len_arg(lens, R, "lens")
+    T = -(-(S - STOI_FRAME) // STOI_HOP) if S > STOI_FRAME else 0
+    tob = _out_arg(tob, (R, T, n_bands), torch.float32, sil, "tob")
+    if table.numel() < _lib.lib().set_log_mel_table_size(STOI_FRAME, nbins) or basis.numel() < (nbins + 31) // 32 * 16 * 64 * 4:
+        raise ValueError("stoi_bands: table / basis images are smaller than nbins = %d needs" % nbins)
+    if T > 0:
+        check(_lib.lib().set_stoi_bands(_p(sil), sil.stride(0), _p(lens), _p(table), _p(basis), _p(tob), R, S, T, STOI_FRAME, STOI_HOP,
+                                        n_bands, bin_lo, nbins, _stream()), "set_stoi_bands")
+    return tob
+
+
+def stoi_score(tob, lens=None, d=None, valid=None):
+    """set_stoi_score: tob [2B,T,n_bands] (row b = clean, row B + b = degraded) -> (d [B] fp32, valid [B] bool).  `lens` int64 [B]:
+    compacted samples per pair (stoi_compact's sil_len[:B]); a row of fewer than 30 frames has valid = False and d = NaN."""
+    _f(tob, "tob")
+    if tob.dim() != 3 or tob.shape[0] % 2:
+        raise ValueError("stoi_score: tob must be [2B,T,n_bands], got %s" % (tuple(tob.shape),))
+    B, T, n_bands = tob.shape[0] // 2, tob.shape[1], tob.shape[2]
+    _len_arg(lens, B, "lens")
+    d = _out_arg(d, (B,), torch.float32, tob, "d")
+    valid = _out_arg(valid, (B,), torch.bool, tob, "valid")
+    check(_lib.lib().set_stoi_score(_p(tob) if T else None, _p(lens), _p(d), _p(valid), B, T, n_bands, STOI_SEG, _stream()), "set_stoi_score")
+    return d, valid
+
+
 def preln_self_attn(x, ln, attn, key_padding=None, mask=None, eps=1e-5):
     """Inference form of autograd_ops.preln_self_attn."""
     h = layernorm_ch(x, ln[0], ln[1], eps=eps)
