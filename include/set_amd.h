@@ -929,6 +929,34 @@ int set_stoi_bands(const float *sil, int64_t sil_bs, const int64_t *lens, const 
 int set_stoi_score(const float *tob, const int64_t *lens, float *d, uint8_t *valid, int32_t B, int32_t T, int32_t n_bands, int32_t seg,
                    void *stream);
 
+/* Wav-level mel-cepstral distortion of the reference's eval script (csrc/wav_mcd.hip; eval/mcd.py `cal_mcd` on
+ * librosa.feature.mfcc(sr=22050, n_mfcc=34, n_fft=1024, hop_length=256, n_mels=80, fmin=55, fmax=7600, htk=True), librosa 0.8.0).  All
+ * tensors fp32 and contiguous; every `frames*` is int64 [B] on the device or NULL (every row full) and is read clamped into [0, T]: no
+ * kernel leaves its buffers whatever the device holds.  No atomics anywhere: two runs agree bit for bit, and a row of a ragged batch equals
+ * the same pair run alone.
+ *
+ * set_db_mel: SetLogMelArgs as for set_log_mel, with pad = n_fft / 2 and reflect = 1 (librosa 0.8.0's center=True), else
+ *   SET_E_UNSUPPORTED; mag_eps is not read.  A row of len_b samples has T_b = 1 + len_b / hop frames when len_b > pad and none otherwise;
+ *   T = 1 + N / hop, N > pad.  mel[b][t][m] = fl(log_scale * log(max(S, floor))) evaluated in double, S = sum_bin basis[m][bin] (re^2 + im^2)
+ *   with both products on v_mfma_f32_32x32x2_f32 by the kernel body of set_log_mel (csrc/dft_gemm.h); frames t >= T_b are +0.0.  dB of a
+ *   power is floor = 1e-10, log_scale = 10 / ln 10.  table / basis are the images of set_log_mel.
+ * set_db_peak: db [B][T][M], frames [B] -> peak [B] = max over t < T_b and all m of db[b][t][m]; -inf for a row without frames.  Frames at
+ *   or beyond T_b are not read.
+ * set_db_mfcc: out [B][T][K], out[b][t][k] = sum_n x[n] table[k][n] in ascending n (fp32 FMA), x[n] = max(db[b][t][n], fl(peak[b] -
+ *   top_db)).  table [K][M] = s_k cos(pi k (2n+1) / (2M)), k = 0..K-1, s_0 = 1/sqrt(M), s_k = sqrt(2/M) (metrics.dct_ortho_table).  Rows
+ *   t >= frames[b] are written as +0.0.  K <= 64, M <= 96, else SET_E_UNSUPPORTED.
+ * set_coef_rms_dist: x [B][Tx][K], y [B][Ty][K] -> mcd [B], valid [B] uint8.  A pair with frames_x != frames_y, or without frames, has
+ *   valid = 0 and mcd = NaN.  Else, with T_b the common count: s_k = sum_{t < T_b} (x[t][k] - y[t][k])^2 in double (thread q of 4 sums
+ *   t = q, q + 4, ... ascending; s_k = (p_0 + p_1) + (p_2 + p_3)); mcd = fl((sum_k 10 / ln 10 sqrt(2 s_k)) / K / T_b), the sum over k
+ *   ascending in double; valid = 1.  The sum inside the root runs over the FRAMES, as the reference's axis=1 on [K, T] arrays does.
+ *   K <= 64, else SET_E_UNSUPPORTED. */
+int set_db_mel(const SetLogMelArgs *args, void *stream);
+int set_db_peak(const float *db, const int64_t *frames, float *peak, int32_t B, int32_t T, int32_t M, void *stream);
+int set_db_mfcc(const float *db, const int64_t *frames, const float *peak, const float *table, float *out, int32_t B, int32_t T, int32_t M,
+                int32_t K, float top_db, void *stream);
+int set_coef_rms_dist(const float *x, const float *y, const int64_t *frames_x, const int64_t *frames_y, float *mcd, uint8_t *valid, int32_t B,
+                      int32_t Tx, int32_t Ty, int32_t K, void *stream);
+
 /* MFMA fragment-layout self test: runs a 32x32xK product through v_mfma_f32_32x32x2_f32 with the layout
  * this library assumes and returns the max abs error vs an in-kernel scalar reference via *max_err (HOST).
  * Synchronises.  Used by tests to pin the hardware layout assumption. */

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_PKG, "libset_amd.so")
 # measurement only (tools/build_exp.sh): load an experimental build of the library instead; never built or rebuilt from here
 _LIB_OVERRIDE = os.environ.get("SET_AMD_LIB")
 SOURCES = ["conv1d.hip", "weight_image.hip", "conv_x2.hip", "resblock_x2.hip", "glue.hip", "diffnet.hip", "diffnet_x3.hip", "boundary.hip", "diffusion_ops.hip", "diffusion_loop.hip",
-           "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip", "melspec.hip", "mcd.hip", "stoi.hip"]
+           "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip", "melspec.hip", "mcd.hip", "stoi.hip", "wav_mcd.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 # constants mirrored from set_amd.h
@@ -342,6 +342,10 @@ SIGNATURES = {
     "set_stoi_compact": (C.c_int, [_V, _V, _I64, _V, _V, _V, _V, _I64, _V, _I32, _I32, _I32, _V]),
     "set_stoi_bands": (C.c_int, [_V, _I64, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _V]),
     "set_stoi_score": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _I32, _V]),
+    "set_db_mel": (C.c_int, [C.POINTER(SetLogMelArgs), _V]),
+    "set_db_peak": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _V]),
+    "set_db_mfcc": (C.c_int, [_V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _F, _V]),
+    "set_coef_rms_dist": (C.c_int, [_V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _V]),
     "set_frame_weight": (C.c_int, [_V, _V, _I64, _I32, _V]),
     "set_l1_elem": (C.c_int, [_V, _V, _V, _V, _I64, _V]),
     "set_scale_bcast": (C.c_int, [_V, _V, _V, _I64, _I64, _V, _F, _V]),

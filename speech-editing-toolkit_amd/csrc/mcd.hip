@@ -1,7 +1,7 @@
 // Mel-cepstral distortion on the device (utils/eval/mcd.py `get_metrics_mels`): mel -> MFCC -> exact DTW (or zero fill) -> three numbers
 // per pair.
 //   set_mfcc            c[b][t][k-1] = sum_n x[b][t][n] cos(pi k (2n+1) / (2M)), k = 1..K: a plain fp32 FMA chain in ascending n against a
-//                       host-built table; ~3 k MACs per frame.
+//                       host-built table; ~3 k MACs per frame.  The kernel is mfcc_kernel<false> of mfcc.h (wav_mcd.hip runs its other form).
 //   set_dtw             the exact DTW of utils/metrics/dtw.py `accelerated_dtw(x, y, 'euclidean', warp=1)`.  One 256-thread block per pair;
 //                       strips of 256 rows; thread t owns row i of the strip, holds x_i in registers and walks the columns skewed: at step
 //                       s it is at column s - t, so the three predecessors of its cell were finished one and two steps earlier --
@@ -17,7 +17,7 @@
 //                       in ascending t, then a fixed LDS tree.
 //   set_mcd_finish      mcd = num / frames, penalty = 2 - (len_1 + len_2) / frames.
 // Costs are in the difference form sqrt(sum_k (x_ik - y_jk)^2): on integer grids every cost, every D and every comparison is exact.
-#include "common.h"
+#include "mfcc.h"  // mfcc_kernel<DB>, row_len, MCD_K_MAX / MCD_M_MAX: shared with wav_mcd.hip
 
 namespace {
 
@@ -25,15 +25,8 @@ constexpr int DTW_ROWS = 256;                   // rows per strip = threads per 
 constexpr int DTW_CB = 64;                      // columns staged at a time
 constexpr int DTW_RING = DTW_ROWS + DTW_CB;     // columns the ring holds (a multiple of 64: the bank of a column survives the wrap)
 constexpr int DTW_TY_MAX = 8192;                // boundary buffer: 8 bytes of LDS per column
-constexpr int MCD_K_MAX = 64, MCD_M_MAX = 96;
 
 constexpr int dtw_lds_bytes(int kp, int Ty) { return (DTW_RING * (kp + 1) + 2 * Ty + 16) * 4; }
-
-// a row's length, read as the caller wrote it but never outside [lo, T]: the kernels stay inside their buffers whatever the device holds
-__device__ __forceinline__ int row_len(const int64_t *p, int b, int lo, int T) {
-    const int64_t v = p ? p[b] : (int64_t)T;
-    return (int)(v < lo ? lo : (v > T ? T : v));
-}
 
 template <int KP>
 __global__ void __launch_bounds__(256) dtw_kernel(const float *__restrict__ x, const float *__restrict__ y, const int64_t *__restrict__ len_x,
@@ -199,37 +192,6 @@ __global__ void __launch_bounds__(64) mcd_finish_kernel(const float *__restrict_
     frames[b] = fr;
 }
 
-constexpr int MFCC_FR = 16;  // frames per block
-
-__global__ void __launch_bounds__(256) mfcc_kernel(const float *__restrict__ mel, const int64_t *__restrict__ lengths,
-                                                   const float *__restrict__ table, float *__restrict__ out, int T, int M, int K, int take_log) {
-    __shared__ float xs[MFCC_FR][MCD_M_MAX];
-    __shared__ float ts[MCD_K_MAX * (MCD_M_MAX + 1)];  // row stride 97: lanes at different k, same n, on different banks
-    const int tid = threadIdx.x, b = blockIdx.y, t0 = blockIdx.x * MFCC_FR;
-    const int len = row_len(lengths, b, 0, T);
-    for (int e = tid; e < K * M; e += 256) {
-        const int k = e / M;
-        ts[k * (MCD_M_MAX + 1) + (e - k * M)] = table[e];
-    }
-    for (int e = tid; e < MFCC_FR * M; e += 256) {
-        const int f = e / M, n = e - f * M, t = t0 + f;
-        float v = 0.0f;
-        if (t < len) {
-            v = mel[((int64_t)b * T + t) * M + n];
-            if (take_log) v = (float)log10((double)v);  // rounded once
-        }
-        xs[f][n] = v;
-    }
-    __syncthreads();
-    for (int e = tid; e < MFCC_FR * K; e += 256) {
-        const int f = e / K, k = e - f * K, t = t0 + f;
-        if (t >= T) break;
-        float acc = 0.0f;
-        for (int n = 0; n < M; ++n) acc = __builtin_fmaf(xs[f][n], ts[k * (MCD_M_MAX + 1) + n], acc);
-        out[((int64_t)b * T + t) * K + k] = t < len ? acc : 0.0f;
-    }
-}
-
 }  // namespace
 
 extern "C" int set_mfcc(const float *mel, const int64_t *lengths, const float *table, float *out, int32_t B, int32_t T, int32_t M, int32_t K,
@@ -239,7 +201,8 @@ extern "C" int set_mfcc(const float *mel, const int64_t *lengths, const float *t
     if (K > MCD_K_MAX || M > MCD_M_MAX) return set_fail(SET_E_UNSUPPORTED, "set_mfcc", "built for n_mfcc <= 64, n_mels <= 96");
     SET_REQUIRE((int64_t)B * T * M < (int64_t)1 << 40, "set_mfcc");
     const dim3 grid((T + MFCC_FR - 1) / MFCC_FR, B);
-    hipLaunchKernelGGL(mfcc_kernel, grid, dim3(256), 0, (hipStream_t)stream, mel, lengths, table, out, T, M, K, take_log);
+    hipLaunchKernelGGL(mfcc_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, mel, lengths, table, out, T, M, K, take_log,
+                       (const float *)nullptr, 0.0f);
     return set_check_launch("set_mfcc");
 }
 

@@ -69,8 +69,20 @@ def slaney_mel_basis(sr, n_fft, n_mels, fmin, fmax):
     (utils/audio/__init__.py:69-70)."""
     fmin = 0.0 if fmin == -1 else float(fmin)
     fmax = sr / 2.0 if fmax == -1 else float(fmax)
+    return _triangles(sr, n_fft, _mel_to_hz(np.linspace(_hz_to_mel(fmin), _hz_to_mel(fmax), n_mels + 2)))
+
+
+def htk_mel_basis(sr, n_fft, n_mels, fmin, fmax):
+    """The HTK-scale filterbank, mel = 2595 log10(1 + f / 700): librosa.filters.mel(htk=True), whose default area normalisation
+    2 / (f_{m+2} - f_m) still applies.  Triangles between n_mels + 2 points equally spaced in mel from fmin to fmax.  float64 arithmetic,
+    float32 [n_mels, n_fft/2 + 1] result."""
+    mel = 2595.0 * np.log10(1.0 + np.array([float(fmin), float(fmax)]) / 700.0)
+    return _triangles(sr, n_fft, 700.0 * (np.power(10.0, np.linspace(mel[0], mel[1], n_mels + 2) / 2595.0) - 1.0))
+
+
+def _triangles(sr, n_fft, edges):
+    """Area-normalised triangles between consecutive triples of `edges` (Hz, float64 [n_mels + 2]) on the n_fft/2 + 1 bin frequencies."""
     freqs = np.linspace(0.0, sr / 2.0, 1 + n_fft // 2)
-    edges = _mel_to_hz(np.linspace(_hz_to_mel(fmin), _hz_to_mel(fmax), n_mels + 2))
     fdiff = np.diff(edges)
     ramps = edges[:, None] - freqs[None, :]
     lower = -ramps[:-2] / fdiff[:-1, None]

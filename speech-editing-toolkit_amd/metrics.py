@@ -1,5 +1,5 @@
-"""Evaluation metrics on the GPU: mel-cepstral distortion (csrc/mcd.hip) and short-time objective intelligibility (csrc/stoi.hip; the
-second half of this file).
+"""Evaluation metrics on the GPU: mel-cepstral distortion (csrc/mcd.hip), short-time objective intelligibility (csrc/stoi.hip; the
+second part of this file) and the wav-level mel-cepstral distortion of the reference's eval script (csrc/wav_mcd.hip; the third part).
 
 Mel-cepstral distortion: mel -> MFCC -> exact DTW or zero fill -> (mcd, penalty, frames) per pair.
 
@@ -13,10 +13,12 @@ After the reference's utils/eval/mcd.py `get_metrics_mels`, term by term:
               mcd = sum ||.|| / max(len), frames = max(len).  penalty = 2 - (len_1 + len_2) / frames in both.
     wav_mcd   melspec.LogMel(hparams, "librosa") on both waveforms, then mel_mcd.
 
-Two things are NOT what a run of the reference's file gives:
+One thing is NOT what a run of the reference's file gives:
   * The reference calls `fastdtw` (radius 1), an APPROXIMATION of DTW (and not a dependency here).  This module computes the exact DTW that
     the reference's own utils/metrics/dtw.py defines, so its `dist` is <= fastdtw's, and the two are equal whenever fastdtw finds the optimum.
-  * eval/mcd.py's wav-level variant (HTK filterbank, orthonormal DCT of dB power, 34 coefficients) is not built.
+
+eval/mcd.py's wav-level variant -- the MCD column eval/get_metrics.py prints -- is the third part of this file (csrc/wav_mcd.hip):
+`htk_mfcc`, `wav_mcd_htk`, `mcd_mean`, and `eval_wav_pairs` for the MCD and STOI means of a batch of waveform pairs in one call.
 
 Mels are [B, T, M], the package's layout; the reference's single-pair (k, n) = [M, T] layout is one `transpose` away.  Everything is a
 kernel of libset_amd.so: CPU tensors are refused, there is no eager fallback.  The only host work is the DCT table (float64, once per
@@ -233,3 +235,150 @@ def wav_stoi(wav_ref, wav_gen, len_ref=None, len_gen=None):
 def stoi_mean(d, valid):
     """The mean of d over the valid pairs (eval/stoi.py `cal_stoi_with_waves_batch`), a 0-dim tensor on the device; NaN when none is."""
     return torch.where(valid, d, torch.zeros_like(d)).sum() / valid.sum()
+
+
+# ---- wav-level mel-cepstral distortion (eval/mcd.py `cal_mcd`, the MCD of eval/get_metrics.py) ----------------------------------------------
+# librosa.feature.mfcc(y, sr=22050, n_fft=1024, win_length=1024, hop_length=256, n_mels=80, fmin=55, fmax=7600, n_mfcc=34, htk=True) under
+# the reference's librosa 0.8.0, restated: reflection padding of 512, periodic Hann, |STFT|^2, the HTK-scale area-normalised filterbank,
+# 10 log10(max(1e-10, S)), the clamp at 80 dB under the utterance's own maximum, the orthonormal DCT-II with c0.  Three launches per
+# signal (include/set_amd.h, the wav-level block): dB mel, the peak, the clamped DCT; then one for the distance, or set_dtw and
+# set_mcd_finish.  Built for these constants: the kernel body is the log-mel's (n_fft 1024, hop 256, n_mels <= 96).
+HTK_SR, HTK_NFFT, HTK_HOP, HTK_MELS, HTK_FMIN, HTK_FMAX, HTK_MFCC, HTK_TOP_DB = 22050, 1024, 256, 80, 55, 7600, 34, 80.0
+HTK_PAD = HTK_NFFT // 2
+_HTK_IMAGES = ops.CacheSlot()  # (packed DFT table, packed filterbank, bin_lo, nbins, n_mels) of the restated filterbank on the device last used
+_ORTHO_TABLES = {}  # (K, M, device) -> the orthonormal DCT table on that device
+
+
+def dct_ortho_table(n_mfcc, n_mels):
+    """float32 [K, M]: s_k cos(pi k (2n+1) / (2M)) for k = 0..K-1, s_0 = 1/sqrt(M), s_k = sqrt(2/M) -- rows of scipy.fft.dct(type=2,
+    norm='ortho') -- each rounded once from float64; the angle is reduced exactly in integers as `dct_table` does."""
+    k = np.arange(n_mfcc, dtype=np.int64)[:, None]
+    n = np.arange(n_mels, dtype=np.int64)[None, :]
+    ang = 2.0 * np.pi * ((k * (2 * n + 1)) % (4 * n_mels)).astype(np.float64) / (4 * n_mels)
+    scale = np.where(k == 0, np.sqrt(1.0 / n_mels), np.sqrt(2.0 / n_mels))
+    return (scale * np.cos(ang)).astype(np.float32)
+
+
+def _htk_images(device, mel_basis=None):
+    from . import melspec
+
+    def build(_old):
+        b = melspec.htk_mel_basis(HTK_SR, HTK_NFFT, HTK_MELS, HTK_FMIN, HTK_FMAX) if mel_basis is None else mel_basis
+        b = (b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)).astype(np.float32)
+        if b.ndim != 2 or b.shape[1] != HTK_NFFT // 2 + 1 or not 1 <= b.shape[0] <= M_MAX:
+            raise ValueError("mel_basis must be [n_mels <= %d, %d], got %s" % (M_MAX, HTK_NFFT // 2 + 1, tuple(b.shape)))
+        lo, hi = melspec.bin_range(b)
+        table = melspec.pack_dft_table(melspec.dft_table(HTK_NFFT, HTK_NFFT, lo, hi - lo))
+        basis = melspec.pack_mel_basis(b, lo, hi - lo)
+        return torch.from_numpy(table).to(device), torch.from_numpy(basis).to(device), lo, hi - lo, b.shape[0]
+    return _HTK_IMAGES.get((device,), build) if mel_basis is None else build(None)
+
+
+def htk_frames(n_samples):
+    """Frames of a waveform of n_samples under center=True: 1 + N // 256; 0 when reflection is impossible (N <= 512)."""
+    return 1 + int(n_samples) // HTK_HOP if n_samples > HTK_PAD else 0
+
+
+def _sample_lengths(lengths, B, N, device, name):
+    """(samples int64 [B] on the device or None, frames int64 [B] on the device or None, frames as host ints or None).  Host values are
+    checked here: a row of <= 512 samples cannot be reflected and is refused.  A device tensor passes without a host sync; the kernels
+    read it clamped into [0, N], and such a row has no frames and is invalid."""
+    if lengths is None:
+        return None, None, [htk_frames(N)] * B
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype != torch.int64 or lengths.shape != (B,):
+            raise ValueError("%s must be int64 [%d], got %s %s" % (name, B, lengths.dtype, tuple(lengths.shape)))
+        lengths = lengths.contiguous()
+        n = lengths.clamp(0, N)
+        return lengths, torch.where(n > HTK_PAD, 1 + n // HTK_HOP, torch.zeros_like(n)), None
+    host = np.asarray(lengths.numpy() if isinstance(lengths, torch.Tensor) else lengths).astype(np.int64).reshape(-1)
+    if host.shape[0] != B or host.min() <= HTK_PAD or host.max() > N:
+        raise ValueError("%s must be %d values in (%d, %d] (reflection padding of %d needs more samples than that), got %s"
+                         % (name, B, HTK_PAD, N, HTK_PAD, host.tolist()))
+    frames = [htk_frames(n) for n in host]
+    return torch.from_numpy(host).to(device), torch.tensor(frames, dtype=torch.int64, device=device), frames
+
+
+def _htk_mfcc(wav, lengths, n_mfcc, top_db, mel_basis, name):
+    """wav [B, N] -> (c [B, T, n_mfcc], frames on the device or None, frames on the host or None)."""
+    B, N = wav.shape
+    if N <= HTK_PAD:
+        raise ValueError("%s: reflection padding of %d needs more than %d samples, got %d" % (name, HTK_PAD, HTK_PAD, N))
+    n_mfcc = int(n_mfcc)
+    samples, frames, host = _sample_lengths(lengths, B, N, wav.device, name)
+    table, basis, lo, nbins, n_mels = _htk_images(wav.device, mel_basis)
+    if not 1 <= n_mfcc <= min(K_MAX, n_mels):
+        raise ValueError("htk_mfcc is built for 1 <= n_mfcc <= min(%d, n_mels = %d), got %d" % (K_MAX, n_mels, n_mfcc))
+    key = (n_mfcc, n_mels, wav.device)
+    if key not in _ORTHO_TABLES:
+        _ORTHO_TABLES[key] = torch.from_numpy(dct_ortho_table(n_mfcc, n_mels)).to(wav.device)
+    db = ops.db_mel(wav, table, basis, samples, n_mels=n_mels, bin_lo=lo, nbins=nbins)
+    c = ops.db_mfcc(db, _ORTHO_TABLES[key], ops.db_peak(db, frames), frames, top_db)
+    return c, frames, host
+
+
+def htk_mfcc(wav, lengths=None, *, n_mfcc=HTK_MFCC, top_db=HTK_TOP_DB, mel_basis=None):
+    """librosa.feature.mfcc(htk=True) at the constants of eval/mcd.py for a batch: wav [B, N] (or [N]) fp32 on the GPU -> c [B, T, n_mfcc]
+    (or [T, n_mfcc]), T = 1 + N // 256, c0 included; with `lengths` (samples per row) also the frames per row, int64 on the device.  Rows at
+    or beyond a row's frame count are +0.0.  The 80 dB clamp hangs under each row's own maximum over its own frames.  `mel_basis` replaces
+    the restated filterbank (float32 [n_mels <= 96, 513], e.g. librosa's own array).  The filterbank is restated from its definition
+    (melspec.htk_mel_basis); librosa is not a dependency."""
+    ops._f(wav, "wav")
+    single = wav.dim() == 1
+    if single:
+        wav = wav[None]
+    if wav.dim() != 2:
+        raise ValueError("wav must be [B, N] or [N], got %s" % (tuple(wav.shape),))
+    c, frames, _ = _htk_mfcc(wav, lengths, n_mfcc, top_db, mel_basis, "lengths")
+    if single:
+        c = c[0]
+    return c if lengths is None else (c, frames)
+
+
+def wav_mcd_htk(wav_ref, wav_est, len_ref=None, len_est=None, *, use_dtw=False):
+    """eval/mcd.py `cal_mcd` for a batch of waveform pairs: wav_ref [B, N1], wav_est [B, N2] (or one pair [N1], [N2]; len_* in samples) ->
+    (mcd [B] fp32, valid [B] bool) on the device; nothing is synchronised or copied to the host.
+
+    use_dtw=False (what `cal_mcd_with_wave_batch` runs), term by term: on the [34, T] arrays diff2sum = sum over axis 1 -- over the
+    FRAMES, one value per coefficient -- and mcd = mean_k(10 / ln 10 sqrt(2 diff2sum_k)) / T_ref.  It needs equal frame counts (the
+    reference's subtraction would raise): when both lengths are host values an unequal pair raises here; when one lives on the device the
+    pair has valid = False and mcd = NaN, as has a pair with a row of <= 512 samples.
+
+    use_dtw=True is NOT what the reference's file runs: that hands the [34, T] arrays to fastdtw as they are, aligning coefficient indices
+    with frames as the feature axis, and fails for unequal T.  Built here is the evident intent: the exact DTW over frames ([T, 34]
+    sequences, `dtw`) and mcd = dist / steps, the mean distance of the aligned frames, as the branch's last lines compute."""
+    ops._f(wav_ref, "wav_ref"), ops._f(wav_est, "wav_est")
+    single = wav_ref.dim() == 1 and wav_est.dim() == 1
+    if single:
+        wav_ref, wav_est = wav_ref[None], wav_est[None]
+    if wav_ref.dim() != 2 or wav_est.dim() != 2 or wav_ref.shape[0] != wav_est.shape[0] or wav_ref.device != wav_est.device:
+        raise ValueError("wav_ref and wav_est must be [B, N1] and [B, N2] (or [N1] and [N2]) on one device, got %s and %s"
+                         % (tuple(wav_ref.shape), tuple(wav_est.shape)))
+    c1, f1, h1 = _htk_mfcc(wav_ref, len_ref, HTK_MFCC, HTK_TOP_DB, None, "len_ref")
+    c2, f2, h2 = _htk_mfcc(wav_est, len_est, HTK_MFCC, HTK_TOP_DB, None, "len_est")
+    if not use_dtw:
+        if h1 is not None and h2 is not None and h1 != h2:
+            raise ValueError("wav_mcd_htk(use_dtw=False) needs equal frame counts in every pair, got %s and %s" % (h1, h2))
+        mcd, valid = ops.coef_rms_dist(c1, c2, f1, f2)
+    else:
+        dist, steps = ops.dtw(c1, c2, f1, f2)
+        mcd = ops.mcd_finish(dist, steps, f1, f2, c1.shape[1], c2.shape[1])[0]
+        valid = torch.ones_like(steps, dtype=torch.bool)
+        for f in (f1, f2):
+            if f is not None:
+                valid &= f > 0
+        mcd = torch.where(valid, mcd, torch.full_like(mcd, float("nan")))
+    return (mcd[0], valid[0]) if single else (mcd, valid)
+
+
+def mcd_mean(mcd, valid):
+    """The mean of mcd over the valid pairs (eval/mcd.py `cal_mcd_with_wave_batch`), a 0-dim tensor on the device; NaN when none is."""
+    return torch.where(valid, mcd, torch.zeros_like(mcd)).sum() / valid.sum()
+
+
+def eval_wav_pairs(wav_ref, wav_est, len_ref=None, len_est=None):
+    """The two means eval/get_metrics.py prints that are built here, for a batch of (ground truth, prediction) waveform pairs:
+    {"mcd": mcd_mean(wav_mcd_htk), "stoi": stoi_mean(wav_stoi)}, 0-dim tensors on the device.  PESQ is a third-party C library and is not
+    built."""
+    return {"mcd": mcd_mean(*wav_mcd_htk(wav_ref, wav_est, len_ref, len_est)),
+            "stoi": stoi_mean(*wav_stoi(wav_ref, wav_est, len_ref, len_est))}

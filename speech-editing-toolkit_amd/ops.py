@@ -734,6 +734,69 @@ def stoi_score(tob, lens=None, d=None, valid=None):
     return d, valid
 
 
+DB_FLOOR, DB_SCALE = 1e-10, 10.0 / math.log(10.0)  # librosa.power_to_db: 10 log10(max(amin, S)), ref = 1
+
+
+def db_mel(wav, table, basis, lengths=None, *, n_mels, bin_lo, nbins, out=None):
+    """set_db_mel: wav [B,N] -> 10 log10(max(1e-10, basis |STFT|^2)) [B,T,n_mels], T = 1 + N // 256, reflection padding of 512 (`table` /
+    `basis`: the packed images of set_log_mel; `lengths` int64 [B] samples on the device or None).  A row of more than 512 samples has
+    1 + len // 256 frames, a shorter one none; frames at or beyond a row's own count are +0.0."""
+    _f(wav, "wav"), _f(table, "table"), _f(basis, "basis")
+    if wav.dim() != 2 or wav.shape[1] <= 512:
+        raise ValueError("db_mel: wav must be [B,N] with N > 512, got %s" % (tuple(wav.shape),))
+    B, N = wav.shape
+    _len_arg(lengths, B, "lengths")
+    T = 1 + N // 256
+    out = _out_arg(out, (B, T, n_mels), torch.float32, wav, "out")
+    if table.numel() < _lib.lib().set_log_mel_table_size(1024, nbins) or basis.numel() < (nbins + 31) // 32 * 16 * 64 * 4:
+        raise ValueError("db_mel: table / basis images are smaller than nbins = %d needs" % nbins)
+    a = _lib.SetLogMelArgs(wav=_p(wav), lengths=_p(lengths), table=_p(table), basis=_p(basis), mel=_p(out),
+                           wav_bs=wav.stride(0) if B > 1 else N,  # (a one-row tensor's stride is whatever its maker left there)
+                           log_scale=DB_SCALE, B=B, N=N, T=T, n_fft=1024, hop=256, n_mels=n_mels, bin_lo=bin_lo, nbins=nbins, pad=512,
+                           reflect=1, clamp_input=0, mag_eps=0.0, floor=DB_FLOOR)
+    check(_lib.lib().set_db_mel(C.byref(a), _stream()), "set_db_mel")
+    return out
+
+
+def db_peak(db, frames=None, peak=None):
+    """set_db_peak: db [B,T,M] -> peak [B], the maximum over the row's own frames (`frames` int64 [B] or None) and all bands; -inf for a
+    row without frames."""
+    _f(db, "db")
+    if db.dim() != 3:
+        raise ValueError("db_peak: db must be [B,T,M], got %s" % (tuple(db.shape),))
+    B, T, M = db.shape
+    _len_arg(frames, B, "frames")
+    peak = _out_arg(peak, (B,), torch.float32, db, "peak")
+    check(_lib.lib().set_db_peak(_p(db), _p(frames), _p(peak), B, T, M, _stream()), "set_db_peak")
+    return peak
+
+
+def db_mfcc(db, table, peak, frames=None, top_db=80.0, out=None):
+    """set_db_mfcc: db [B,T,M], peak [B] -> [B,T,K] = table [K,M] (metrics.dct_ortho_table) applied to max(db, peak - top_db); rows at or
+    beyond `frames` are +0.0."""
+    _f(db, "db"), _f(table, "table"), _f(peak, "peak")
+    if db.dim() != 3 or table.dim() != 2 or table.shape[1] != db.shape[2] or peak.shape != (db.shape[0],):
+        raise ValueError("db_mfcc: db must be [B,T,M], table [K,M] and peak [B], got %s, %s and %s"
+                         % (tuple(db.shape), tuple(table.shape), tuple(peak.shape)))
+    B, T, M = db.shape
+    K = table.shape[0]
+    _len_arg(frames, B, "frames")
+    out = _out_arg(out, (B, T, K), torch.float32, db, "out")
+    check(_lib.lib().set_db_mfcc(_p(db), _p(frames), _p(peak), _p(table), _p(out), B, T, M, K, float(top_db), _stream()), "set_db_mfcc")
+    return out
+
+
+def coef_rms_dist(x, y, frames_x=None, frames_y=None, mcd=None, valid=None):
+    """set_coef_rms_dist: x [B,Tx,K], y [B,Ty,K] -> (mcd [B] fp32, valid [B] bool): eval/mcd.py `cal_mcd(use_dtw=False)` per pair,
+    mean_k(10 / ln 10 sqrt(2 sum_t (x - y)^2)) / T.  A pair of unequal frame counts, or without frames, has valid = False and mcd = NaN."""
+    B, Tx, Ty, K = _pair_args(x, y, frames_x, frames_y, "coef_rms_dist")
+    mcd = _out_arg(mcd, (B,), torch.float32, x, "mcd")
+    valid = _out_arg(valid, (B,), torch.bool, x, "valid")
+    check(_lib.lib().set_coef_rms_dist(_p(x), _p(y), _p(frames_x), _p(frames_y), _p(mcd), _p(valid), B, Tx, Ty, K, _stream()),
+          "set_coef_rms_dist")
+    return mcd, valid
+
+
 def preln_self_attn(x, ln, attn, key_padding=None, mask=None, eps=1e-5):
     """Inference form of autograd_ops.preln_self_attn."""
     h = layernorm_ch(x, ln[0], ln[1], eps=eps)
