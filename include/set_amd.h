@@ -957,6 +957,61 @@ int set_db_mfcc(const float *db, const int64_t *frames, const float *peak, const
 int set_coef_rms_dist(const float *x, const float *y, const int64_t *frames_x, const int64_t *frames_y, float *mcd, uint8_t *valid, int32_t B,
                       int32_t Tx, int32_t Ty, int32_t K, void *stream);
 
+/* HiFi-GAN mel loss and its waveform gradient (csrc/mel_loss.hip; tasks/vocoder/hifigan.py:35-38, F.l1_loss of two
+ * modules/vocoder/hifigan/mel_utils.py:59-76 `mel_spectrogram`s).  All tensors fp32 and contiguous.  No atomics anywhere: two runs agree bit
+ * for bit, every sum has one fixed order, and a row's gradient depends on the other rows only through the factor 1 / count.
+ *
+ * set_mel_linear: SetLogMelArgs as for set_log_mel (floor and log_scale are not read); mel [B][T][n_mels] = the filterbank product itself,
+ *   the value set_log_mel takes the log of, bit for bit.
+ * set_mel_loss_fwd: mel_hat, mel_y [B][T][n_mels] (set_mel_linear's) -> loss [1], g_mel [B][T][n_mels] and, when not NULL, log_hat / log_y.
+ *   With L = fl(log_scale * log(max(mel, floor))) evaluated in double (set_log_mel's own value), d = fl(L_hat - L_y), count = B T n_mels:
+ *     g_mel = (mel_hat >= floor && d != 0) ? copysign(fl(log_scale), d) / mel_hat : 0                  (torch: sign(0) = 0, clamp(min=)
+ *   passes the gradient at mel >= floor) -- count times d loss / d mel_hat: set_mel_loss_bwd divides by count once, at the end, so a
+ *   row's gradient has the same bits before that whatever the batch -- and loss = fl(S / count) with S = sum |d| in this order: block k of 4096 elements, thread tid of 256
+ *   sums elements 4096 k + 256 i + tid in ascending i = 0..15 (elements beyond count add nothing); column c = tid & 63 of the block is
+ *   ((s[c] + s[64 + c]) + s[128 + c]) + s[192 + c]; the blocks' columns are summed by csrc/rows_sum.h (16 row groups of four chains), and
+ *   the 64 column sums in ascending order.  part: set_mel_loss_fwd_scratch_floats(count) floats of scratch.
+ * set_mel_loss_bwd: g_mel [B][T][n_mels] and the waveform wav [B][wav_bs >= N] (the y_hat the forward saw) -> g_wav [B][N], every sample
+ *   written: 1 / count times d/d wav of sum g_mel[b][t][m] mel[b][t][m] through the filterbank, the magnitude sqrt(re^2 + im^2 + mag_eps), the windowed DFT,
+ *   the reflect padding of pad = (n_fft - hop) / 2 and the clamp to [-1, 1] (gradient passed where -1 <= wav <= 1, both ends included).
+ *   Three launches: (1) per 64-frame tile re / im again by GEMM 1 of set_log_mel on the same `table`, g_mag = basis^T g_mel, g_re = g_mag
+ *   re / mag, g_im likewise -> spec [B][2][nbins rounded up to 32s][T rounded up to 64s] (set_mel_loss_bwd_spec_floats); (2) the padded
+ *   gradient g_pad [B][(T + 3) hop], g_pad[hop u + c] = sum_{q < 4} sum_f W[0][f][hop q + c] g_re[f][u - q] + W[1][f][hop q + c]
+ *   g_im[f][u - q], a gather (a block owns 64 hops); (3) g_wav[j] = (g_pad[j + pad] + g_pad[pad - j] for 1 <= j <= pad) + g_pad[pad +
+ *   2 (N - 1) - j] for N - 1 - pad <= j <= N - 2, g_pad read as 0 beyond its end, divided by count (fp32; 1 for a g_mel that carries
+ *   its own scale), times the clamp mask.
+ *   basis_t  image of mel_basis^T: [32-bin chunk][k-step s 0..47][lane], = mel_basis[2 s + (lane >> 5)][bin_lo + 32 chunk + (lane & 31)],
+ *            0 outside the matrix and for bins beyond bin_lo + nbins
+ *   itable   image of the table W of set_log_mel for launch (2): set_mel_idft_table_size(n_fft, nbins) floats ordered
+ *            [32-bin chunk][wave 0..3][q 0..3][part 0..1][s 0..15][lane][2], element e = W[part][32 chunk + 2 s + (lane >> 5)][256 q +
+ *            64 wave + 32 e + (lane & 31)]
+ * Built for n_fft = 1024, hop = 256, n_mels <= 96, pad = 384: anything else is SET_E_UNSUPPORTED.  table / itable / g_pad 16-byte aligned. */
+typedef struct SetMelLossFwdArgs {
+    const float *mel_hat, *mel_y;
+    float *g_mel, *log_hat, *log_y, *part, *loss;
+    double log_scale;
+    int32_t B, T, n_mels;
+    float floor;
+} SetMelLossFwdArgs;
+typedef struct SetMelLossBwdArgs {
+    const float *wav, *table, *basis_t, *itable, *g_mel;
+    float *spec, *g_pad, *g_wav;
+    int64_t wav_bs;
+    int32_t B, N, T;
+    int32_t n_fft, hop, n_mels;
+    int32_t bin_lo, nbins, pad;
+    float mag_eps, count;
+    int32_t pad_;
+} SetMelLossBwdArgs;
+int64_t set_sizeof_mel_loss_fwd_args(void);
+int64_t set_sizeof_mel_loss_bwd_args(void);
+int set_mel_linear(const SetLogMelArgs *args, void *stream);
+int64_t set_mel_loss_fwd_scratch_floats(int64_t count);
+int set_mel_loss_fwd(const SetMelLossFwdArgs *args, void *stream);
+int64_t set_mel_idft_table_size(int32_t n_fft, int32_t nbins);
+int64_t set_mel_loss_bwd_spec_floats(int32_t B, int32_t T, int32_t nbins);
+int set_mel_loss_bwd(const SetMelLossBwdArgs *args, void *stream);
+
 /* MFMA fragment-layout self test: runs a 32x32xK product through v_mfma_f32_32x32x2_f32 with the layout
  * this library assumes and returns the max abs error vs an in-kernel scalar reference via *max_err (HOST).
  * Synchronises.  Used by tests to pin the hardware layout assumption. */

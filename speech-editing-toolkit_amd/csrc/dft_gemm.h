@@ -35,6 +35,69 @@ __device__ __forceinline__ int padded_index(int64_t i, int len, int pad, int ref
     return valid ? (int)idx : -1;
 }
 
+// The two steps of log_mel_kernel below that the spectral backward of the mel loss (mel_loss.hip) repeats on the same table image and LDS
+// slice, as functions: the staged slice and GEMM 1 of one 32-bin chunk.  Same loads, same k order, same MFMAs as the kernel body: the
+// spectrum the backward recomputes has the forward's bits.  log_mel_kernel keeps its own text of the two steps: routed through these
+// functions hipcc schedules and allocates its body otherwise (the device assembly of all three users changes), and the shipped instances
+// stay the code they were measured as.  A change to either copy belongs in both.
+__device__ __forceinline__ void dft_stage_slice(float *S, const float *__restrict__ x, int len, int t0, int pad, int reflect, int clamp_input,
+                                                int tid) {
+    const int64_t i0 = (int64_t)t0 * MEL_HOP + tid;
+    constexpr int NB = 12;
+    for (int u0 = 0; u0 < MEL_U; u0 += NB) {
+        int idx[NB];
+        float v[NB];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) idx[k] = u0 + k < MEL_U ? padded_index(i0 + (int64_t)(u0 + k) * MEL_HOP, len, pad, reflect) : -1;
+#pragma unroll
+        for (int k = 0; k < NB; ++k) v[k] = x[idx[k] < 0 ? 0 : idx[k]];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            float w = clamp_input ? fminf(fmaxf(v[k], -1.0f), 1.0f) : v[k];
+            if (u0 + k < MEL_U) S[tid * MEL_U + u0 + k] = idx[k] < 0 ? 0.0f : w;
+        }
+    }
+}
+
+// re / im [cb] of chunk `ch`: register r of lane l = bin row urow16(r) + 4 (l >> 5) of the chunk, frame 32 cb + (l & 31) of the tile
+__device__ __forceinline__ void dft_chunk_spectrum(const float *__restrict__ table, int ch, const float *S, int lane, f32x16 (&re)[2],
+                                                   f32x16 (&im)[2]) {
+    const int h = lane >> 5, j = lane & 31;
+    const f32x4 *__restrict__ wp = reinterpret_cast<const f32x4 *>(table) + (int64_t)ch * (MEL_NFFT / 4) * 64 + lane;
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) re[cb][r] = im[cb][r] = 0.0f;
+    f32x4 A[MEL_KB / 2], An[MEL_KB / 2];
+#pragma unroll
+    for (int p = 0; p < MEL_KB / 2; ++p) A[p] = wp[p * 64];
+    constexpr int NBODY = MEL_NFFT / 2 / MEL_KB;
+    for (int body = 0; body < NBODY; ++body) {
+        const int nb = body + 1 < NBODY ? body + 1 : body;  // last body: re-load itself (in bounds, unused)
+#pragma unroll
+        for (int p = 0; p < MEL_KB / 2; ++p) An[p] = wp[(nb * (MEL_KB / 2) + p) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+        const int n0 = body * (2 * MEL_KB);
+        const float *sp = S + ((n0 & (MEL_HOP - 1)) + h) * MEL_U + (n0 >> 8) + j;
+        float B0[MEL_KB], B1[MEL_KB];
+#pragma unroll
+        for (int u = 0; u < MEL_KB; ++u) {
+            B0[u] = sp[u * 2 * MEL_U];
+            B1[u] = sp[u * 2 * MEL_U + 32];
+        }
+#pragma unroll
+        for (int u = 0; u < MEL_KB; ++u) {
+            const float ar = A[u >> 1][(u & 1) * 2], ai = A[u >> 1][(u & 1) * 2 + 1];
+            re[0] = mfma32(ar, B0[u], re[0]);
+            im[0] = mfma32(ai, B0[u], im[0]);
+            re[1] = mfma32(ar, B1[u], re[1]);
+            im[1] = mfma32(ai, B1[u], im[1]);
+        }
+#pragma unroll
+        for (int p = 0; p < MEL_KB / 2; ++p) A[p] = An[p];
+    }
+}
+
 template <class P>
 __global__ void __launch_bounds__(256, 2) log_mel_kernel(SetLogMelArgs a, int nchunks) {
     extern __shared__ __attribute__((aligned(16))) float S[];

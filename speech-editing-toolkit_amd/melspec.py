@@ -162,6 +162,31 @@ def pack_mel_basis(mel_basis, bin_lo, nbins):
     return img.reshape(nch, 16, 64, 4)
 
 
+def pack_mel_basis_t(mel_basis, bin_lo, nbins):
+    """The image of the transposed filterbank for the mel loss's backward (include/set_amd.h, set_mel_loss_bwd): [chunk][s][lane] =
+    mel_basis[2 s + (lane >> 5)][bin_lo + 32 chunk + (lane & 31)], s = 0..47, zero outside the matrix and beyond bin_lo + nbins -- the A
+    operand of g_mag = basis^T g_mel, whose result lands in the register layout of re / im."""
+    b = np.asarray(mel_basis, dtype=np.float32)
+    n_mels = min(b.shape[0], 3 * 32)
+    nch = (nbins + CHUNK - 1) // CHUNK
+    full = np.zeros((3 * 32, nch * CHUNK), dtype=np.float32)
+    full[:n_mels, :nbins] = b[:n_mels, bin_lo:bin_lo + nbins]
+    v = full.reshape(48, 2, nch, CHUNK)                          # s, h, chunk, i
+    return np.ascontiguousarray(v.transpose(2, 0, 1, 3)).reshape(nch, 48, 64)
+
+
+def pack_idft_table(table):
+    """The image of dft_table's result for the inverse product of the mel loss's backward (set_mel_loss_bwd): [chunk][wave][q][part][s]
+    [lane][2], element e = table[part][32 chunk + 2 s + (lane >> 5)][256 q + 64 wave + 32 e + (lane & 31)], rows beyond nbins zero."""
+    table = np.asarray(table, dtype=np.float32)
+    _, nbins, n_fft = table.shape
+    nch = (nbins + CHUNK - 1) // CHUNK
+    full = np.zeros((2, nch * CHUNK, n_fft), dtype=np.float32)
+    full[:, :nbins] = table
+    v = full.reshape(2, nch, 16, 2, n_fft // 256, 4, 2, 32)     # part, chunk, s, h, q, wave, e, i
+    return np.ascontiguousarray(v.transpose(1, 5, 4, 0, 2, 3, 7, 6)).reshape(nch, 4, n_fft // 256, 2, 16, 64, 2)
+
+
 class LogMel:
     """wav [B, N] (or [N]) fp32 on the GPU -> log-mel [B, T, n_mels] (or [T, n_mels]); with `lengths` also the frames per row.
 

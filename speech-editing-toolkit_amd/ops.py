@@ -567,6 +567,69 @@ def log_mel(wav, table, basis, lengths=None, *, n_fft, hop, n_mels, bin_lo, nbin
     return mel
 
 
+def _buf(shape, device, sentinel):
+    """An output or scratch buffer a kernel must write in full: uninitialised, or filled with `sentinel` (the tests pass NaN)."""
+    t = torch.empty(shape, dtype=torch.float32, device=device)
+    return t if sentinel is None else t.fill_(sentinel)
+
+
+def mel_linear(wav, table, basis, *, n_fft, hop, n_mels, bin_lo, nbins, pad, reflect, clamp_input, mag_eps, sentinel=None):
+    """set_mel_linear: wav [B,N] -> the filterbank product [B,T,n_mels] that set_log_mel takes the log of (same kernel body, same images)."""
+    _f(wav, "wav"), _f(table, "table"), _f(basis, "basis")
+    B, N = wav.shape
+    T = 1 + (N + 2 * pad - n_fft) // hop
+    mel = _buf((B, max(T, 0), n_mels), wav.device, sentinel)
+    a = _lib.SetLogMelArgs(wav=_p(wav), lengths=None, table=_p(table), basis=_p(basis), mel=_p(mel), wav_bs=wav.stride(0), log_scale=1.0,
+                           B=B, N=N, T=T, n_fft=n_fft, hop=hop, n_mels=n_mels, bin_lo=bin_lo, nbins=nbins, pad=pad, reflect=int(reflect),
+                           clamp_input=int(clamp_input), mag_eps=float(mag_eps), floor=1.0)
+    if table.numel() < _lib.lib().set_log_mel_table_size(n_fft, nbins) or basis.numel() < (nbins + 31) // 32 * 16 * 64 * 4:
+        raise ValueError("mel_linear: table / basis images are smaller than n_fft = %d, nbins = %d need" % (n_fft, nbins))
+    check(_lib.lib().set_mel_linear(C.byref(a), _stream()), "set_mel_linear")
+    return mel
+
+
+def mel_loss_fwd(mel_hat, mel_y, *, floor, log_scale, return_logs=False, sentinel=None):
+    """set_mel_loss_fwd: the two linear mels [B,T,n_mels] -> (loss [1] = mean |L_hat - L_y|, g_mel = B T n_mels d loss / d mel_hat, L_hat, L_y);
+    the two log-mels are None unless `return_logs`.  Two launches, no atomics, one summation order."""
+    _f(mel_hat, "mel_hat"), _f(mel_y, "mel_y")
+    if mel_hat.dim() != 3 or mel_hat.shape != mel_y.shape:
+        raise ValueError("mel_loss_fwd: mel_hat and mel_y must be equal [B, T, n_mels], got %s and %s" % (tuple(mel_hat.shape), tuple(mel_y.shape)))
+    B, T, M = mel_hat.shape
+    dev = mel_hat.device
+    g_mel, loss = _buf((B, T, M), dev, sentinel), _buf((1,), dev, sentinel)
+    log_hat = _buf((B, T, M), dev, sentinel) if return_logs else None
+    log_y = _buf((B, T, M), dev, sentinel) if return_logs else None
+    part = _buf((_lib.lib().set_mel_loss_fwd_scratch_floats(B * T * M),), dev, sentinel)
+    a = _lib.SetMelLossFwdArgs(mel_hat=_p(mel_hat), mel_y=_p(mel_y), g_mel=_p(g_mel), log_hat=_p(log_hat), log_y=_p(log_y), part=_p(part),
+                               loss=_p(loss), log_scale=float(log_scale), B=B, T=T, n_mels=M, floor=float(floor))
+    check(_lib.lib().set_mel_loss_fwd(C.byref(a), _stream()), "set_mel_loss_fwd")
+    return loss, g_mel, log_hat, log_y
+
+
+def mel_loss_bwd(wav, g_mel, table, basis_t, itable, *, n_fft, hop, n_mels, bin_lo, nbins, pad, mag_eps, count=1.0, sentinel=None):
+    """set_mel_loss_bwd: the waveform [B,N] the linear mel was taken of and g_mel [B,T,n_mels] -> d/d wav [B,N] through filterbank,
+    magnitude, windowed DFT, reflect padding and the input clamp, divided by `count` at the end (mel_loss_fwd's g_mel is count times the
+    loss's gradient).  vocoder_losses.MelSpectrogramLoss prepares the images.  Three launches."""
+    _f(wav, "wav"), _f(g_mel, "g_mel"), _f(table, "table"), _f(basis_t, "basis_t"), _f(itable, "itable")
+    B, N = wav.shape
+    T = 1 + (N + 2 * pad - n_fft) // hop
+    if tuple(g_mel.shape) != (B, T, n_mels):
+        raise ValueError("mel_loss_bwd: g_mel must be [%d, %d, %d], got %s" % (B, T, n_mels, tuple(g_mel.shape)))
+    L = _lib.lib()
+    nch = (nbins + 31) // 32
+    if table.numel() < L.set_log_mel_table_size(n_fft, nbins) or itable.numel() < L.set_mel_idft_table_size(n_fft, nbins) \
+            or basis_t.numel() < nch * 48 * 64:
+        raise ValueError("mel_loss_bwd: table / basis_t / itable images are smaller than n_fft = %d, nbins = %d need" % (n_fft, nbins))
+    dev = wav.device
+    spec = _buf((max(L.set_mel_loss_bwd_spec_floats(B, T, nbins), 0),), dev, sentinel)
+    g_pad, g_wav = _buf((B, (max(T, 0) + 3) * hop), dev, sentinel), _buf((B, N), dev, sentinel)
+    a = _lib.SetMelLossBwdArgs(wav=_p(wav), table=_p(table), basis_t=_p(basis_t), itable=_p(itable), g_mel=_p(g_mel), spec=_p(spec),
+                               g_pad=_p(g_pad), g_wav=_p(g_wav), wav_bs=wav.stride(0), B=B, N=N, T=T, n_fft=n_fft, hop=hop, n_mels=n_mels,
+                               bin_lo=bin_lo, nbins=nbins, pad=pad, mag_eps=float(mag_eps), count=float(count))
+    check(L.set_mel_loss_bwd(C.byref(a), _stream()), "set_mel_loss_bwd")
+    return g_wav
+
+
 def _len_arg(lengths, B, name):
     _i(lengths, name)
     if lengths is not None and lengths.shape != (B,):
