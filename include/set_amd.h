@@ -1012,6 +1012,62 @@ int64_t set_mel_idft_table_size(int32_t n_fft, int32_t nbins);
 int64_t set_mel_loss_bwd_spec_floats(int32_t B, int32_t T, int32_t nbins);
 int set_mel_loss_bwd(const SetMelLossBwdArgs *args, void *stream);
 
+/* Multi-resolution STFT loss and its waveform gradient, one resolution per call (csrc/stft_loss.hip; tasks/vocoder/hifigan.py:46-47 on
+ * modules/vocoder/hifigan/stft_loss.py).  All tensors fp32 and contiguous unless said.  With mag(s) = sqrt(max(re^2 + im^2, 1e-7)) of the
+ * windowed DFT of the reflect-padded (n_fft / 2 each side) row, periodic Hann of `win` samples centred in n_fft, T = 1 + N / hop frames,
+ * n_fft / 2 + 1 bins, count = B T (n_fft / 2 + 1):
+ *     sc = sqrt(S_d) / sqrt(S_g), mag = S_l / count;  S_d = sum (y_mag - x_mag)^2, S_g = sum y_mag^2, S_l = sum |ln y_mag - ln x_mag|
+ * over the whole batch.  No atomics anywhere: two runs agree bit for bit and every sum has one fixed order.  A row's magnitudes do not
+ * depend on the batch; the losses and the gradient couple the rows through exactly three scalars: D = sqrt(S_d), G = sqrt(S_g), count.
+ *
+ * Geometries are compiled in: set_stft_geometries writes up to max_triples (n_fft, hop, win) triples and returns how many exist; any
+ * other triple is SET_E_UNSUPPORTED with the list in the message.  set_stft_sizes -> out8 = {T, floats of `table`, floats of `itable`,
+ * doubles of `part`, floats of the kept magnitudes `mag`, floats of `spec`, floats of `g_pad`, Ts = T rounded up to 64s}.
+ *   table    [32-bin chunk][k-step s < win/2][lane][2], element e = W[e][32 chunk + (lane & 31)][left + 2 s + (lane >> 5)], left = (n_fft -
+ *            win) / 2: only the win non-zero window samples; W = melspec.dft_table's [2][bins][n_fft], rows beyond the last bin zero
+ *   itable   [32-bin chunk][wave vw < NW][k-step kk < 32 Q][lane], Q = ceil(win / hop), q = kk >> 5, part = (kk >> 4) & 1, s = kk & 15:
+ *            W[part][32 chunk + 2 s + (lane >> 5)][left + hop q + c], c = 32 rb + (lane & 31); rb = vw with NW = ceil(hop / 32) when a hop
+ *            has 4 or 8 row blocks of 32 samples, rb = vw >> 1 with NW = 4 when it has 2; zero where c >= hop, hop q + c >= win or the
+ *            bin does not exist
+ * set_stft_magnitude: x [B][x_bs >= N] -> mag [B][T][n_fft/2 + 1].  Each (bin, frame) is one accumulator that takes the win window samples
+ *   in ascending order (v_mfma_f32_32x32x2_f32); re^2 + im^2 = fl(fl(re re) + fl(im im)).
+ * set_stft_loss_fwd: x, y -> loss [2] = {sc, mag}, stats [6] doubles = {D, G, count, S_d, S_g, S_l}; when `mag` is not NULL it receives
+ *   the magnitudes of the signal that is not differentiated (x when which = 1, y when which = 0) as [B][chunks x 32][Ts] for
+ *   set_stft_loss_bwd.  Order of the sums: block (z, b, tile) = 64 frames x bin chunks 4 z .. 4 z + 3 of row b, one chunk per wave; lane l
+ *   of a wave adds its entries in double in the order column block cb = 0, 1 (frame 64 tile + 32 cb + (l & 31)), register r = 0..15 (bin
+ *   32 chunk + (r & 3) + 8 (r >> 2) + 4 (l >> 5)); an entry is d = fl(y_mag - x_mag) squared, y_mag squared (both exact in double) and
+ *   |fl(ln y_mag) - fl(ln x_mag)| with ln evaluated in double and rounded to fp32 once, the difference in fp32; frames >= T and bins
+ *   beyond the last add 0.  The 64 lanes by v += v[lane ^ o] for o = 32, 16, 8, 4, 2, 1; the waves as ((w0 + w1) + w2) + w3 -> part[((z B
+ *   + b) tiles + tile)][3].  Then thread t of 256 adds blocks t, t + 256, ... in ascending order and the 256 thread sums are added in
+ *   ascending order.  D, G by double sqrt; sc = fl32(D / G), mag = fl32(S_l / count).
+ * set_stft_loss_bwd: d (u_sc scale sc + u_mag scale mag) / d (y when which = 1, x when which = 0) -> g_wav [B][N], every sample written
+ *   (accumulate = 0) or added to (accumulate = 1).  u_sc, u_mag: device scalars (never read by the host); stats: set_stft_loss_fwd's.
+ *   With m the differentiated signal's magnitude, r the other's (from `mag`, or by a second DFT when mag is NULL):
+ *     g_m = (c1 (m - r) - c2 m) + c3 sign(m - r) / m,   c1 = u_sc scale / (D G) (0 when D = 0), c2 = u_sc scale D / G^3 (0 when which = 0),
+ *     c3 = u_mag scale / count, the coefficients evaluated in double and rounded to fp32 once;  g_re = g_m re / m, g_im = g_m im / m where
+ *     re^2 + im^2 >= 1e-7, else 0 -> spec [B][2][chunks x 32][Ts]; then g_pad [B][(T + Q - 1) hop] (padded sample left + i at i) = the
+ *     inverse windowed DFT as a gather (one accumulator per sample; order: chunk, tap q, part, bin), and the fold g_wav[j] = (g_p[j + P] +
+ *     g_p[P - j] for 1 <= j <= P) + g_p[P + 2 (N - 1) - j] for N - 1 - P <= j <= N - 2, P = n_fft / 2, g_p = 0 where no window sample lies.
+ *   A g_m [B][T][n_fft/2 + 1] that is not NULL is used as the magnitude gradient instead (stats, u_sc, u_mag are then not read).
+ * N > n_fft / 2 (reflect padding), B <= 65535.  table / itable / g_pad 16-byte aligned. */
+typedef struct SetStftLossArgs {
+    const float *x, *y, *table, *itable, *u_sc, *u_mag, *g_m;
+    float *mag, *loss, *spec, *g_pad, *g_wav;
+    double *part, *stats;
+    int64_t x_bs, y_bs;
+    int32_t B, N, T;
+    int32_t n_fft, hop, win;
+    int32_t which, accumulate;
+    float scale;
+    int32_t pad_;
+} SetStftLossArgs;
+int64_t set_sizeof_stft_loss_args(void);
+int32_t set_stft_geometries(int32_t *triples, int32_t max_triples);
+int set_stft_sizes(int32_t n_fft, int32_t hop, int32_t win, int64_t B, int64_t N, int64_t *out8);
+int set_stft_magnitude(const SetStftLossArgs *args, void *stream);
+int set_stft_loss_fwd(const SetStftLossArgs *args, void *stream);
+int set_stft_loss_bwd(const SetStftLossArgs *args, void *stream);
+
 /* MFMA fragment-layout self test: runs a 32x32xK product through v_mfma_f32_32x32x2_f32 with the layout
  * this library assumes and returns the max abs error vs an in-kernel scalar reference via *max_err (HOST).
  * Synchronises.  Used by tests to pin the hardware layout assumption. */

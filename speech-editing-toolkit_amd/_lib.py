@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_PKG, "libset_amd.so")
 # measurement only (tools/build_exp.sh): load an experimental build of the library instead; never built or rebuilt from here
 _LIB_OVERRIDE = os.environ.get("SET_AMD_LIB")
 SOURCES = ["conv1d.hip", "weight_image.hip", "conv_x2.hip", "resblock_x2.hip", "glue.hip", "diffnet.hip", "diffnet_x3.hip", "boundary.hip", "diffusion_ops.hip", "diffusion_loop.hip",
-           "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip", "melspec.hip", "mcd.hip", "stoi.hip", "wav_mcd.hip", "mel_loss.hip"]
+           "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip", "melspec.hip", "mcd.hip", "stoi.hip", "wav_mcd.hip", "mel_loss.hip", "stft_loss.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 # constants mirrored from set_amd.h
@@ -218,6 +218,20 @@ class SetMelLossBwdArgs(C.Structure):
     ]
 
 
+class SetStftLossArgs(C.Structure):
+    _fields_ = [
+        ("x", C.c_void_p), ("y", C.c_void_p), ("table", C.c_void_p), ("itable", C.c_void_p), ("u_sc", C.c_void_p), ("u_mag", C.c_void_p),
+        ("g_m", C.c_void_p),
+        ("mag", C.c_void_p), ("loss", C.c_void_p), ("spec", C.c_void_p), ("g_pad", C.c_void_p), ("g_wav", C.c_void_p),
+        ("part", C.c_void_p), ("stats", C.c_void_p),
+        ("x_bs", C.c_int64), ("y_bs", C.c_int64),
+        ("B", C.c_int32), ("N", C.c_int32), ("T", C.c_int32),
+        ("n_fft", C.c_int32), ("hop", C.c_int32), ("win", C.c_int32),
+        ("which", C.c_int32), ("accumulate", C.c_int32),
+        ("scale", C.c_float), ("pad_", C.c_int32),
+    ]
+
+
 _V, _I32, _I64, _U64, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/set_amd.h declares
@@ -363,6 +377,12 @@ SIGNATURES = {
     "set_mel_idft_table_size": (_I64, [_I32, _I32]),
     "set_mel_loss_bwd_spec_floats": (_I64, [_I32, _I32, _I32]),
     "set_mel_loss_bwd": (C.c_int, [C.POINTER(SetMelLossBwdArgs), _V]),
+    "set_sizeof_stft_loss_args": (_I64, []),
+    "set_stft_geometries": (_I32, [C.POINTER(_I32), _I32]),
+    "set_stft_sizes": (C.c_int, [_I32, _I32, _I32, _I64, _I64, C.POINTER(_I64)]),
+    "set_stft_magnitude": (C.c_int, [C.POINTER(SetStftLossArgs), _V]),
+    "set_stft_loss_fwd": (C.c_int, [C.POINTER(SetStftLossArgs), _V]),
+    "set_stft_loss_bwd": (C.c_int, [C.POINTER(SetStftLossArgs), _V]),
     "set_mfcc": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _I32, _I32, _V]),
     "set_dtw": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _V]),
     "set_dtw_path": (C.c_int, [_V, _V, _V, _V, _V, _I32, _I32, _I32, _V]),
@@ -484,6 +504,7 @@ def lib():
     assert L.set_sizeof_log_mel_args() == C.sizeof(SetLogMelArgs), "SetLogMelArgs ABI mismatch"
     assert L.set_sizeof_mel_loss_fwd_args() == C.sizeof(SetMelLossFwdArgs), "SetMelLossFwdArgs ABI mismatch"
     assert L.set_sizeof_mel_loss_bwd_args() == C.sizeof(SetMelLossBwdArgs), "SetMelLossBwdArgs ABI mismatch"
+    assert L.set_sizeof_stft_loss_args() == C.sizeof(SetStftLossArgs), "SetStftLossArgs ABI mismatch"
     _lib = L
     return L
 

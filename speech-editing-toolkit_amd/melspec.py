@@ -187,6 +187,59 @@ def pack_idft_table(table):
     return np.ascontiguousarray(v.transpose(1, 5, 4, 0, 2, 3, 7, 6)).reshape(nch, 4, n_fft // 256, 2, 16, 64, 2)
 
 
+def pack_stft_table(table, win_length):
+    """The image of dft_table's result for the STFT loss (include/set_amd.h, set_stft_magnitude): only the win_length non-zero window
+    samples, [chunk][s][lane][2] with element e = table[e][32 chunk + (lane & 31)][left + 2 s + (lane >> 5)], left = (n_fft -
+    win_length) / 2, rows beyond nbins zero -- the A fragment of k-step s of the real and the imaginary row block as one 8-byte unit."""
+    table = np.asarray(table, dtype=np.float32)
+    _, nbins, n_fft = table.shape
+    left = (n_fft - win_length) // 2
+    nch = (nbins + CHUNK - 1) // CHUNK
+    full = np.zeros((2, nch * CHUNK, win_length), dtype=np.float32)
+    full[:, :nbins] = table[:, :, left:left + win_length]
+    v = full.reshape(2, nch, CHUNK, win_length // 2, 2)                                      # part, chunk, i, s, h
+    return np.ascontiguousarray(v.transpose(1, 3, 4, 2, 0)).reshape(nch, win_length // 2, 64, 2)  # chunk, s, (h, i), part
+
+
+def unpack_stft_table(image, nbins, n_fft):
+    """Inverse of pack_stft_table: float32 [2, nbins, n_fft], zero outside the window."""
+    image = np.asarray(image, dtype=np.float32)
+    nch, half = image.shape[0], image.shape[1]
+    v = image.reshape(nch, half, 2, CHUNK, 2).transpose(4, 0, 3, 1, 2)                      # part, chunk, i, s, h
+    out = np.zeros((2, nbins, n_fft), dtype=np.float32)
+    left = (n_fft - 2 * half) // 2
+    out[:, :, left:left + 2 * half] = np.ascontiguousarray(v).reshape(2, nch * CHUNK, 2 * half)[:, :nbins]
+    return out
+
+
+def stft_idft_layout(hop, win_length):
+    """(Q, row blocks of a hop, NW): the taps a window spans, the 32-sample row blocks of a hop, and the waves the inverse kernel gives
+    a 64-hop tile -- one per row block when a hop has 4 or 8, four (a row block and a column block each) when it has 2."""
+    q, rbt = -(-win_length // hop), -(-hop // 32)
+    if rbt not in (2, 4, 8):
+        raise ValueError("a hop of %d samples is %d row blocks of 32; the inverse kernel takes 2, 4 or 8" % (hop, rbt))
+    return q, rbt, (rbt if rbt >= 4 else 4)
+
+
+def pack_stft_idft_table(table, hop, win_length):
+    """The image of dft_table's result for the inverse product of the STFT loss's backward (set_stft_loss_bwd): [chunk][wave][kk][lane]
+    with q = kk >> 5, part = (kk >> 4) & 1, s = kk & 15 = table[part][32 chunk + 2 s + (lane >> 5)][left + hop q + c], c = 32 rb +
+    (lane & 31), rb = wave (4 or 8 row blocks) or wave >> 1 (2 row blocks); zero where c >= hop, hop q + c >= win_length or the row is
+    beyond nbins."""
+    table = np.asarray(table, dtype=np.float32)
+    _, nbins, n_fft = table.shape
+    left = (n_fft - win_length) // 2
+    Q, rbt, NW = stft_idft_layout(hop, win_length)
+    nch = (nbins + CHUNK - 1) // CHUNK
+    full = np.zeros((2, nch * CHUNK, Q, rbt * 32), dtype=np.float32)                        # part, bin, q, c
+    for q in range(Q):
+        n = min(hop, win_length - hop * q)
+        full[:, :nbins, q, :n] = table[:, :, left + hop * q:left + hop * q + n]
+    ch, wave, kk, lane = np.ix_(np.arange(nch), np.arange(NW), np.arange(32 * Q), np.arange(64))
+    rb = wave if rbt >= 4 else wave >> 1
+    return np.ascontiguousarray(full[(kk >> 4) & 1, 32 * ch + 2 * (kk & 15) + (lane >> 5), kk >> 5, 32 * rb + (lane & 31)])
+
+
 class LogMel:
     """wav [B, N] (or [N]) fp32 on the GPU -> log-mel [B, T, n_mels] (or [T, n_mels]); with `lengths` also the frames per row.
 

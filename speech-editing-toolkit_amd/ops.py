@@ -630,6 +630,106 @@ def mel_loss_bwd(wav, g_mel, table, basis_t, itable, *, n_fft, hop, n_mels, bin_
     return g_wav
 
 
+def stft_geometries():
+    """The (n_fft, hop, win) triples csrc/stft_loss.hip is compiled for."""
+    L = _lib.lib()
+    n = L.set_stft_geometries(None, 0)
+    buf = (C.c_int32 * (3 * n))()
+    L.set_stft_geometries(buf, n)
+    return [tuple(buf[3 * i:3 * i + 3]) for i in range(n)]
+
+
+_STFT_SIZE_KEYS = ("T", "table", "itable", "part", "mag", "spec", "g_pad", "Ts")
+
+
+def stft_sizes(n_fft, hop, win, B, N):
+    """set_stft_sizes as a dict: T, Ts and the element counts of table, itable, part (doubles), mag, spec, g_pad."""
+    out = (C.c_int64 * 8)()
+    check(_lib.lib().set_stft_sizes(n_fft, hop, win, B, N, out), "set_stft_sizes")
+    return dict(zip(_STFT_SIZE_KEYS, out))
+
+
+def _stft_args(x, y, table, n_fft, hop, win, what):
+    _f(x, "x"), _f(table, "table")
+    if y is not None:
+        _f(y, "y")
+        if y.shape != x.shape:
+            raise ValueError("%s: x and y must be equal [B, N], got %s and %s" % (what, tuple(x.shape), tuple(y.shape)))
+    if x.dim() != 2:
+        raise ValueError("%s: x must be [B, N], got %s" % (what, tuple(x.shape)))
+    B, N = x.shape
+    sz = stft_sizes(n_fft, hop, win, B, N)
+    if table.numel() < sz["table"]:
+        raise ValueError("%s: the table image is smaller than (%d, %d, %d) needs" % (what, n_fft, hop, win))
+    a = _lib.SetStftLossArgs(x=_p(x), y=_p(y), table=_p(table), x_bs=x.stride(0), y_bs=0 if y is None else y.stride(0), B=B, N=N, T=sz["T"],
+                             n_fft=n_fft, hop=hop, win=win, scale=1.0)
+    return a, sz
+
+
+def stft_magnitude(x, table, *, n_fft, hop, win, sentinel=None):
+    """set_stft_magnitude: x [B,N] -> sqrt(max(re^2 + im^2, 1e-7)) [B, T, n_fft/2 + 1] of the centred, reflect-padded STFT."""
+    a, sz = _stft_args(x, None, table, n_fft, hop, win, "stft_magnitude")
+    mag = _buf((x.shape[0], sz["T"], n_fft // 2 + 1), x.device, sentinel)
+    a.mag = _p(mag)
+    check(_lib.lib().set_stft_magnitude(C.byref(a), _stream()), "set_stft_magnitude")
+    return mag
+
+
+def stft_loss_fwd(x, y, table, *, n_fft, hop, win, which=1, keep=False, sentinel=None):
+    """set_stft_loss_fwd: (loss [2] = spectral convergence and log-magnitude loss of one resolution, stats [6] float64 = D, G, count and
+    the three sums, the kept magnitudes of the signal that is not differentiated or None).  `which`: 1 = y is differentiated, 0 = x."""
+    a, sz = _stft_args(x, y, table, n_fft, hop, win, "stft_loss_fwd")
+    dev = x.device
+    loss = _buf((2,), dev, sentinel)
+    stats = torch.empty(6, dtype=torch.float64, device=dev)
+    part = torch.empty(sz["part"], dtype=torch.float64, device=dev)
+    if sentinel is not None:
+        stats.fill_(sentinel), part.fill_(sentinel)
+    mag = _buf((sz["mag"],), dev, sentinel) if keep else None
+    a.loss, a.stats, a.part, a.mag, a.which = _p(loss), _p(stats), _p(part), _p(mag), int(which)
+    check(_lib.lib().set_stft_loss_fwd(C.byref(a), _stream()), "set_stft_loss_fwd")
+    return loss, stats, mag
+
+
+def stft_loss_bwd(x, y, table, itable, *, n_fft, hop, win, which=1, stats=None, u_sc=None, u_mag=None, scale=1.0, mag=None, g_m=None,
+                  g_wav=None, sentinel=None, scratch=None):
+    """set_stft_loss_bwd: the gradient [B,N] of scale (u_sc sc + u_mag mag) with respect to y (which = 1) or x (which = 0), written to a
+    new tensor or ADDED to `g_wav`.  u_sc, u_mag: fp32 device tensors of one element; stats: stft_loss_fwd's; mag: its kept magnitudes
+    (None: the other signal's DFT is computed again).  `g_m` [B,T,bins] replaces the loss's own magnitude gradient.  A dict `scratch`
+    receives the two intermediate buffers (spec, g_pad) for inspection."""
+    a, sz = _stft_args(x, y, table, n_fft, hop, win, "stft_loss_bwd")
+    _f(itable, "itable")
+    B, N = x.shape
+    dev = x.device
+    if itable.numel() < sz["itable"]:
+        raise ValueError("stft_loss_bwd: the inverse table image is smaller than (%d, %d, %d) needs" % (n_fft, hop, win))
+    if g_m is not None:
+        _f(g_m, "g_m")
+        if tuple(g_m.shape) != (B, sz["T"], n_fft // 2 + 1):
+            raise ValueError("stft_loss_bwd: g_m must be [%d, %d, %d], got %s" % (B, sz["T"], n_fft // 2 + 1, tuple(g_m.shape)))
+    else:
+        _f(u_sc, "u_sc"), _f(u_mag, "u_mag")
+        _chk(stats, torch.float64, "stats")
+        if stats is None or u_sc is None or u_mag is None or stats.numel() < 6 or u_sc.numel() != 1 or u_mag.numel() != 1:
+            raise ValueError("stft_loss_bwd: needs stats [6] and one-element u_sc, u_mag (or g_m)")
+    if mag is not None and _f(mag, "mag").numel() < sz["mag"]:
+        raise ValueError("stft_loss_bwd: the kept magnitudes are smaller than the forward writes")
+    accumulate = g_wav is not None
+    if accumulate:
+        _f(g_wav, "g_wav")
+        if tuple(g_wav.shape) != (B, N):
+            raise ValueError("stft_loss_bwd: g_wav must be [%d, %d], got %s" % (B, N, tuple(g_wav.shape)))
+    else:
+        g_wav = _buf((B, N), dev, sentinel)
+    spec, g_pad = _buf((sz["spec"],), dev, sentinel), _buf((sz["g_pad"],), dev, sentinel)
+    a.itable, a.stats, a.u_sc, a.u_mag, a.g_m, a.mag = _p(itable), _p(stats), _p(u_sc), _p(u_mag), _p(g_m), _p(mag)
+    a.spec, a.g_pad, a.g_wav, a.which, a.accumulate, a.scale = _p(spec), _p(g_pad), _p(g_wav), int(which), int(accumulate), float(scale)
+    check(_lib.lib().set_stft_loss_bwd(C.byref(a), _stream()), "set_stft_loss_bwd")
+    if scratch is not None:
+        scratch.update(spec=spec, g_pad=g_pad)
+    return g_wav
+
+
 def _len_arg(lengths, B, name):
     _i(lengths, name)
     if lengths is not None and lengths.shape != (B,):

@@ -10,6 +10,15 @@ generator step always calls backward.  It also makes a second backward (retain_g
 is the three backward launches in a forward under autograd whose loss is never differentiated; torch.no_grad() skips them.
 
 `y` is data: a `y` that requires grad raises instead of silently getting none.  There is no CPU fallback.
+
+Also built: the multi-resolution STFT loss (tasks/vocoder/hifigan.py:46-47 on modules/vocoder/hifigan/stft_loss.py; csrc/stft_loss.hip),
+the other waveform-domain term of the generator step:
+
+    stft_loss = MultiResolutionSTFTLoss()
+    sc, mag = stft_loss(y.squeeze(1), y_.squeeze(1))          # the task's order: the REAL waveform first, the generated one second
+
+differentiable in whichever one of the two arguments requires grad.  Its gradient is computed in backward(), once per resolution, from
+the two upstream scalars combined on the device.
 """
 import torch
 
@@ -111,3 +120,120 @@ def mel_l1_loss(y_hat, y, hparams):
     if fn is None:
         fn = _CACHE[key] = MelSpectrogramLoss({k: hparams[k] for k in melspec._HP_KEYS if k in hparams})
     return fn(y_hat, y)
+
+
+# ---- multi-resolution STFT loss -----------------------------------------------------------------------------------------------------------
+
+class _StftLoss(torch.autograd.Function):
+    """(sc, mag) of `mod`'s resolutions, averaged; backward runs the spectral backward once per resolution with both upstream scalars."""
+
+    @staticmethod
+    def forward(ctx, x, y, mod, sentinel):
+        need = [bool(n) for n in ctx.needs_input_grad[:2]]
+        which = 0 if need[0] else 1
+        tables = mod._tables(x.device)
+        keep = any(need) and not mod.recompute
+        n = len(mod.geometries)
+        res = [ops.stft_loss_fwd(x, y, tables[i][0], n_fft=g[0], hop=g[1], win=g[2], which=which, keep=keep, sentinel=sentinel)
+               for i, g in enumerate(mod.geometries)]
+        # the mean over the resolutions in the constructor's order: ((l0 + l1) + l2) / n, fp32 on the device
+        tot = res[0][0]
+        for r in res[1:]:
+            tot = tot + r[0]
+        if n > 1:
+            tot = tot / n
+        ctx.mod, ctx.which, ctx.sentinel = mod, which, sentinel
+        ctx.stats, ctx.mags = [r[1] for r in res], [r[2] for r in res]
+        ctx.save_for_backward(x, y)
+        return tot[0].reshape(()), tot[1].reshape(())
+
+    @staticmethod
+    def backward(ctx, g_sc, g_mag):
+        x, y = ctx.saved_tensors
+        mod, which = ctx.mod, ctx.which
+        u = [torch.zeros(1, dtype=torch.float32, device=x.device) if g is None else g.reshape(1).contiguous() for g in (g_sc, g_mag)]
+        tables = mod._tables(x.device)
+        g_wav = None
+        for i, g in enumerate(mod.geometries):  # summed in the constructor's order: the first resolution writes, the others add
+            g_wav = ops.stft_loss_bwd(x, y, tables[i][0], tables[i][1], n_fft=g[0], hop=g[1], win=g[2], which=which, stats=ctx.stats[i],
+                                      u_sc=u[0], u_mag=u[1], scale=1.0 / len(mod.geometries), mag=ctx.mags[i], g_wav=g_wav,
+                                      sentinel=ctx.sentinel)
+        return (g_wav, None, None, None) if which == 0 else (None, g_wav, None, None)
+
+
+class MultiResolutionSTFTLoss(torch.nn.Module):
+    """The reference's MultiResolutionSTFTLoss: per resolution sc = ||y_mag - x_mag||_F / ||y_mag||_F and mag = mean |log y_mag - log
+    x_mag| over the whole batch, with mag(s) = sqrt(clamp(re^2 + im^2, min=1e-7)) of torch.stft(center=True, reflect) under the periodic
+    Hann window of win_length; the result is the two means over the resolutions.
+
+    forward(x, y) -> (sc_loss, mag_loss), 0-dim.  x, y: equal fp32 GPU tensors [B, N] or [B, 1, N] with N > max(fft_size) / 2.  The task
+    passes the real waveform as x and the generated one as y; the loss is differentiable in whichever ONE of them requires grad.
+    `recompute=True` computes the other signal's spectrum again in backward instead of keeping its magnitudes from the forward.
+    `sentinel` fills every output and scratch buffer before its kernel runs (the tests pass NaN)."""
+
+    def __init__(self, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240), window="hann_window",
+                 recompute=False):
+        super().__init__()
+        if not len(fft_sizes) == len(hop_sizes) == len(win_lengths) or len(fft_sizes) == 0:
+            raise ValueError("fft_sizes, hop_sizes and win_lengths must be equally long and not empty")
+        if window != "hann_window":
+            raise ValueError("the STFT loss is built for window='hann_window', got %r" % (window,))
+        self.geometries = [tuple(int(v) for v in g) for g in zip(fft_sizes, hop_sizes, win_lengths)]
+        built = ops.stft_geometries()
+        for g in self.geometries:
+            if g not in built:
+                raise ValueError("the STFT loss has no kernels for (fft_size, hop, win_length) = %s; compiled geometries: %s" % (g, built))
+        self.recompute = bool(recompute)
+        self._images = ops.CacheSlot()  # per resolution (DFT table image, inverse table image) on the device last used
+
+    def _build_images(self, device):
+        out = []
+        for n_fft, hop, win in self.geometries:
+            table = melspec.dft_table(n_fft, win, 0, n_fft // 2 + 1)
+            out.append((torch.from_numpy(melspec.pack_stft_table(table, win)).to(device),
+                        torch.from_numpy(melspec.pack_stft_idft_table(table, hop, win)).to(device)))
+        return out
+
+    def _tables(self, device):
+        return self._images.get((device,), lambda old: self._build_images(device))
+
+    def _check(self, x, y):
+        for t, name in ((x, "x"), (y, "y")):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError("%s must live on the GPU: the STFT loss has no CPU fallback" % name)
+            if t.dtype != torch.float32:
+                raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+        if x.shape != y.shape or x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[1] != 1):
+            raise ValueError("x and y must be equal [B, N] or [B, 1, N], got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+        pad = max(g[0] for g in self.geometries) // 2
+        if x.shape[-1] <= pad:
+            raise ValueError("reflect padding of %d needs more than %d samples, got %d" % (pad, pad, x.shape[-1]))
+        if torch.is_grad_enabled() and x.requires_grad and y.requires_grad:
+            raise ValueError("the STFT loss is differentiable in one of its arguments; both require grad (detach the data)")
+
+    def forward(self, x, y, sentinel=None):
+        self._check(x, y)
+        B, N = x.shape[0], x.shape[-1]
+        return _StftLoss.apply(x.reshape(B, N).contiguous(), y.reshape(B, N).contiguous(), self, sentinel)
+
+
+class STFTLoss(MultiResolutionSTFTLoss):
+    """One resolution, the reference's signature: forward(x, y) -> (sc_loss, mag_loss)."""
+
+    def __init__(self, fft_size=1024, shift_size=120, win_length=600, window="hann_window", recompute=False):
+        super().__init__([fft_size], [shift_size], [win_length], window, recompute)
+
+
+_STFT = {}  # (fft_size, hop_size, win_length) -> STFTLoss, for stft_magnitude's table images
+
+
+def stft_magnitude(x, fft_size, hop_size, win_length, sentinel=None):
+    """The reference's stft() on the GPU: x [B, N] fp32 -> sqrt(clamp(re^2 + im^2, min=1e-7)) [B, 1 + N // hop_size, fft_size/2 + 1]."""
+    key = (int(fft_size), int(hop_size), int(win_length))
+    fn = _STFT.get(key)
+    if fn is None:
+        fn = _STFT[key] = STFTLoss(*key)
+    fn._check(x, x.detach())
+    if x.dim() != 2:
+        raise ValueError("stft_magnitude takes [B, N], got %s" % (tuple(x.shape),))
+    return ops.stft_magnitude(x.detach().contiguous(), fn._tables(x.device)[0][0], n_fft=key[0], hop=key[1], win=key[2], sentinel=sentinel)
