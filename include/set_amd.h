@@ -339,6 +339,11 @@ typedef struct SetDiffnetStackArgs {
      * rounding, not bit for bit.  SET_AMD_X3=0 disables it, =2 forces it at any size. */
     const void *wx3_all;
     int32_t x3_mode;
+    /* != 0: xa, xb and skip are in the channel-quad layout on input and output -- element (b, c, t) at float
+     * b*256*T + ((c >> 2)*T + t)*4 + (c & 3), 16-byte aligned -- so that the kernel's accesses are 16 bytes wide.  Only the Winograd
+     * form of the two-piece fp16 split-operand kernel (x3_mode 2, dilation_cycle_length 1, even T, 64- or 96-frame tiles) honours it;
+     * with any other plan the call returns SET_E_INVALID.  0 (the default): [B][256][T]. */
+    int32_t xs_q4;
 } SetDiffnetStackArgs;
 int set_diffnet_stack(const SetDiffnetStackArgs *args, void *stream);
 int64_t set_sizeof_diffnet_stack_args(void);
@@ -462,6 +467,11 @@ typedef struct SetDiffLoopArgs {
      * (set_diffnet_layers_fwd_bf16); NULL: one launch per layer.  SET_AMD_BF16_FUSE=n overrides the group size (1 = per layer). */
     float *bf16_ws;
     int64_t bf16_ws_floats;
+    /* != 0: the library may keep ws_x0, ws_x1 and ws_skip in the channel-quad layout of SetDiffnetStackArgs.xs_q4 (they are scratch: only
+     * their layout changes, x does not).  It does so for a chain whose layer stack runs the Winograd split-operand kernel and whose step
+     * boundary is the fused two-piece fp16 one; every other chain keeps [B][256][T].  The workspaces must then be 16-byte aligned.
+     * SET_AMD_WS_Q4=0 in the environment keeps the plain layout.  0 (the default): plain. */
+    int32_t ws_q4;
 } SetDiffLoopArgs;
 int set_diffusion_loop(const SetDiffLoopArgs *args, void *stream);
 

@@ -82,6 +82,7 @@ class SetDiffLoopArgs(C.Structure):
         ("err_flag", C.c_void_p),
         ("cond", C.c_void_p), ("img16_all", C.c_void_p), ("b_cond_all", C.c_void_p),
         ("bf16_ws", C.c_void_p), ("bf16_ws_floats", C.c_int64),
+        ("ws_q4", C.c_int32),
     ]
 
 
@@ -96,7 +97,7 @@ class SetDiffnetStackArgs(C.Structure):
         ("x_all", C.c_void_p), ("save_y", C.c_void_p), ("save_z", C.c_void_p),
         ("err_flag", C.c_void_p),
         ("w1s_all", C.c_void_p), ("w2s_all", C.c_void_p), ("z_ws", C.c_void_p), ("wx3_all", C.c_void_p),
-        ("x3_mode", C.c_int32),
+        ("x3_mode", C.c_int32), ("xs_q4", C.c_int32),
     ]
 
 

@@ -189,6 +189,9 @@ struct BoundaryX2Args {
     int32_t *err_flag;
 };
 
+// Q4: skip and xin_next in the channel-quad layout (common.h, q4f_index) -- phase 1 reads 16 quads of 16 bytes per lane instead of 64 floats,
+// phase 5 stores its four consecutive accumulator registers as one quad.  Same values, same arithmetic.
+template <bool Q4>
 __global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2Args ax) {
     const BoundaryArgs &a = ax.g;
     extern __shared__ __attribute__((aligned(16))) unsigned char bl[];  // [2][64][BX_XR]: s -> h pieces; x0 / x' (fp32) and x' pieces overlay
@@ -203,12 +206,21 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2A
     {
         const int f = lane, cg = w;
         const rsrc_t rs = make_rsrc(a.skip + (int64_t)b * DC * T);
-        const unsigned vo = 4u * (unsigned)min(t0 + f, T - 1);
+        const unsigned vo = (Q4 ? 16u : 4u) * (unsigned)min(t0 + f, T - 1);
         const bool tv = t0 + f < T;
         for (int c0 = 0; c0 < 64; c0 += 16) {
             float v[16];
+            if (Q4) {
 #pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = buf_load(rs, vo, (unsigned)(64 * cg + c0 + u) * T4);
+                for (int j = 0; j < 4; ++j) {
+                    const f32x4 q = buf_load4(rs, vo, (unsigned)(64 * cg + c0 + 4 * j) * T4);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[4 * j + e] = q[e];
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < 16; ++u) v[u] = buf_load(rs, vo, (unsigned)(64 * cg + c0 + u) * T4);
+            }
 #pragma unroll
             for (int q8 = 0; q8 < 2; ++q8) {
                 u32x4_t u0, u1;
@@ -371,14 +383,25 @@ __global__ void __launch_bounds__(256, 2) diffnet_boundary_x2_kernel(BoundaryX2A
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
             if (t0 + 32 * cb + l31 < T) {
-                const unsigned so = 4u * (unsigned)(4 * half * T + t0 + 32 * cb + l31);
+                const unsigned so = Q4 ? 16u * (unsigned)(half * T + t0 + 32 * cb + l31) : 4u * (unsigned)(4 * half * T + t0 + 32 * cb + l31);
 #pragma unroll
-                for (int i = 0; i < 2; ++i)
+                for (int i = 0; i < 2; ++i) {
+                    if (Q4) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {  // registers 4 j .. 4 j + 3: rows 32 (2 w + i) + 8 j + 4 half + 0 .. 3 = one quad
+                            f32x4 q;
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) q[e] = fmaxf(acc[i][cb][4 * j + e] * inv + bin[i][4 * j + e], 0.0f);
+                            buf_store4_padded<false>(q, ro, so, (unsigned)(32 * (2 * w + i) + 8 * j) * T4);
+                        }
+                        continue;
+                    }
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int ur = 32 * (2 * w + i) + urow16(r);
                         buf_store(fmaxf(acc[i][cb][r] * inv + bin[i][r], 0.0f), ro, so, 4u * (unsigned)ur * (unsigned)T);
                     }
+                }
             }
         }
     }
@@ -390,10 +413,33 @@ bool boundary_fusable(const SetDiffLoopArgs &a) {
     return a.T % 4 == 0 && a.M <= 96 && a.M >= 2 && ((a.M + 15) / 16 * 16 / 2) % 8 == 0;
 }
 
+// plain [256][T] rows -> channel quads: thread (utterance, quad, frame) reads its four channels (coalesced over frames), writes 16 bytes
+__global__ void __launch_bounds__(256) relayout_q4_kernel(const float *src, float *dst, int T, int64_t n_quads) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (b * 64 + quad) * T + t
+    if (i >= n_quads) return;
+    const int64_t bq = i / T;
+    const int t = (int)(i - bq * T);
+    const float *p = src + bq * 4 * T + t;
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = p[(int64_t)e * T];
+    *reinterpret_cast<f32x4 *>(dst + 4 * i) = v;
+}
+
+int launch_relayout_q4(const float *src, float *dst, int Bg, int T, hipStream_t s) {
+    const int64_t n_quads = (int64_t)Bg * (DC / 4) * T;
+    SET_REQUIRE((n_quads + 255) / 256 < ((int64_t)1 << 31), "set_diffusion_loop(relayout)");
+    hipLaunchKernelGGL(relayout_q4_kernel, dim3((unsigned)((n_quads + 255) / 256)), dim3(256), 0, s, src, dst, T, n_quads);
+    return set_check_launch("set_diffusion_loop(relayout)");
+}
+
 int launch_boundary(const SetDiffLoopArgs &a, int Bg, const float *skip, float *x, const float *eps, int sid, uint64_t quad_offset,
-                    float *xin_next, bool x2, hipStream_t s) {
+                    float *xin_next, bool x2, bool q4, hipStream_t s) {
     static SetDeviceOnce lds_once;
-    if (int rc = set_lds_optin(lds_once, 80 * 1024, "boundary(attr)", diffnet_boundary_kernel, diffnet_boundary_x2_kernel)) return rc;
+    if (int rc = set_lds_optin(lds_once, 80 * 1024, "boundary(attr)", diffnet_boundary_kernel, diffnet_boundary_x2_kernel<false>,
+                               diffnet_boundary_x2_kernel<true>))
+        return rc;
+    SET_REQUIRE(!q4 || x2, "set_diffusion_loop(boundary: the channel-quad layout needs the two-piece fp16 boundary)");
     BoundaryArgs g = {};
     g.skip = skip; g.x = x; g.eps = eps; g.coef4 = a.coef4 + 4 * sid;
     g.w_skip_p = a.w_skip_p; g.b_skip = a.b_skip; g.w_outp_p = a.w_outp_p; g.b_outp = a.b_outp;
@@ -407,7 +453,10 @@ int launch_boundary(const SetDiffLoopArgs &a, int Bg, const float *skip, float *
         gx.w_outp_x2 = reinterpret_cast<const unsigned short *>(a.w_outp_x2);
         gx.w_in_x2 = reinterpret_cast<const unsigned short *>(a.w_in_x2);
         gx.err_flag = a.err_flag;
-        hipLaunchKernelGGL(diffnet_boundary_x2_kernel, dim3((a.T + 63) / 64, Bg), dim3(256), (size_t)2 * BX_PIECE, s, gx);
+        if (q4)
+            hipLaunchKernelGGL(diffnet_boundary_x2_kernel<true>, dim3((a.T + 63) / 64, Bg), dim3(256), (size_t)2 * BX_PIECE, s, gx);
+        else
+            hipLaunchKernelGGL(diffnet_boundary_x2_kernel<false>, dim3((a.T + 63) / 64, Bg), dim3(256), (size_t)2 * BX_PIECE, s, gx);
     } else {
         hipLaunchKernelGGL(diffnet_boundary_kernel, dim3((a.T + 63) / 64, Bg), dim3(256), (size_t)DC * BD_LD * sizeof(float), s, g);
     }

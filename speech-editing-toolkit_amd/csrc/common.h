@@ -208,6 +208,20 @@ __device__ __forceinline__ void buf_atomic_add(float v, rsrc_t r, unsigned voff,
 __device__ __forceinline__ void buf_store_agent(float v, rsrc_t r, unsigned voff, unsigned soff) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)voff, (int)soff, 16);
 }
+// ---- the channel-quad ("q4") layout of an fp32 [256][T] buffer: the x ping-pong and skip workspaces of the reverse loop (DESIGN 3.6 with fp32
+// elements).  Element (c, t) is float q4f_index(c, t, T) of its utterance: the four channels of a quad at one frame are 16 contiguous bytes, which
+// is what four consecutive accumulator registers of a 32x32 block hold (urow16).  Byte offset = (wave-uniform) 4 (c & ~3) T + (per-lane) 16 t.
+__host__ __device__ inline int64_t q4f_index(int c, int t, int T) { return ((int64_t)(c >> 2) * T + t) * 4 + (c & 3); }
+// 16-byte store with its row offset in an SGPR, plain or agent-scope write-through (sc1, as buf_store_agent).  gfx950 needs a wait state between such
+// a store and a VALU instruction that rewrites its data registers, and the compiler does not insert it (tests/test_isa_schedule.py):
+// the pad follows the store, and the scheduling barriers keep it there.
+template <bool AGENT>
+__device__ __forceinline__ void buf_store4_padded(f32x4 v, rsrc_t r, unsigned voff, unsigned soff) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), r, (int)voff, (int)soff, AGENT ? 16 : 0);
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("s_nop 1" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
 
 // two fp32 values -> their two-piece fp16 splittings (a0 + a1 = a to 22 significand bits), each piece pair packed into one dword with the
 // first value in the low half: v_cvt_pk_f16_f32, two back-conversions, v_pk_add_f32, v_cvt_pk_f16_f32 -- five instructions where two

@@ -36,6 +36,8 @@ int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, const StackPlan &p
 // may the boundary of this loop run as one launch?  (reads SET_AMD_FUSED_BOUNDARY)
 bool boundary_fusable(const SetDiffLoopArgs &a);
 // skip sum of Bg utterances -> x_{t-1} in place (eps explicit or Philox at quad_offset) -> next step's stack input (xin_next, NULL after
-// the last step); x2: on two-piece fp16 operands
+// the last step); x2: on two-piece fp16 operands; q4 (x2 only): skip and xin_next in the channel-quad layout (common.h, q4f_index)
 int launch_boundary(const SetDiffLoopArgs &a, int Bg, const float *skip, float *x, const float *eps, int sid, uint64_t quad_offset,
-                    float *xin_next, bool x2, hipStream_t s);
+                    float *xin_next, bool x2, bool q4, hipStream_t s);
+// src [Bg][256][T] -> dst in the channel-quad layout: the first step's input projection, once per loop
+int launch_relayout_q4(const float *src, float *dst, int Bg, int T, hipStream_t s);

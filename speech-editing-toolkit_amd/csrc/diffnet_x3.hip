@@ -758,8 +758,10 @@ __device__ __forceinline__ void x3v_init(const X3Tile &a, f32x4 (&PQ)[2][4][NB])
 // one pair of planes of the V tile: PH = 0: d1 + d2 | d2 - d1 (U1, U2);  PH = 1: d0 - d2 | d1 - d3 (U0, -U3).  lane (l15, cs): pair l15 of every
 // column block, 8 channels 32 w + 8 cs ..; returns the largest magnitude staged (range check of the fp16 pieces)
 // (two halves, so that the second pass's loads can be issued in front of the barrier that retires the first pair of planes)
-template <int NB, int PH>
-__device__ __forceinline__ void x3v_stage_load(const X3Tile &a, int w, int lane, f32x2 (&x12)[NB][8], float (&xh)[NB][8]) {
+// xs[nb][2 k + f]: channel ch0 + k at frame t + f; xh[nb][k]: the halo frame.  Q4 (the channel-quad layout of common.h, q4f_index): a lane's 8
+// channels are two quads, and frames t, t + 1 of a quad are 32 contiguous bytes -- 4 16-byte loads per column block instead of 8 8-byte ones
+template <int NB, int PH, bool Q4>
+__device__ __forceinline__ void x3v_stage_load(const X3Tile &a, int w, int lane, float (&xs)[NB][16], float (&xh)[NB][8]) {
     const int l15 = lane & 15, cs = lane >> 4;
     const int ch0 = 32 * w + 8 * cs;
     const int T = a.T;
@@ -770,11 +772,36 @@ __device__ __forceinline__ void x3v_stage_load(const X3Tile &a, int w, int lane,
         const X3Col c = x3_col(a, nb);
         const rsrc_t rx = make_rsrc(a.xin + (int64_t)c.b * XC * T);
         const int t = c.t0 + 2 * l15;  // frames t, t + 1 (T even: both inside or both outside)
+        const int th = l15 == 0 ? c.t0 - 1 : c.t0 + 32;  // halo frame of the block's end lanes
+        if (Q4) {
+            const unsigned vox = 16u * (unsigned)(2 * cs * T + min(t, T - 2)), soff = (unsigned)(32 * w) * T4;
+#pragma unroll
+            for (int q = 0; q < 2; ++q)
+#pragma unroll
+                for (int f = 0; f < 2; ++f) {
+                    const f32x4 v = buf_load4(rx, vox + 16u * (unsigned)f, soff + (unsigned)(4 * q) * T4);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) xs[nb][2 * (4 * q + i) + f] = v[i];
+                }
+            if (PH == 1 && edge) {
+                const unsigned voh = 16u * (unsigned)(2 * cs * T + min(max(th, 0), T - 1));
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const f32x4 v = buf_load4(rx, voh, soff + (unsigned)(4 * q) * T4);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) xh[nb][4 * q + i] = v[i];
+                }
+            }
+            continue;
+        }
         const unsigned vox = 4u * (unsigned)min(t, T - 2) + (unsigned)ch0 * T4;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) x12[nb][k] = buf_load2(rx, vox, (unsigned)k * T4);
+        for (int k = 0; k < 8; ++k) {
+            const f32x2 v = buf_load2(rx, vox, (unsigned)k * T4);
+            xs[nb][2 * k] = v[0];
+            xs[nb][2 * k + 1] = v[1];
+        }
         if (PH == 1) {
-            const int th = l15 == 0 ? c.t0 - 1 : c.t0 + 32;  // halo frame of the block's end lanes
             const unsigned voh = 4u * (unsigned)min(max(th, 0), T - 1) + (unsigned)ch0 * T4;
             if (edge) {
 #pragma unroll
@@ -784,7 +811,7 @@ __device__ __forceinline__ void x3v_stage_load(const X3Tile &a, int w, int lane,
     }
 }
 template <int NB, int PH>
-__device__ __forceinline__ float x3v_stage_store(const X3Tile &a, unsigned char *lds, const float *dsh, int w, int lane, const f32x2 (&x12)[NB][8],
+__device__ __forceinline__ float x3v_stage_store(const X3Tile &a, unsigned char *lds, const float *dsh, int w, int lane, const float (&xs)[NB][16],
                                                  const float (&xh)[NB][8]) {
     typedef SplitF16x2 S;
     const int l15 = lane & 15, cs = lane >> 4;
@@ -807,7 +834,7 @@ __device__ __forceinline__ float x3v_stage_store(const X3Tile &a, unsigned char 
             for (int h = 0; h < 2; ++h) {
                 const int e = 2 * e2 + h;
                 const float ds = e < 4 ? dA[e & 3] : dB[e & 3];
-                const float d1 = v12 ? x12[nb][e][0] + ds : 0.0f, d2 = v12 ? x12[nb][e][1] + ds : 0.0f;
+                const float d1 = v12 ? xs[nb][2 * e] + ds : 0.0f, d2 = v12 ? xs[nb][2 * e + 1] + ds : 0.0f;
                 if (PH == 0) {
                     V[0][h] = d1 + d2;
                     V[1][h] = d2 - d1;
@@ -871,7 +898,42 @@ __device__ __forceinline__ void x3v_plane(f32x4 (&acc)[4][NB], u32x4_t (&A)[PFV]
     }
 }
 
-template <int NB>
+// the 16 accumulator rows of a lane (rows 32 w + urow16(r) + 4 half, one frame) from / to a [256][T] buffer; the lane's (half, frame) part of the
+// address is in voff (plain: 4 (4 half T + t), Q4: 16 (half T + t)), the rest is wave-uniform
+template <bool Q4, bool NT>
+__device__ __forceinline__ void x3v_rows_load(float (&v)[16], rsrc_t r, unsigned voff, int w, unsigned T4) {
+    if (Q4) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const f32x4 q = NT ? buf_load4_stream(r, voff, (unsigned)(32 * w + 8 * j) * T4) : buf_load4(r, voff, (unsigned)(32 * w + 8 * j) * T4);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[4 * j + i] = q[i];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) v[k] = NT ? buf_load_nt(r, voff, (unsigned)(32 * w + urow16(k)) * T4) : buf_load(r, voff, (unsigned)(32 * w + urow16(k)) * T4);
+    }
+}
+template <bool Q4>
+__device__ __forceinline__ void x3v_rows_store(const float (&v)[16], rsrc_t r, unsigned voff, int w, unsigned T4) {
+    if (Q4) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            f32x4 q;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) q[i] = v[4 * j + i];
+            buf_store4_padded<true>(q, r, voff, (unsigned)(32 * w + 8 * j) * T4);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) buf_store_agent(v[k], r, voff, (unsigned)(32 * w + urow16(k)) * T4);
+    }
+}
+
+// Q4: xin, xout and skp are in the channel-quad layout (common.h, q4f_index).  Accumulator registers 4 j .. 4 j + 3 of lane (l31, half) are
+// channels 32 w + 8 j + 4 half + 0 .. 3 of one frame (urow16) = quad 8 w + 2 j + half: one 16-byte access where the plain layout takes four of
+// 4 bytes.  Same values through the same arithmetic; only addresses differ.
+template <int NB, bool Q4>
 __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB], unsigned char *lds, PhaseProbe<11> &pp, PhaseTimeline<32> &tl) {
     // phase p: a sum of the probe build and stamp 8 + p of the timeline build, which has stamps of its own besides (tl.mark alone)
     pp.lap(0); tl.mark(8);
@@ -897,10 +959,10 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
     const unsigned abase = (unsigned)((x_n1<S>() + x_n2<S>() + 8) * 2) + (unsigned)(w * X_KSV * 4 * 2 * 1024);
     const unsigned boff = (unsigned)(l15 * XRV + kg * 16);
     u32x4_t A[PFV][4][2];
-    f32x2 x12[NB][8];
+    float xs[NB][16];
     float xh[NB][8];
-    x3v_stage_load<NB, 0>(a, w, lane, x12, xh);
-    float amax = x3v_stage_store<NB, 0>(a, lds, dsh, w, lane, x12, xh);
+    x3v_stage_load<NB, 0, Q4>(a, w, lane, xs, xh);
+    float amax = x3v_stage_store<NB, 0>(a, lds, dsh, w, lane, xs, xh);
 #pragma unroll
     for (int p = 0; p < PFV; ++p)
 #pragma unroll
@@ -913,7 +975,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
     x3v_plane<NB, PFV>(PQ[0], A, rw, lane16, abase, 0, lds, boff);
     x3v_plane<NB, PFV>(PQ[1], A, rw, lane16, abase, 1, lds + xv_plane<NB>(), boff);
     pp.lap(2); tl.mark(10);
-    x3v_stage_load<NB, 1>(a, w, lane, x12, xh);  // second pair's x: in flight through the E / O combine and the barrier
+    x3v_stage_load<NB, 1, Q4>(a, w, lane, xs, xh);  // second pair's x: in flight through the E / O combine and the barrier
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb)
@@ -928,7 +990,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
     __syncthreads();  // every wave is done reading the first pair of planes
     tl.mark(21);
     // ---- second pair
-    amax = fmaxf(amax, x3v_stage_store<NB, 1>(a, lds, dsh, w, lane, x12, xh));
+    amax = fmaxf(amax, x3v_stage_store<NB, 1>(a, lds, dsh, w, lane, xs, xh));
     if (!(amax < 32768.0f) && a.err_flag) __hip_atomic_store(a.err_flag, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int p = 0; p < PFV; ++p)
@@ -951,15 +1013,14 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
         const X3Col c = x3_col(a, cb);
         const int t = c.t0 + l31;
         tv[cb] = c.ok && t < T;
-        vo4[cb] = 4u * (unsigned)(4 * half * T + min(t, T - 1));
+        vo4[cb] = Q4 ? 16u * (unsigned)(half * T + min(t, T - 1)) : 4u * (unsigned)(4 * half * T + min(t, T - 1));
         ub[cb] = (int64_t)c.b * XC * T;
     }
     float xres[NB][16];
 #pragma unroll
     for (int cb = 0; cb < NB; ++cb) {
         const rsrc_t rx = make_rsrc(a.xin + ub[cb]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) xres[cb][r] = buf_load(rx, vo4[cb], (unsigned)(32 * w + urow16(r)) * T4);
+        x3v_rows_load<Q4, false>(xres[cb], rx, vo4[cb], w, T4);
     }
     __syncthreads();  // every wave is done reading the V tile: the z tile overlays it (row = frame of the tile)
     tl.mark(23);
@@ -1021,16 +1082,17 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
 #pragma unroll
         for (int cb = 0; cb < NB; ++cb) {
             const rsrc_t rsk = make_rsrc(a.skp + ub[cb]);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sk[cb][r] = buf_load_nt(rsk, vo4[cb], (unsigned)(32 * w + urow16(r)) * T4);
+            x3v_rows_load<Q4, true>(sk[cb], rsk, vo4[cb], w, T4);
         }
     }
 #pragma unroll
     for (int cb = 0; cb < NB; ++cb) {
         if (tv[cb]) {
             const rsrc_t rxo = make_rsrc(a.xout + ub[cb]);
+            float o[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r) buf_store_agent((acc[0][0][cb][r] * is2) * RSQRT2, rxo, vo4[cb], (unsigned)(32 * w + urow16(r)) * T4);
+            for (int r = 0; r < 16; ++r) o[r] = (acc[0][0][cb][r] * is2) * RSQRT2;
+            x3v_rows_store<Q4>(o, rxo, vo4[cb], w, T4);
         }
     }
     tl.mark(25);
@@ -1038,9 +1100,10 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
     for (int cb = 0; cb < NB; ++cb) {
         if (tv[cb]) {
             const rsrc_t rsk = make_rsrc(a.skp + ub[cb]);
+            float o[16];
 #pragma unroll
-            for (int r = 0; r < 16; ++r)
-                buf_store_agent(first ? acc[0][1][cb][r] * is2 : acc[0][1][cb][r] * is2 + sk[cb][r], rsk, vo4[cb], (unsigned)(32 * w + urow16(r)) * T4);
+            for (int r = 0; r < 16; ++r) o[r] = first ? acc[0][1][cb][r] * is2 : acc[0][1][cb][r] * is2 + sk[cb][r];
+            x3v_rows_store<Q4>(o, rsk, vo4[cb], w, T4);
         }
     }
     pp.lap(10); tl.mark(18);
@@ -1050,7 +1113,7 @@ __device__ __forceinline__ void x3v_main(const X3Tile &a, f32x4 (&PQ)[2][4][NB],
 #ifndef X3V_TL_TASK
 #define X3V_TL_TASK 10  // timeline build: the task of every block whose stamps are stored
 #endif
-template <int NB>
+template <int NB, bool Q4>
 __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetStackArgs a, int ntiles, int ntasks, int fault_tile) {
     typedef SplitF16x2 S;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -1125,7 +1188,7 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
         }
         const int n_next = __builtin_amdgcn_readfirstlane(s_task[0]);
         tl.mark(4);
-        x3v_main<NB>(lt, PQ, lds, pp, tl);
+        x3v_main<NB, Q4>(lt, PQ, lds, pp, tl);
 #if SET_PHASE_PROBE == 2
         // timeline of this block's X3V_TL_TASK-th task, waves 0 and 7: row (2 block + wave / 7) of 32 dwords = ticks since the task's first stamp
         // (slot 5: the task number, 6: 1 if the dependency wait had to spin)
@@ -1152,21 +1215,23 @@ __global__ void __launch_bounds__(512, 1) diffnet_stack_x3v_kernel(SetDiffnetSta
     pp.flush(g_x3_phase_buf);
 }
 
-template <int NB>
+template <int NB, bool Q4>
 int launch_x3v(const SetDiffnetStackArgs &a, int n_cu, hipStream_t s) {
     static SetDeviceOnce lds_once;
-    if (int rc = set_lds_optin(lds_once, 160 * 1024, "set_diffnet_stack(x3v attr)", diffnet_stack_x3v_kernel<NB>)) return rc;
+    if (int rc = set_lds_optin(lds_once, 160 * 1024, "set_diffnet_stack(x3v attr)", diffnet_stack_x3v_kernel<NB, Q4>)) return rc;
     const int Q = a.B * ((a.T + 31) / 32);
     const int ntiles = (Q + NB - 1) / NB;
     const int64_t ntasks64 = (int64_t)ntiles * a.L;
     SET_REQUIRE(ntasks64 < (1ll << 30), "set_diffnet_stack(task count)");
     SET_REQUIRE((int64_t)2 * XC * a.T * 4 < ((int64_t)1 << 31), "set_diffnet_stack(split-operand kernel: T too large)");
     SET_REQUIRE(a.dilation_cycle_length == 1 && a.T % 2 == 0, "set_diffnet_stack(x3v: dilation 1 and even T only)");
+    SET_REQUIRE(!Q4 || ((reinterpret_cast<uintptr_t>(a.xa) | reinterpret_cast<uintptr_t>(a.xb) | reinterpret_cast<uintptr_t>(a.skip)) & 15) == 0,
+                "set_diffnet_stack(xs_q4: xa, xb and skip must be 16-byte aligned)");
     const size_t ldsz = (size_t)xv_tile<NB>() + NB * XC * sizeof(float) + 16;
     SET_HIP(set_zero_async(a.sync_ws, stack_sync_words(SQ_QUEUE, ntiles) * sizeof(int32_t), s), "set_diffnet_stack(memset)");
     // the cap for 64-frame tiles only (the rule of the earlier forms: workers beyond 0.8 tile chains mostly wait)
     const int grid = stack_grid(n_cu, ntiles, ntasks64, NB == 2, 0);
-    hipLaunchKernelGGL(diffnet_stack_x3v_kernel<NB>, dim3(grid), dim3(512), ldsz, s, a, ntiles, (int)ntasks64, stack_fault_tile());
+    hipLaunchKernelGGL((diffnet_stack_x3v_kernel<NB, Q4>), dim3(grid), dim3(512), ldsz, s, a, ntiles, (int)ntasks64, stack_fault_tile());
     return set_check_launch("set_diffnet_stack");
 }
 
@@ -1522,7 +1587,9 @@ extern "C" int set_pack_diffnet_layer_x3(const float *w_dil, const float *w_out,
 //   variant from the library.  The NU template parameter of the kernel stays for tools/build_exp.sh experiments.)
 //   round 6: Winograd F(2,3) form of GEMM 1 on 64- / 96-frame tiles (two-piece fp16, dilation 1, even T) -- see diffnet_stack_x3v_kernel
 int set_launch_diffnet_stack_x3(const SetDiffnetStackArgs &a, const StackPlan &p, hipStream_t s) {
-    if (p.x3_wino) return p.x3_ncb == 3 ? launch_x3v<3>(a, p.n_cu, s) : launch_x3v<2>(a, p.n_cu, s);
+    // xs_q4 (xa, xb and skip in the channel-quad layout): the Winograd form only; stack_launch refuses it on every other plan
+    if (p.x3_wino && a.xs_q4) return p.x3_ncb == 3 ? launch_x3v<3, true>(a, p.n_cu, s) : launch_x3v<2, true>(a, p.n_cu, s);
+    if (p.x3_wino) return p.x3_ncb == 3 ? launch_x3v<3, false>(a, p.n_cu, s) : launch_x3v<2, false>(a, p.n_cu, s);
     if (p.family == STACK_X3_F16)
         return p.x3_ncb == 1 ? launch_x3<SplitF16x2, 1, 1>(a, p.n_cu, s) : launch_x3<SplitF16x2, 1, 2>(a, p.n_cu, s);
     return p.x3_ncb == 1 ? launch_x3<SplitBf16x3, 1, 1>(a, p.n_cu, s) : launch_x3<SplitBf16x3, 1, 2>(a, p.n_cu, s);

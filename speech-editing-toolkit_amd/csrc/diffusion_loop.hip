@@ -108,6 +108,7 @@ int stack_validate(const SetDiffnetStackArgs &a) {
 }
 
 int stack_launch(const SetDiffnetStackArgs &a, const StackPlan &p, hipStream_t s) {
+    SET_REQUIRE(!a.xs_q4 || p.x3_wino, "set_diffnet_stack(xs_q4: only the Winograd split-operand kernel reads the channel-quad layout)");
     if (p.family >= STACK_X3_BF16) return set_launch_diffnet_stack_x3(a, p, s);
     if (p.split_x2) return set_launch_diffnet_stack_split_x2(a, p, s);
     return set_launch_diffnet_stack_f32(a, p, s);
@@ -166,6 +167,8 @@ struct StepPlan {
     int fuse;             // STEP_BF16_GROUPS: layers per launch
     bool fused_boundary;  // the step boundary (and the next step's in-projection) as one launch
     bool boundary_x2;     // ... on two-piece fp16 operands
+    bool ws_q4;           // ws_x0, ws_x1 and ws_skip in the channel-quad layout (common.h, q4f_index): STEP_STACK on the Winograd split-operand
+                          // kernel between fused two-piece fp16 boundaries, the only kernels that read it
     StackPlan stack;      // STEP_STACK
 };
 
@@ -225,6 +228,12 @@ int plan_steps(Chain &c, int g) {
     }
     int v = 0;
     if (env_int("SET_AMD_BOUNDARY_X2", &v)) p.boundary_x2 = p.boundary_x2 && v != 0;
+    // the workspace layout, decided here once for the chain.  SET_AMD_WS_Q4=0 keeps the plain layout (the A/B switch)
+    int q4_env = 1;
+    (void)env_int("SET_AMD_WS_Q4", &q4_env);
+    const bool aligned16 = ((reinterpret_cast<uintptr_t>(c.ws_x0) | reinterpret_cast<uintptr_t>(c.ws_x1) | reinterpret_cast<uintptr_t>(c.ws_skip)) & 15) == 0;
+    p.ws_q4 = a.ws_q4 != 0 && q4_env != 0 && p.body == STEP_STACK && p.stack.x3_wino && p.fused_boundary && p.boundary_x2 && aligned16;
+    c.stack.xs_q4 = p.ws_q4 ? 1 : 0;
     return SET_OK;
 }
 
@@ -315,9 +324,11 @@ int diffusion_chain(const SetDiffLoopArgs &a, int g, int b0, int Bg, hipStream_t
         // input projection + ReLU (diffnet.py:118-120); with the fused boundary it is part of the previous step's
         // boundary launch
         if (!p.fused_boundary || k == 0) {
-            SetConv1dArgs cin = conv1x1_args(c.x, a.w_in_p, a.b_in, c.ws_x0, Bg, M, DC, T);
+            // (channel-quad workspaces: projected into ws_x1, which layer 0 overwrites, and re-laid into ws_x0 -- once per loop)
+            SetConv1dArgs cin = conv1x1_args(c.x, a.w_in_p, a.b_in, p.ws_q4 ? c.ws_x1 : c.ws_x0, Bg, M, DC, T);
             cin.act = SET_ACT_RELU;
             rc = set_conv1d(&cin, s);
+            if (rc == SET_OK && p.ws_q4) rc = launch_relayout_q4(c.ws_x1, c.ws_x0, Bg, T, s);
             if (rc != SET_OK) break;
         }
         if (ev) (void)hipEventRecord(ev[2 * k], s);
@@ -334,7 +345,7 @@ int diffusion_chain(const SetDiffLoopArgs &a, int g, int b0, int Bg, hipStream_t
         const uint64_t quad_offset = (uint64_t)(k + 1) * quads_total + quads_before;
         if (p.fused_boundary) {
             // only the skip sum feeds the output head (diffnet.py:128); the next step's stack input buffer is ws_x0
-            rc = launch_boundary(a, Bg, c.ws_skip, c.x, eps, sid, quad_offset, k + 1 < a.steps ? c.ws_x0 : nullptr, p.boundary_x2, s);
+            rc = launch_boundary(a, Bg, c.ws_skip, c.x, eps, sid, quad_offset, k + 1 < a.steps ? c.ws_x0 : nullptr, p.boundary_x2, p.ws_q4, s);
             continue;
         }
         // skip sum / sqrt(L) -> skip_projection -> ReLU -> output_projection (diffnet.py:128-131)

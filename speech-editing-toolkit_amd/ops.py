@@ -1435,6 +1435,7 @@ def diffusion_loop(*, x, noise, seed, condproj, dstep, coef4, w_in, b_in, packs,
     a.w_outp_p, a.b_outp = w_outp.packed().data_ptr(), b_outp.data_ptr()
     a.ws_x0, a.ws_x1, a.ws_skip, a.ws_h = (w.data_ptr() for w in ws)
     a.ws_x0pred = ws_x0pred.data_ptr()
+    a.ws_q4 = 1  # the workspaces are ours: the library may keep them in the channel-quad layout (SetDiffLoopArgs.ws_q4)
     a.n_groups = default_groups(B, T) if n_groups is None else int(n_groups)
     spans, loop_ms = None, None
     if want_layer_spans:

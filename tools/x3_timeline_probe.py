@@ -1,7 +1,8 @@
 """Timeline of ONE task of every block of diffnet_stack_x3v_kernel (timeline build: tools/build_exp.sh tl diffnet_x3.hip -DSET_PHASE_PROBE=2, then
 SET_AMD_LIB=build/exp/libset_amd_tl.so): every wave keeps s_memtime stamps of its X3V_TL_TASK-th task in SGPRs and waves 0 and 7 store them once,
 after the task -- no memory access between the stamps, unlike the summed phase counters of tools/x3_phase_probe.py.  Prints the median (and
-10 / 90 % quantiles) of every interval over the blocks, in us (ticks scaled by the median task period = next task's first stamp - this one's)."""
+10 / 90 % quantiles) of every interval over the blocks, in us (ticks scaled by the median task period = next task's first stamp - this one's).
+X3_TL_Q4=1: the kernel's channel-quad form (xs_q4; profiles/ws_q4_x3v_timeline.log)."""
 import os, sys
 import numpy as np
 import torch
@@ -10,6 +11,14 @@ sys.path.insert(0, ROOT)
 import set_amd  # noqa
 from set_amd import _lib, ops
 dev = torch.device("cuda:0")
+if os.environ.get("X3_TL_Q4") == "1":
+    # the channel-quad form of the kernel (SetDiffnetStackArgs.xs_q4): the same launches with the flag set.  The operands are random, so which
+    # element sits where does not matter to the timeline; ops.diffnet_stack itself has no such argument (the loop owns the layout).
+    class _Q4Args(_lib.SetDiffnetStackArgs):
+        def __init__(self):
+            super().__init__()
+            self.xs_q4 = 1
+    ops.SetDiffnetStackArgs = _Q4Args
 L = 20
 g = torch.Generator().manual_seed(1)
 w1 = torch.empty(L, 512 * 768, device=dev); w2 = torch.empty(L, 512 * 256, device=dev)
