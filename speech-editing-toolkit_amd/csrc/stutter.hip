@@ -3,9 +3,11 @@
 //   logits[b][t][j] = bias[j] + sum_c W[j][c] h[b][c][t]                       (nn.Linear(H, 3) on the post_net1 output)
 //   ce    = mean over rows with label != 2 of -log p_y                         (nn.CrossEntropyLoss(ignore_index=2))
 //   focal = mean over ALL B*T rows of -alpha_y (1 - p_y - s)^3 (log p_y + s)   (MultiFocalLoss, s = 1e-6, alpha = {5e-3, 1, 0})
-// log p_y = z_y - logsumexp(z): finite where the reference's log(softmax) underflows to log(0).  Losses are per-block partial sums
-// combined in block order by a second launch; weight / bias gradients are per-(utterance, 256-frame chunk) partial rows combined in
-// row order.
+// log p_y = (z_y - max z) - log(sum exp(z - max z)): finite where the reference's log(softmax) underflows to log(0), and blind to an offset
+// common to the three logits (z_y - (max z + log sum) rounds at ulp(max z)).  A batch of pad rows alone (no label != 2) gives ce = 0 / 0 =
+// NaN as torch does, a finite focal term, and every gradient exactly 0.  Labels outside {0, 1, 2} are clamped to 0 and 2.  Losses are
+// per-block partial sums combined in block order by a second launch; weight / bias gradients are per-(utterance, 256-frame chunk) partial
+// rows combined in row order.
 // Nothing is atomic and nothing is read back to the host: two runs are bit-identical.
 #include "common.h"
 
@@ -24,9 +26,8 @@ __device__ __forceinline__ void row_softmax(const float z[3], int y, float p[3],
     const float m = fmaxf(fmaxf(z[0], z[1]), z[2]);
     const float e0 = expf(z[0] - m), e1 = expf(z[1] - m), e2 = expf(z[2] - m);
     const float s = (e0 + e1) + e2;
-    const float lse = m + logf(s);
     p[0] = e0 / s; p[1] = e1 / s; p[2] = e2 / s;
-    logp_y = z[y] - lse;
+    logp_y = (z[y] - m) - logf(s);
 }
 
 // block = 4 waves over one utterance's 64-frame tile; lane = frame (coalesced reads along T), wave w takes channels w, w+4, ...
