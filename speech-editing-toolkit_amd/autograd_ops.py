@@ -242,6 +242,7 @@ def _head_views(heads, *packed):
 class _Conv1dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, chan_add, res, cw, dil, pad, pro, pro_param, act, alpha, mask, impl, t_out=None):
+        assert not (act == "relu" and res is not None), "the backward gates ReLU on the saved output: conv1d() adds the residual as its own node"
         x = x.contiguous()
         y = ops.conv1d(x, cw, bias, dil=dil, pad=pad, pro=pro, pro_param=pro_param, act=act, alpha=alpha, res=res,
                        mask=mask, in_chan_add=chan_add, impl=impl, T_out=t_out)
@@ -300,6 +301,13 @@ def conv1d(x, weight, bias=None, *, dil=1, pad=0, pro="none", pro_param=0.0, act
         z = _Conv1dFn.apply(x, weight.raw(), bias, in_chan_add, None, weight, dil, pad, pro, pro_param, "none", alpha,
                             None, impl, T_out)
         y = activation(z, act, act_param)
+        return add_chan_mask(y, None, mask) if mask is not None else y
+    if act == "relu" and res is not None:
+        # _Conv1dFn gates the ReLU on its saved output, which is relu(z) only while nothing is added to it: the residual (and the mask behind
+        # it) run as nodes of their own.  Same operations in the same order as the fused epilogue (+ res, then * mask): the same bits.
+        # No model combines the two (diffnet.py, fs.py), so no form a model uses gains a launch or a saved tensor.
+        y = add(_Conv1dFn.apply(x, weight.raw(), bias, in_chan_add, None, weight, dil, pad, pro, pro_param, act, alpha, None,
+                                impl, T_out), res)
         return add_chan_mask(y, None, mask) if mask is not None else y
     return _Conv1dFn.apply(x, weight.raw(), bias, in_chan_add, res, weight, dil, pad, pro, pro_param, act, alpha, mask,
                            impl, T_out)
