@@ -16,6 +16,9 @@ current stream wait for them, leaf_fence orders a bucket all-reduce behind both 
 * Nothing is allocated inside a block: torch's current stream is unchanged there (only ops._stream(), our kernels' launch stream, moves),
   so the compute stream would own what the leaf stream uses.  A per-stream scratch buffer regrown inside goes to hold_until_join.
 * Blocks do not nest (ops._STREAM_TLS.leaf is the open block's stream); a block left by an exception records no marker.
+* Join before the next reader: the first block of every backward pass (graph task) queues leaf_join as an engine callback; a pass that
+  raises runs no callbacks, so FlatAdamW.zero_grad() / step() / abort_step() join as well.  tests/stream_audit.py checks all of the above
+  call by call on the recorded sequence of library calls.
 """
 import collections
 import ctypes as C
@@ -124,6 +127,7 @@ class LeafStream:
             check(L().set_stream_create_low_priority(C.byref(self.raw)), "set_stream_create_low_priority")
         self.stream = torch.cuda.ExternalStream(self.raw.value, device=torch.device("cuda", idx))
         self.dirty = False
+        self.joined_task = -1  # graph task (backward pass) whose end-of-pass join is queued
         self.ledger = OperandLedger(_mb_env("SET_AMD_LEAF_MARK_MB", 128), _mb_env("SET_AMD_LEAF_KEEP_MB", 8192))
         self.marks = collections.deque()  # (marker slot, ledger count it covers), oldest first
         self.released_by_marker = self.early_joins = 0
@@ -203,12 +207,14 @@ class leaf_work:
         st.ledger.hold(self.tensors)
         ops._STREAM_TLS.leaf = st.raw
         self._st = st
-        if not st.dirty:
-            st.dirty = True
-            try:  # the stream that ran backward() waits for the leaf stream when the pass is over: callers may read .grad right away
-                torch.autograd.Variable._execution_engine.queue_callback(leaf_join)
-            except RuntimeError:
-                pass  # not inside a backward pass (a test calling a backward function by hand): FlatAdamW.step() / abort_step() join
+        st.dirty = True
+        # The stream that ran backward() waits for the leaf stream when the pass is over: callers may read .grad right away.  Once per
+        # backward pass, keyed by the engine's graph task and not by `dirty`: a pass that raised never ran its callbacks, and a block
+        # opened outside a pass queued none -- both leave `dirty` set, and the next pass must still end with its join.
+        task = torch._C._current_graph_task_id()
+        if task != -1 and task != st.joined_task:  # (-1: not inside a backward pass -- a test calling a backward function by hand;
+            st.joined_task = task                  # FlatAdamW.step() / abort_step() join)
+            torch.autograd.Variable._execution_engine.queue_callback(leaf_join)
         return True
 
     def __exit__(self, *exc):

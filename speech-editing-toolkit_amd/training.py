@@ -89,6 +89,7 @@ class FlatAdamW:
     def zero_grad(self, accumulate=False):
         """Start an optimizer step.  accumulate=True: more than one backward will run before step() (the reference's
         `accumulate_grad_batches`, utils/commons/trainer.py:331-340); the gradient exchange then waits for step()."""
+        leaf_stream.leaf_join()  # (a backward pass that raised, without abort_step(): its gradient kernels may still be queued)
         self.flat_g.zero_()
         A.zero_arena_begin(self.flat_g.device, self.n, owner=self)  # this step's zero-initialised gradient temporaries
         self.bucketer.reset(defer=accumulate)
