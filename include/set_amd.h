@@ -1078,6 +1078,67 @@ int set_stft_magnitude(const SetStftLossArgs *args, void *stream);
 int set_stft_loss_fwd(const SetStftLossArgs *args, void *stream);
 int set_stft_loss_bwd(const SetStftLossArgs *args, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * HiFi-GAN's multi-period discriminator as the generator step uses it (modules/vocoder/hifigan/hifigan.py:154-223 and the loss
+ * functions :301-338; tasks/vocoder/hifigan.py:26-50): forward on the real and the generated waveform with every feature map, the
+ * adversarial and feature-matching losses, and their gradient with respect to the generated waveform.  csrc/sconv.hip.
+ *
+ * Layout: the reference folds [B, 1, T] into [B, 1, H, p] (right reflect pad to Tp = ceil(T / p) p, H = Tp / p) and runs (K, 1)
+ * Conv2d layers, which never mix the p columns.  Here every (b, w) column is a row of its own: activations are [R][C][H], contiguous,
+ * R = 2 B p, row (sig B + b) p + w, the real signal's rows (sig = 0) first.  t.view(B, p, C, H).permute(0, 2, 3, 1) of one signal's
+ * rows is the reference's [B, C, H, p] tensor without a copy.  H_out = (H_in + 2 pad - K) / s + 1.
+ *
+ * set_sconv1d_fwd:  out[r][co][h] = act(bias[co] + sum_ci sum_k W[co][ci][k] x[r][ci][s h + k - pad]), x = 0 outside [0, H_in);
+ *   act = 0: identity, act = 1: v > 0 ? v : slope v;  1 <= s <= 4, 1 <= K <= 7, 0 <= pad < K, any Cin / Cout; bias may be NULL.
+ *   wp: the image of set_pack_conv_weight(W).  fp32 operands on v_mfma_f32_32x32x2_f32: each output is one fp32 fma chain over
+ *   (16-channel chunk ascending, tap ascending, channel ascending), from 0, then + bias, then act.
+ * set_sconv1d_dgrad:  dz_in[r][ci][j] = gate(f_in[r][ci][j]) (add[r][ci][j] + sum_co sum_k W[co][ci][k] dz_out[r][co][(j + pad - k) / s])
+ *   over the k with (j + pad - k) % s == 0 and 0 <= (j + pad - k) / s < H_out;  gate(v) = v > 0 ? 1 : slope (slope at exactly 0, as
+ *   torch's leaky_relu backward);  f_in NULL: no gate;  add NULL: none.  wtp: the image of set_pack_conv_weight of the transposed
+ *   weight W'[ci][co][k] (Cout' = Cin, Cin' = Cout).  Cin, Cout, H_in, K, s, pad are the FORWARD layer's.  One fma chain per element
+ *   over (16-channel chunk of co, tap k ascending among the element's taps, co ascending), from 0, then + add, then the gate.
+ * set_mpd_fold_conv_fwd:  the first layer (one input channel) straight from the waveforms y, y_hat [B][T] (contiguous):
+ *   xpad[n] = y[n] for n < T, y[2 (T - 1) - n] for T <= n < Tp;  out[(sig B + b) p + w][c][h] = act(bias[c] + sum_k w[c][k]
+ *   xpad[(s h + k - pad) p + w]) with rows outside [0, H) zero; w: the RAW weight [C][K]; T > p.  One fma chain over k ascending.
+ * set_mpd_fold_conv_bwd:  dz [B p][C][H_out] (the generated rows' gradient at the first layer's pre-activation) -> g_wav [B][T], every
+ *   sample written:  G(i, w) = fma chain over c ascending, inside it k ascending, of w[c][k] dz[b p + w][c][(i + pad - k) / s] (taps
+ *   that hit no output frame add an exact 0);  g_wav[b][n] = G(n / p, n % p) + G(m / p, m % p), the second term only where the mirror
+ *   m = 2 (T - 1) - n lies in [T, Tp).
+ * One row's [C][H] slice must stay below 2 GiB (SET_E_UNSUPPORTED).  No atomics; results do not depend on R or on the run. */
+int32_t set_sconv1d_out_len(int32_t H_in, int32_t K, int32_t s, int32_t pad);
+int set_sconv1d_fwd(const float *x, const float *wp, const float *bias, float *out, int32_t R, int32_t Cin, int32_t Cout, int32_t H_in,
+                    int32_t K, int32_t s, int32_t pad, int32_t act, float slope, void *stream);
+int set_sconv1d_dgrad(const float *dz_out, const float *wtp, const float *f_in, const float *add, float *dz_in, int32_t R, int32_t Cin,
+                      int32_t Cout, int32_t H_in, int32_t K, int32_t s, int32_t pad, float slope, void *stream);
+int set_mpd_fold_conv_fwd(const float *y, const float *y_hat, const float *w, const float *bias, float *out, int32_t B, int32_t T,
+                          int32_t p, int32_t C, int32_t K, int32_t s, int32_t pad, int32_t act, float slope, void *stream);
+int set_mpd_fold_conv_bwd(const float *dz, const float *w, float *g_wav, int32_t B, int32_t T, int32_t p, int32_t C, int32_t K,
+                          int32_t s, int32_t pad, void *stream);
+
+/* The three loss forms of hifigan.py:301-338 over a list of tensors.  `items`: a DEVICE array of n_items x SET_MULTI_LOSS_WORDS
+ * 64-bit words (plain words, not structs):
+ *   [0] address of a   [1] address of b (L1 only)   [2] address of grad_a (backward; 0 = none)   [3] mode (SET_LOSS_*)
+ *   [4..7] extents, outermost first (unused ones 1)   [8..11] element strides of a (and of grad_a)   [12..15] element strides of b
+ *   [16] the item's first chunk: the chunks of the items before it, ceil(numel / SET_MULTI_LOSS_CHUNK) each   [17] result slot
+ * total_chunks = the chunks of all items.  Modes: L1 mean |a - b|, SQ1 mean (1 - a)^2, SQ0 mean a^2.
+ * set_multi_loss_fwd: loss[k] = fp32(scale * sum over the items of slot k, in list order, of sum_i / numel_i), k < n_slots <= 4, left on
+ *   the device.  Order of an item's sum (all in double; a term is |a - b|, (1 - a)^2 or a^2 of the operands converted to double):
+ *   element li is the row-major index over the extents; block c (a chunk) has thread t add the terms of elements CHUNK c + t + 256 u,
+ *   u = 0..7 ascending, then the 256 thread sums are halved (red[t] += red[t + st], st = 128, 64, .. 1) -> part[first chunk + c];
+ *   then thread t of one block adds the item's partials t, t + 256, .. ascending and the thread sums are halved the same way.
+ *   part: total_chunks doubles of scratch.  Two kernels (partials, finish).
+ * set_multi_loss_bwd: grad_a = coef {sign(a - b), 2 (a - 1), 2 a} in fp32, sign(0) = 0, coef = fp32(u[slot] scale / numel) with the
+ *   product and the quotient in double; u: n_slots device floats (the upstream gradients; never read by the host); written at a's
+ *   strides, for the items whose word [2] is not 0.  One kernel. */
+#define SET_MULTI_LOSS_WORDS 18
+#define SET_MULTI_LOSS_CHUNK 2048
+#define SET_LOSS_L1 0
+#define SET_LOSS_SQ1 1
+#define SET_LOSS_SQ0 2
+int set_multi_loss_fwd(const int64_t *items, int32_t n_items, int64_t total_chunks, float scale, int32_t n_slots, double *part,
+                       float *loss, void *stream);
+int set_multi_loss_bwd(const int64_t *items, int32_t n_items, int64_t total_chunks, float scale, const float *u, void *stream);
+
 /* MFMA fragment-layout self test: runs a 32x32xK product through v_mfma_f32_32x32x2_f32 with the layout
  * this library assumes and returns the max abs error vs an in-kernel scalar reference via *max_err (HOST).
  * Synchronises.  Used by tests to pin the hardware layout assumption. */

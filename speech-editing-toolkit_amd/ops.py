@@ -1681,3 +1681,157 @@ def pos_add(x, alpha, pos, table):
 def add_masked(a, b, m):
     """a + b * m[b][t] on [B,C,T]"""
     return sum_div(a.contiguous(), add_chan_mask(b, None, m))
+
+
+# --------------------------------------------------------------------------
+# multi-period discriminator (csrc/sconv.hip): strided convs on [R][C][H] rows, the folded first layer, the list losses
+# --------------------------------------------------------------------------
+def sconv_out_len(H_in, K, stride, pad):
+    """H_out = (H_in + 2 pad - K) // stride + 1 (set_sconv1d_out_len; raises outside 1 <= K <= 7, 1 <= stride <= 4, 0 <= pad < K)."""
+    n = _lib.lib().set_sconv1d_out_len(int(H_in), int(K), int(stride), int(pad))
+    if n < 0:
+        check(n, "set_sconv1d_out_len")
+    return n
+
+
+def _rows3(t, name):
+    _f(t, name)
+    if t.dim() != 3:
+        raise ValueError("%s must be a contiguous [R, C, H] tensor, got %s" % (name, tuple(t.shape)))
+    return t
+
+
+def sconv1d_fwd(x, weight, bias=None, *, stride, pad, slope=None, sentinel=None):
+    """set_sconv1d_fwd: x [R,Cin,H_in] -> act(conv(x) + bias) [R,Cout,H_out]; `slope` None: no activation, else leaky ReLU."""
+    _rows3(x, "x"), _f(bias, "bias")
+    R, Cin, H_in = x.shape
+    if Cin != weight.Cin:
+        raise ValueError("sconv1d_fwd: x has %d channels, the weight takes %d" % (Cin, weight.Cin))
+    H_out = sconv_out_len(H_in, weight.K, stride, pad)
+    out = _buf((R, weight.Cout, H_out), x.device, sentinel)
+    check(_lib.lib().set_sconv1d_fwd(_p(x), _p(weight.packed()), _p(bias), _p(out), R, Cin, weight.Cout, H_in, weight.K, int(stride), int(pad),
+                                     int(slope is not None), float(slope or 0.0), _stream()), "set_sconv1d_fwd")
+    return out
+
+
+def sconv1d_dgrad(dz_out, weight, H_in, *, stride, pad, f_in=None, add=None, slope=0.0, sentinel=None):
+    """set_sconv1d_dgrad: dz_out [R,Cout,H_out] -> gate(f_in) * (add + conv^T(dz_out)) [R,Cin,H_in]; `weight` is the FORWARD layer's
+    ConvWeight (its transposed image is packed here); f_in / add: [R,Cin,H_in] or None."""
+    _rows3(dz_out, "dz_out")
+    R, Cout, H_out = dz_out.shape
+    if Cout != weight.Cout or H_out != sconv_out_len(H_in, weight.K, stride, pad):
+        raise ValueError("sconv1d_dgrad: dz_out %s does not belong to a (%d -> %d, K = %d, stride %d, pad %d) layer on %d frames"
+                         % (tuple(dz_out.shape), weight.Cin, weight.Cout, weight.K, stride, pad, H_in))
+    for t, name in ((f_in, "f_in"), (add, "add")):
+        if t is not None and tuple(_rows3(t, name).shape) != (R, weight.Cin, H_in):
+            raise ValueError("sconv1d_dgrad: %s must be [%d, %d, %d], got %s" % (name, R, weight.Cin, H_in, tuple(t.shape)))
+    dz_in = _buf((R, weight.Cin, H_in), dz_out.device, sentinel)
+    check(_lib.lib().set_sconv1d_dgrad(_p(dz_out), _p(weight.transposed().packed()), _p(f_in), _p(add), _p(dz_in), R, weight.Cin, Cout, int(H_in),
+                                       weight.K, int(stride), int(pad), float(slope), _stream()), "set_sconv1d_dgrad")
+    return dz_in
+
+
+def mpd_fold_conv_fwd(y, y_hat, w, bias, period, *, stride, pad, slope=None, sentinel=None):
+    """set_mpd_fold_conv_fwd: y, y_hat [B,T] -> the first layer's map [2 B p, C, H_out] (real rows first); w: the raw weight [C, K]
+    (any contiguous shape of C K elements with C first)."""
+    _f(y, "y"), _f(y_hat, "y_hat"), _f(w, "w"), _f(bias, "bias")
+    if y.dim() != 2 or y.shape != y_hat.shape:
+        raise ValueError("mpd_fold_conv_fwd: y and y_hat must be equal [B, T], got %s and %s" % (tuple(y.shape), tuple(y_hat.shape)))
+    B, T = y.shape
+    Cc = w.shape[0]
+    K = w.numel() // Cc
+    if T <= period:
+        raise ValueError("mpd_fold_conv_fwd: the reflect pad of period %d needs more than %d samples, got %d" % (period, period, T))
+    H_out = sconv_out_len((T + period - 1) // period, K, stride, pad)
+    out = _buf((2 * B * period, Cc, H_out), y.device, sentinel)
+    check(_lib.lib().set_mpd_fold_conv_fwd(_p(y), _p(y_hat), _p(w), _p(bias), _p(out), B, T, int(period), Cc, K, int(stride), int(pad),
+                                           int(slope is not None), float(slope or 0.0), _stream()), "set_mpd_fold_conv_fwd")
+    return out
+
+
+def mpd_fold_conv_bwd(dz, w, B, T, period, *, stride, pad, sentinel=None):
+    """set_mpd_fold_conv_bwd: dz [B p, C, H_out] (generated rows) -> d/d y_hat [B, T]."""
+    _rows3(dz, "dz"), _f(w, "w")
+    Cc = w.shape[0]
+    K = w.numel() // Cc
+    H_out = sconv_out_len((T + period - 1) // period, K, stride, pad)
+    if tuple(dz.shape) != (B * period, Cc, H_out):
+        raise ValueError("mpd_fold_conv_bwd: dz must be [%d, %d, %d], got %s" % (B * period, Cc, H_out, tuple(dz.shape)))
+    g_wav = _buf((B, T), dz.device, sentinel)
+    check(_lib.lib().set_mpd_fold_conv_bwd(_p(dz), _p(w), _p(g_wav), B, T, int(period), Cc, K, int(stride), int(pad), _stream()),
+          "set_mpd_fold_conv_bwd")
+    return g_wav
+
+
+LOSS_MODES = dict(l1=0, sq1=1, sq0=2)
+MULTI_LOSS_WORDS, MULTI_LOSS_CHUNK = 18, 2048
+
+
+def _loss_dims(a, b):
+    """(extents, a strides, b strides) of an item, four each: size-1 dims dropped, the rest ordered by a's stride (largest first, the
+    tensor's own order among equals) and merged wherever both operands allow -- a dense tensor and a target of the same layout become one
+    run in memory order.  More than four dims left, or an `a` that overlaps itself, is refused."""
+    dims = [(n, sa, (b.stride(i) if b is not None else 0)) for i, (n, sa) in enumerate(zip(a.shape, a.stride())) if n != 1]
+    if any(sa == 0 for _n, sa, _sb in dims):
+        raise ValueError("a loss operand must not overlap itself (an expanded dim): the gradient has its layout")
+    dims.sort(key=lambda d: -d[1])
+    merged = []
+    for n, sa, sb in dims:
+        if merged and merged[-1][1] == n * sa and merged[-1][2] == n * sb:
+            m = merged[-1]
+            merged[-1] = (m[0] * n, sa, sb)
+        else:
+            merged.append((n, sa, sb))
+    if len(merged) > 4:
+        raise ValueError("a loss operand pair of shape %s needs more than four strided dims" % (tuple(a.shape),))
+    merged = [(1, 0, 0)] * (4 - len(merged)) + merged
+    return [m[0] for m in merged], [m[1] for m in merged], [m[2] for m in merged]
+
+
+def multi_loss_items(a_list, b_list, modes, slots, grads=None):
+    """The device table of set_multi_loss_fwd / _bwd for the operand pairs (b None for the squared forms) -> (table [n, 18] int64 on the
+    device, total_chunks).  `grads`: per item the gradient buffer (a's strides) or None."""
+    import numpy as np
+    rows, chunk0 = [], 0
+    for i, (a, b, mode, slot) in enumerate(zip(a_list, b_list, modes, slots)):
+        _chk_loss_operand(a, "a")
+        if mode == LOSS_MODES["l1"]:
+            _chk_loss_operand(b, "b")
+            if b.shape != a.shape or b.device != a.device:
+                raise ValueError("loss operands must have equal shapes on one device, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+        else:
+            b = None
+        if a.numel() == 0:
+            raise ValueError("a loss operand has no elements")
+        e, sa, sb = _loss_dims(a, b)
+        g = grads[i] if grads is not None else None
+        rows.append([a.data_ptr(), b.data_ptr() if b is not None else 0, g.data_ptr() if g is not None else 0, mode] + e + sa + sb + [chunk0, slot])
+        chunk0 += (a.numel() + MULTI_LOSS_CHUNK - 1) // MULTI_LOSS_CHUNK
+    host = torch.from_numpy(np.asarray(rows, dtype=np.int64).reshape(len(rows), MULTI_LOSS_WORDS))
+    dev = a_list[0].device
+    if dev.type == "cuda":
+        host = host.pin_memory()
+    return host.to(dev, non_blocking=True), chunk0, host
+
+
+def _chk_loss_operand(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("loss operand %s must live on the GPU: the set_amd path has no CPU fallback" % name)
+    if t.dtype != torch.float32:
+        raise TypeError("loss operand %s must be float32, got %s" % (name, t.dtype))
+
+
+def multi_loss_fwd(table, n_items, total_chunks, scale, n_slots, sentinel=None):
+    """set_multi_loss_fwd -> loss [n_slots] fp32 on the device."""
+    part = torch.empty(total_chunks, dtype=torch.float64, device=table.device)
+    if sentinel is not None:
+        part.fill_(sentinel)
+    loss = _buf((n_slots,), table.device, sentinel)
+    check(_lib.lib().set_multi_loss_fwd(_p(table), n_items, total_chunks, float(scale), n_slots, _p(part), _p(loss), _stream()), "set_multi_loss_fwd")
+    return loss
+
+
+def multi_loss_bwd(table, n_items, total_chunks, scale, u):
+    """set_multi_loss_bwd: writes the gradient buffers the table names; u [n_slots] fp32 on the device."""
+    _f(u, "u")
+    check(_lib.lib().set_multi_loss_bwd(_p(table), n_items, total_chunks, float(scale), _p(u), _stream()), "set_multi_loss_bwd")
