@@ -1139,6 +1139,51 @@ int set_multi_loss_fwd(const int64_t *items, int32_t n_items, int64_t total_chun
                        float *loss, void *stream);
 int set_multi_loss_bwd(const int64_t *items, int32_t n_items, int64_t total_chunks, float scale, const float *u, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * HiFi-GAN's multi-scale discriminator as the generator step uses it (modules/vocoder/hifigan/hifigan.py:226-298): grouped strided
+ * convs with up to 41 taps, the first layer straight from the waveforms, and AvgPool1d(4, 2, padding = 1).  csrc/msd.hip.  Activations
+ * are [R][C][H] rows as above (R = 2 B, the real signal's rows first); the dense layers 7 and 8 run on set_sconv1d_*.
+ *
+ * set_gconv1d_fwd:  out[r][co][h] = act(bias[co] + sum_{ci in group(co)} sum_k W[co][ci][k] x[r][g Cin/G + ci][s h + k - pad]), W
+ *   [Cout][Cin / G][K], g = co / (Cout / G), x = 0 outside [0, H_in);  1 <= K <= SET_GCONV_KMAX, 1 <= s <= 4, 0 <= pad < K, any G
+ *   dividing Cin and Cout, any Cin / G and Cout / G (ragged sizes are zero-padded inside the image).  wp: G images of
+ *   set_pack_conv_weight back to back, image g that of the dense [Cout / G][Cin / G][K] weight of group g
+ *   (set_packed_gconv_weight_size floats in all).  One fp32 fma chain per output over (16-channel chunk of the group's input channels
+ *   ascending, tap ascending, channel ascending), from 0, then + bias, then act (as set_sconv1d_fwd).
+ * set_gconv1d_dgrad:  dz_in = gate(f_in) (add + conv^T(dz_out)) as set_sconv1d_dgrad, per group; wtp: G images of the groups'
+ *   transposed weights W'[ci][co][k].  One fma chain per element over (16-channel chunk of the group's co, tap ascending among the
+ *   element's taps, co ascending), from 0, then + add, then the gate (gate(0) = slope).  All output phases in one launch.
+ * The frames of one block: the forward works on SET_GCONV_TILE_1 output frames when Cout / G fits one 32-row block, else on
+ *   SET_GCONV_TILE_2; the dgrad on s times that many input frames by the 32-row blocks of Cin / G (set_gconv1d_tile(rows per group)).
+ * set_wave_conv_fwd:  the first layer from y, y_hat [B][T]: out[sig B + b][c][h] = act(bias[c] + sum_k w[c][k] wav[h + k - pad]), zeros
+ *   outside; w: the raw weight [C][K], K <= SET_WAVE_CONV_KMAX odd, pad = (K - 1) / 2.  One fma chain over k ascending.  y_hat NULL:
+ *   the B rows of y alone (out [B][C][T]).
+ * set_wave_conv_bwd:  dz [B][C][T] (the generated rows' gradient at the first layer's pre-activation) -> g_wav [B][T], every sample
+ *   written: one fma chain over c ascending, inside it k ascending, of w[c][k] dz[b][c][n + pad - k] (a frame outside adds an exact 0).
+ * set_avgpool4s2_fwd:  x [B][T] -> out [B][T_out], T_out = (T - 2) / 2 + 1 (T >= 2):
+ *   out[j] = 0.25 (((x[2 j - 1] + x[2 j]) + x[2 j + 1]) + x[2 j + 2]), zeros outside (the divisor is 4 at the edges too).
+ * set_avgpool4s2_bwd:  g_in[i] = add[i] + (0.25 g_out[lo] + 0.25 g_out[hi]), lo = (i + 1) / 2 - 1, hi = lo + 1, a term outside
+ *   [0, T_out) an exact 0; add NULL: the bracket alone.  T is the INPUT length.
+ * No atomics; results do not depend on R, B or on the run. */
+#define SET_GCONV_KMAX 41
+#define SET_WAVE_CONV_KMAX 15
+#define SET_GCONV_TILE_1 128
+#define SET_GCONV_TILE_2 64
+int32_t set_gconv1d_out_len(int32_t H_in, int32_t K, int32_t s, int32_t pad);
+int32_t set_gconv1d_tile(int32_t rows_per_group);
+int64_t set_packed_gconv_weight_size(int32_t Cout, int32_t Cin, int32_t K, int32_t groups);
+int set_gconv1d_fwd(const float *x, const float *wp, const float *bias, float *out, int32_t R, int32_t Cin, int32_t Cout, int32_t groups,
+                    int32_t H_in, int32_t K, int32_t s, int32_t pad, int32_t act, float slope, void *stream);
+int set_gconv1d_dgrad(const float *dz_out, const float *wtp, const float *f_in, const float *add, float *dz_in, int32_t R, int32_t Cin,
+                      int32_t Cout, int32_t groups, int32_t H_in, int32_t K, int32_t s, int32_t pad, float slope, void *stream);
+int set_wave_conv_fwd(const float *y, const float *y_hat, const float *w, const float *bias, float *out, int32_t B, int32_t T, int32_t C,
+                      int32_t K, int32_t pad, int32_t act, float slope, void *stream);
+int set_wave_conv_bwd(const float *dz, const float *w, float *g_wav, int32_t B, int32_t T, int32_t C, int32_t K, int32_t pad,
+                      void *stream);
+int32_t set_avgpool4s2_out_len(int32_t T);
+int set_avgpool4s2_fwd(const float *x, float *out, int32_t B, int32_t T, void *stream);
+int set_avgpool4s2_bwd(const float *g_out, const float *add, float *g_in, int32_t B, int32_t T, void *stream);
+
 /* MFMA fragment-layout self test: runs a 32x32xK product through v_mfma_f32_32x32x2_f32 with the layout
  * this library assumes and returns the max abs error vs an in-kernel scalar reference via *max_err (HOST).
  * Synchronises.  Used by tests to pin the hardware layout assumption. */

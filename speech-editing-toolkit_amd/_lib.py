@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_PKG, "libset_amd.so")
 # measurement only (tools/build_exp.sh): load an experimental build of the library instead; never built or rebuilt from here
 _LIB_OVERRIDE = os.environ.get("SET_AMD_LIB")
 SOURCES = ["conv1d.hip", "weight_image.hip", "conv_x2.hip", "resblock_x2.hip", "glue.hip", "diffnet.hip", "diffnet_x3.hip", "boundary.hip", "diffusion_ops.hip", "diffusion_loop.hip",
-           "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip", "melspec.hip", "mcd.hip", "stoi.hip", "wav_mcd.hip", "mel_loss.hip", "stft_loss.hip", "sconv.hip"]
+           "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip", "melspec.hip", "mcd.hip", "stoi.hip", "wav_mcd.hip", "mel_loss.hip", "stft_loss.hip", "sconv.hip", "msd.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 # constants mirrored from set_amd.h
@@ -391,6 +391,16 @@ SIGNATURES = {
     "set_mpd_fold_conv_bwd": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _V]),
     "set_multi_loss_fwd": (C.c_int, [_V, _I32, _I64, _F, _I32, _V, _V, _V]),
     "set_multi_loss_bwd": (C.c_int, [_V, _I32, _I64, _F, _V, _V]),
+    "set_gconv1d_out_len": (_I32, [_I32, _I32, _I32, _I32]),
+    "set_gconv1d_tile": (_I32, [_I32]),
+    "set_packed_gconv_weight_size": (_I64, [_I32, _I32, _I32, _I32]),
+    "set_gconv1d_fwd": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _V]),
+    "set_gconv1d_dgrad": (C.c_int, [_V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _F, _V]),
+    "set_wave_conv_fwd": (C.c_int, [_V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _I32, _I32, _F, _V]),
+    "set_wave_conv_bwd": (C.c_int, [_V, _V, _V, _I32, _I32, _I32, _I32, _I32, _V]),
+    "set_avgpool4s2_out_len": (_I32, [_I32]),
+    "set_avgpool4s2_fwd": (C.c_int, [_V, _V, _I32, _I32, _V]),
+    "set_avgpool4s2_bwd": (C.c_int, [_V, _V, _V, _I32, _I32, _V]),
     "set_mfcc": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _I32, _I32, _V]),
     "set_dtw": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _V]),
     "set_dtw_path": (C.c_int, [_V, _V, _V, _V, _V, _I32, _I32, _I32, _V]),

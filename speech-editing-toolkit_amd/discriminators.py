@@ -19,10 +19,14 @@ on set_sconv1d_fwd / set_sconv1d_dgrad (the stride-1 fifth conv and conv_post wi
 backward, and one kernel pair keeps one summation order across the stack); the first layer reads the waveforms directly.
 
 `y` is data: a `y` that requires grad raises.  There is no CPU fallback.
+
+The multi-scale discriminator (hifigan.py:226-298, csrc/msd.hip) follows the same rules: `MultiScaleDiscriminator` / `DiscriminatorS`
+below, with spectral norm for its first scale; the three loss functions take its [B, C, H] maps as they take the MPD's.
 """
 import torch
+import torch.nn.functional as F
 from torch import nn
-from torch.nn.utils import weight_norm
+from torch.nn.utils import spectral_norm, weight_norm
 
 from . import ops
 from .hifigan import _WNConv
@@ -268,3 +272,223 @@ def discriminator_loss(disc_real_outputs, disc_generated_outputs):
     a = r + g
     out = _multi_loss(a, [None] * len(a), ["sq1"] * len(r) + ["sq0"] * len(g), [0] * len(r) + [1] * len(g), 1.0 / max(len(r), 1), 2)
     return out[0], out[1]
+
+
+# ---- the multi-scale discriminator (hifigan.py:226-298; csrc/msd.hip) -------------------------------------------------------------------
+#
+#     msd = MultiScaleDiscriminator().cuda()
+#     _, y_d_gs, fmap_rs, fmap_gs = msd(y, y_)
+#     a_s = generator_loss(y_d_gs) * hparams['lambda_adv'];  fm_s = feature_loss(fmap_rs, fmap_gs)
+#
+# Three DiscriminatorS see y, pool(y), pool(pool(y)), pool = AvgPool1d(4, 2, padding=1).  Activations are [2 B, C, H] rows, the real
+# signal's first; a returned map is one half of them.  Layer 1 reads the waveforms (set_wave_conv_*), the grouped 41-tap layers run on
+# set_gconv1d_*, the dense 5- and 3-tap layers at the end on set_sconv1d_*.  The first discriminator is spectrally normed: in eval() its
+# weights are weight_orig / sigma with the stored u, v (folded once per weight version); in train() the reference calls it twice per
+# forward and each call does one power iteration, so the real rows see the weights after the first and the generated rows those after
+# the second -- the layers then run once per half with an image each, and weight_u / weight_v are updated in place as torch does.
+# sigma is a constant of d / d y_hat; the backward uses the generated rows' weights.
+MSD_CHANNELS = (128, 128, 256, 512, 1024, 1024, 1024)
+MSD_GROUPS = (1, 4, 16, 16, 16, 16, 1)
+_MSD_KERNELS = (15, 41, 41, 41, 41, 41, 5)
+_MSD_STRIDES = (1, 2, 2, 4, 4, 1, 1)
+
+
+class _SConv:
+    """One conv of a DiscriminatorS: its geometry, the weight it runs with and the operand the kernels take (the raw weight for the
+    first layer, a ConvWeight for a dense layer of at most 7 taps, a GroupedConvWeight otherwise)."""
+
+    def __init__(self, mod, spectral, act):
+        self.mod, self.spectral, self.act = mod, spectral, act
+        self.K, self.stride, self.pad, self.groups = mod.kernel_size[0], mod.stride[0], mod.padding[0], mod.groups
+        self.cout, self.cin = mod.out_channels, mod.in_channels
+        self.kind = "wave" if self.cin == 1 else ("dense" if self.groups == 1 and self.K <= 7 else "grouped")
+        self._slot = ops.CacheSlot()
+
+    def _with_operand(self, W):
+        W = W.contiguous()
+        if self.kind == "wave":
+            return W, W
+        if self.kind == "dense":
+            return W, ops.ConvWeight(W, self.cout, self.cin, self.K)
+        return W, ops.GroupedConvWeight(W, self.cout, self.cin, self.K, self.groups)
+
+    def _sigma_fold(self):
+        m = self.mod
+        w = m.weight_orig
+        sigma = torch.dot(m.weight_u, torch.mv(w.reshape(w.shape[0], -1), m.weight_v))
+        return w / sigma
+
+    def fixed(self):
+        """(weight, operand) of a weight-normed conv, or of a spectrally normed one in eval(): cached per weight version."""
+        m = self.mod
+        if self.spectral:
+            key = ops.weights_key((m.weight_orig, m.weight_u, m.weight_v))
+            return self._slot.get(key, lambda _: self._with_operand(self._sigma_fold().detach()))
+        g, v = m.weight_g, m.weight_v
+        return self._slot.get(ops.weights_key((g, v)), lambda _: self._with_operand(ops.weight_norm_fold(g.contiguous(), v.contiguous())))
+
+    def power_step(self):
+        """One power iteration of torch.nn.utils.spectral_norm on weight_u / weight_v in place, then (weight_orig / sigma, operand)."""
+        m = self.mod
+        with torch.no_grad():
+            wm = m.weight_orig.reshape(m.weight_orig.shape[0], -1)
+            m.weight_v.copy_(F.normalize(torch.mv(wm.t(), m.weight_u), dim=0, eps=1e-12))
+            m.weight_u.copy_(F.normalize(torch.mv(wm, m.weight_v), dim=0, eps=1e-12))
+            return self._with_operand(self._sigma_fold())
+
+    def out_len(self, H):
+        return (H + 2 * self.pad - self.K) // self.stride + 1 if H + 2 * self.pad >= self.K else 0
+
+
+def _disc_s_run(convs, weights, a, b, sentinel):
+    """The eight maps [R, C, H] of the rows of `a` (and of `b` behind them when given) under `weights` [(weight, operand)]."""
+    c0, (w0, _op0) = convs[0], weights[0]
+    maps = [ops.wave_conv_fwd(a, b, w0, c0.mod.bias.data, pad=c0.pad, slope=LRELU_SLOPE if c0.act else None, sentinel=sentinel)]
+    for c, (_w, op) in zip(convs[1:], weights[1:]):
+        run = ops.sconv1d_fwd if c.kind == "dense" else ops.gconv1d_fwd
+        maps.append(run(maps[-1], op, c.mod.bias.data, stride=c.stride, pad=c.pad, slope=LRELU_SLOPE if c.act else None, sentinel=sentinel))
+    return maps
+
+
+class _DiscSFn(torch.autograd.Function):
+    """One DiscriminatorS on both signals.  Outputs: the generated score and maps (differentiable in y_hat), then the real ones (not)."""
+
+    @staticmethod
+    def forward(ctx, y_hat, y, mod, sentinel):
+        B, T = y_hat.shape
+        convs = mod._convs
+        n = len(convs)
+        if mod.use_spectral_norm and mod.training:   # the reference's two calls: real first, then generated, one power iteration each
+            w_real = [c.power_step() for c in convs]
+            real = _disc_s_run(convs, w_real, y, None, sentinel)
+            w_gen = [c.power_step() for c in convs]
+            gen = _disc_s_run(convs, w_gen, y_hat, None, sentinel)
+        else:
+            w_gen = [c.fixed() for c in convs]
+            maps = _disc_s_run(convs, w_gen, y, y_hat, sentinel)
+            real, gen = [m[:B] for m in maps], [m[B:] for m in maps]
+        ctx.convs, ctx.weights, ctx.sentinel, ctx.n = convs, w_gen, sentinel, n
+        ctx.save_for_backward(*gen[:-1])
+        score_g, score_r = gen[-1].reshape(B, -1), real[-1].reshape(B, -1)
+        ctx.mark_non_differentiable(score_r, *real)
+        return (score_g, *gen, score_r, *real)
+
+    @staticmethod
+    def backward(ctx, g_score, *rest):
+        n = ctx.n
+        g_maps = list(rest[:n])
+        if g_score is None and all(g is None for g in g_maps):
+            return None, None, None, None
+        saved, convs, weights = ctx.saved_tensors, ctx.convs, ctx.weights
+        B = saved[0].shape[0]
+        adds = [None if g is None else g.contiguous() for g in g_maps]
+        H_last = convs[-1].out_len(saved[-1].shape[2])
+        dz = adds[-1]
+        if g_score is not None:
+            gs = g_score.reshape(B, 1, H_last)
+            dz = gs.contiguous() if dz is None else dz + gs
+        if dz is None:
+            dz = torch.zeros(B, 1, H_last, dtype=torch.float32, device=saved[0].device)
+        # top down: dz of layer i's input = gate(map i - 1) * (dgrad of layer i + the gradient arriving at map i - 1 from outside)
+        for i in range(n - 1, 0, -1):
+            c, f_in = convs[i], saved[i - 1]
+            run = ops.sconv1d_dgrad if c.kind == "dense" else ops.gconv1d_dgrad
+            dz = run(dz, weights[i][1], f_in.shape[2], stride=c.stride, pad=c.pad, f_in=f_in, add=adds[i - 1], slope=LRELU_SLOPE,
+                     sentinel=ctx.sentinel)
+        return ops.wave_conv_bwd(dz, weights[0][0], pad=convs[0].pad, sentinel=ctx.sentinel), None, None, None
+
+
+class DiscriminatorS(nn.Module):
+    """hifigan.py:226-259 with the reference's parameter and buffer names (convs.{i}.bias / weight_g / weight_v, or weight_orig /
+    weight_u / weight_v under spectral norm; conv_post.*).  `channels` and `groups` are ours (narrow nets for tests).
+
+    forward(y, y_hat) -> (score_r, score_g, fmap_r, fmap_g): scores [B, H], eight maps [B, C, H] each."""
+
+    def __init__(self, use_spectral_norm=False, use_cond=False, upsample_rates=None, c_in=1, channels=MSD_CHANNELS, groups=MSD_GROUPS):
+        super().__init__()
+        if use_cond or c_in != 1:
+            raise NotImplementedError("DiscriminatorS is built without the conditional input (use_cond)")
+        if len(channels) != 7 or len(groups) != 7 or groups[0] != 1:
+            raise ValueError("channels and groups must name the seven conv widths and group counts (the first conv has one group)")
+        self.use_spectral_norm = bool(use_spectral_norm)
+        norm_f = spectral_norm if self.use_spectral_norm else weight_norm
+        chans = [1] + [int(c) for c in channels]
+        self.convs = nn.ModuleList([norm_f(nn.Conv1d(chans[i], chans[i + 1], _MSD_KERNELS[i], _MSD_STRIDES[i], groups=int(groups[i]),
+                                                     padding=(_MSD_KERNELS[i] - 1) // 2)) for i in range(7)])
+        self.conv_post = norm_f(nn.Conv1d(chans[7], 1, 3, 1, padding=1))
+        for q in self.parameters():
+            q.requires_grad_(False)
+        mods = list(self.convs) + [self.conv_post]
+        self._convs = [_SConv(m, self.use_spectral_norm, i < 7) for i, m in enumerate(mods)]
+
+    _check_weights = DiscriminatorP._check_weights
+
+    def _check_length(self, T):
+        H = T
+        for i, c in enumerate(self._convs):
+            H = c.out_len(H)
+            if H < 1:
+                raise ValueError("DiscriminatorS: %d samples leave layer %d without an output frame" % (T, i + 1))
+
+    def forward(self, y, y_hat, mel=None, sentinel=None):
+        y2, yh2 = _check_waves(y, y_hat)
+        self._check_weights()
+        self._check_length(y2.shape[1])
+        n = len(self._convs)
+        outs = _DiscSFn.apply(yh2, y2, self, sentinel)
+        return outs[n + 1], outs[0], list(outs[n + 2:2 * n + 2]), list(outs[1:n + 1])
+
+
+class _PoolStep(torch.autograd.Function):
+    """x -> (an alias of x for this scale's discriminator, pool(x) for the next scale).  Backward: g_alias + pool^T(g_pooled) in one launch,
+    so the three scales' gradients meet as g0 + pool^T(g1 + pool^T(g2))."""
+
+    @staticmethod
+    def forward(ctx, x, sentinel):
+        ctx.set_materialize_grads(False)
+        ctx.T, ctx.sentinel = x.shape[1], sentinel
+        return x.view_as(x), ops.avgpool4s2_fwd(x, sentinel=sentinel)
+
+    @staticmethod
+    def backward(ctx, g_alias, g_pooled):
+        if g_pooled is None:
+            return g_alias, None
+        return ops.avgpool4s2_bwd(g_pooled.contiguous(), ctx.T, add=None if g_alias is None else g_alias.contiguous(), sentinel=ctx.sentinel), None
+
+
+class MultiScaleDiscriminator(nn.Module):
+    """hifigan.py:262-298: a spectrally normed DiscriminatorS on the waveform and two weight-normed ones on its 4 / 2 average pools.
+    forward(y, y_hat, mel=None) -> (y_d_rs, y_d_gs, fmap_rs, fmap_gs), the reference's structure and shapes; y, y_hat: fp32 GPU [B, 1, T]
+    (or [B, T]); `mel` is ignored.  Needs no hparams (they only size the conditional net, which is not built)."""
+
+    def __init__(self, use_cond=False, c_in=1, channels=MSD_CHANNELS, groups=MSD_GROUPS):
+        super().__init__()
+        self.discriminators = nn.ModuleList([DiscriminatorS(use_spectral_norm=(i == 0), use_cond=use_cond, c_in=c_in, channels=channels, groups=groups)
+                                             for i in range(3)])
+        self.meanpools = nn.ModuleList([nn.AvgPool1d(4, 2, padding=1), nn.AvgPool1d(4, 2, padding=1)])
+
+    def forward(self, y, y_hat, mel=None, sentinel=None):
+        y2, yh2 = _check_waves(y, y_hat)
+        T, D = y2.shape[1], len(self.discriminators)
+        for i, d in enumerate(self.discriminators):
+            d._check_weights()
+            if T < 2 and i:
+                raise ValueError("MultiScaleDiscriminator: the pool of scale %d has no output sample" % i)
+            T = T if i == 0 else ops.avgpool4s2_out_len(T)
+            d._check_length(T)
+        track = torch.is_grad_enabled() and yh2.requires_grad
+        y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
+        n = len(self.discriminators[0]._convs)
+        for i, d in enumerate(self.discriminators):
+            if i + 1 < D:
+                yh_i, yh_next = _PoolStep.apply(yh2, sentinel) if track else (yh2, ops.avgpool4s2_fwd(yh2, sentinel=sentinel))
+                y_next = ops.avgpool4s2_fwd(y2, sentinel=sentinel)
+            else:
+                yh_i, yh_next, y_next = yh2, None, None
+            outs = _DiscSFn.apply(yh_i, y2, d, sentinel)
+            y_d_rs.append(outs[n + 1])
+            y_d_gs.append(outs[0])
+            fmap_rs.append(list(outs[n + 2:2 * n + 2]))
+            fmap_gs.append(list(outs[1:n + 1]))
+            y2, yh2 = y_next, yh_next
+        return y_d_rs, y_d_gs, fmap_rs, fmap_gs

@@ -1835,3 +1835,146 @@ def multi_loss_bwd(table, n_items, total_chunks, scale, u):
     """set_multi_loss_bwd: writes the gradient buffers the table names; u [n_slots] fp32 on the device."""
     _f(u, "u")
     check(_lib.lib().set_multi_loss_bwd(_p(table), n_items, total_chunks, float(scale), _p(u), _stream()), "set_multi_loss_bwd")
+
+
+# --------------------------------------------------------------------------
+# multi-scale discriminator (csrc/msd.hip): grouped convs with up to 41 taps, the first layer from the waveforms, the 4 / 2 average pool
+# --------------------------------------------------------------------------
+GCONV_KMAX, WAVE_CONV_KMAX = 41, 15
+GCONV_TILES = (128, 64)   # frames per block when a group's rows (Cout / g forward, Cin / g dgrad) fit one 32-row block / need more
+
+
+def gconv_tile(rows_per_group):
+    """Output frames (forward) or, times the stride, input frames (dgrad) of one block (set_gconv1d_tile)."""
+    n = _lib.lib().set_gconv1d_tile(int(rows_per_group))
+    if n < 0:
+        check(n, "set_gconv1d_tile")
+    return n
+
+
+def gconv_out_len(H_in, K, stride, pad):
+    """H_out = (H_in + 2 pad - K) // stride + 1 (set_gconv1d_out_len; raises outside 1 <= K <= 41, 1 <= stride <= 4, 0 <= pad < K)."""
+    n = _lib.lib().set_gconv1d_out_len(int(H_in), int(K), int(stride), int(pad))
+    if n < 0:
+        check(n, "set_gconv1d_out_len")
+    return n
+
+
+class GroupedConvWeight:
+    """Weight operand of set_gconv1d_fwd / _dgrad: W [Cout, Cin / groups, K].  Group g is the dense conv weight W[g Cout/G : (g + 1) Cout/G];
+    its image is what set_pack_conv_weight makes of it (the one layout, the one pack kernel), written into slot g of one buffer -- and
+    likewise the transposed weights for the input gradient.  `getter` as ConvWeight's; the images follow the weight's storage and version."""
+
+    def __init__(self, getter, Cout, Cin, K, groups):
+        if Cout % groups or Cin % groups:
+            raise ValueError("groups = %d must divide Cin = %d and Cout = %d" % (groups, Cin, Cout))
+        self.Cout, self.Cin, self.K, self.groups = int(Cout), int(Cin), int(K), int(groups)
+        self._src = ConvWeight(getter, Cout, Cin // groups, K)   # resolves the weight; never packed as a whole
+        self._fwd, self._tr = CacheSlot(), CacheSlot()
+
+    def raw(self):
+        return self._src.raw()
+
+    def _pack(self, w, wp, transposed):
+        L = _lib.lib()
+        cog, cig, K = self.Cout // self.groups, self.Cin // self.groups, self.K
+        rows, red = (cig, cog) if transposed else (cog, cig)
+        slot = L.set_packed_conv_weight_size(rows, red, K)
+        if wp is None or wp.device != w.device:
+            wp = torch.empty(self.groups * slot, dtype=torch.float32, device=w.device)
+        sco, sci = (K, cig * K) if transposed else (cig * K, K)
+        for g in range(self.groups):
+            check(L.set_pack_conv_weight(_p(w), wp.data_ptr() + 4 * g * slot, rows, red, K, g * cog * cig * K, sco, sci, 1, _stream()),
+                  "set_pack_conv_weight")
+        return wp
+
+    def packed(self):
+        w = self.raw()
+        return self._fwd.get(weights_key((w,)), lambda wp: self._pack(w, wp, False))
+
+    def packed_transposed(self):
+        w = self.raw()
+        return self._tr.get(weights_key((w,)), lambda wp: self._pack(w, wp, True))
+
+
+def gconv1d_fwd(x, weight, bias=None, *, stride, pad, slope=None, sentinel=None):
+    """set_gconv1d_fwd: x [R,Cin,H_in] -> act(grouped conv(x) + bias) [R,Cout,H_out]; `slope` None: no activation, else leaky ReLU."""
+    _rows3(x, "x"), _f(bias, "bias")
+    R, Cin, H_in = x.shape
+    if Cin != weight.Cin:
+        raise ValueError("gconv1d_fwd: x has %d channels, the weight takes %d" % (Cin, weight.Cin))
+    H_out = gconv_out_len(H_in, weight.K, stride, pad)
+    if H_out < 1:
+        raise ValueError("gconv1d_fwd: %d frames give no output frame at K = %d, stride %d, pad %d" % (H_in, weight.K, stride, pad))
+    out = _buf((R, weight.Cout, H_out), x.device, sentinel)
+    check(_lib.lib().set_gconv1d_fwd(_p(x), _p(weight.packed()), _p(bias), _p(out), R, Cin, weight.Cout, weight.groups, H_in, weight.K, int(stride),
+                                     int(pad), int(slope is not None), float(slope or 0.0), _stream()), "set_gconv1d_fwd")
+    return out
+
+
+def gconv1d_dgrad(dz_out, weight, H_in, *, stride, pad, f_in=None, add=None, slope=0.0, sentinel=None):
+    """set_gconv1d_dgrad: dz_out [R,Cout,H_out] -> gate(f_in) * (add + conv^T(dz_out)) [R,Cin,H_in]; f_in / add: [R,Cin,H_in] or None."""
+    _rows3(dz_out, "dz_out")
+    R, Cout, H_out = dz_out.shape
+    if Cout != weight.Cout or H_out != gconv_out_len(H_in, weight.K, stride, pad):
+        raise ValueError("gconv1d_dgrad: dz_out %s does not belong to a (%d -> %d, K = %d, stride %d, pad %d, groups %d) layer on %d frames"
+                         % (tuple(dz_out.shape), weight.Cin, weight.Cout, weight.K, stride, pad, weight.groups, H_in))
+    for t, name in ((f_in, "f_in"), (add, "add")):
+        if t is not None and tuple(_rows3(t, name).shape) != (R, weight.Cin, H_in):
+            raise ValueError("gconv1d_dgrad: %s must be [%d, %d, %d], got %s" % (name, R, weight.Cin, H_in, tuple(t.shape)))
+    dz_in = _buf((R, weight.Cin, H_in), dz_out.device, sentinel)
+    check(_lib.lib().set_gconv1d_dgrad(_p(dz_out), _p(weight.packed_transposed()), _p(f_in), _p(add), _p(dz_in), R, weight.Cin, Cout, weight.groups,
+                                       int(H_in), weight.K, int(stride), int(pad), float(slope), _stream()), "set_gconv1d_dgrad")
+    return dz_in
+
+
+def wave_conv_fwd(y, y_hat, w, bias, *, pad, slope=None, sentinel=None):
+    """set_wave_conv_fwd: y, y_hat [B,T] -> the first layer's map [2 B, C, T] (real rows first); w: the raw weight [C, 1, K] or [C, K].
+    y_hat None: the map of y alone [B, C, T]."""
+    _f(y, "y"), _f(y_hat, "y_hat"), _f(w, "w"), _f(bias, "bias")
+    if y.dim() != 2 or (y_hat is not None and y.shape != y_hat.shape):
+        raise ValueError("wave_conv_fwd: y and y_hat must be equal [B, T], got %s and %s" % (tuple(y.shape), tuple(y_hat.shape)))
+    B, T = y.shape
+    Cc = w.shape[0]
+    K = w.numel() // Cc
+    out = _buf(((1 if y_hat is None else 2) * B, Cc, T), y.device, sentinel)
+    check(_lib.lib().set_wave_conv_fwd(_p(y), _p(y_hat), _p(w), _p(bias), _p(out), B, T, Cc, K, int(pad), int(slope is not None), float(slope or 0.0),
+                                       _stream()), "set_wave_conv_fwd")
+    return out
+
+
+def wave_conv_bwd(dz, w, *, pad, sentinel=None):
+    """set_wave_conv_bwd: dz [B, C, T] (generated rows) -> d/d y_hat [B, T]."""
+    _rows3(dz, "dz"), _f(w, "w")
+    B, Cc, T = dz.shape
+    if w.shape[0] != Cc:
+        raise ValueError("wave_conv_bwd: dz has %d channels, the weight %d" % (Cc, w.shape[0]))
+    g_wav = _buf((B, T), dz.device, sentinel)
+    check(_lib.lib().set_wave_conv_bwd(_p(dz), _p(w), _p(g_wav), B, T, Cc, w.numel() // Cc, int(pad), _stream()), "set_wave_conv_bwd")
+    return g_wav
+
+
+def avgpool4s2_out_len(T):
+    return _lib.lib().set_avgpool4s2_out_len(int(T))
+
+
+def avgpool4s2_fwd(x, sentinel=None):
+    """set_avgpool4s2_fwd: AvgPool1d(4, 2, padding=1) on x [B, T] -> [B, (T - 2) // 2 + 1]."""
+    _f(x, "x")
+    if x.dim() != 2 or x.shape[1] < 2:
+        raise ValueError("avgpool4s2_fwd: x must be [B, T] with T >= 2, got %s" % (tuple(x.shape),))
+    B, T = x.shape
+    out = _buf((B, avgpool4s2_out_len(T)), x.device, sentinel)
+    check(_lib.lib().set_avgpool4s2_fwd(_p(x), _p(out), B, T, _stream()), "set_avgpool4s2_fwd")
+    return out
+
+
+def avgpool4s2_bwd(g_out, T, add=None, sentinel=None):
+    """set_avgpool4s2_bwd: g_out [B, T_out] -> add + pool^T(g_out) [B, T]."""
+    _f(g_out, "g_out"), _f(add, "add")
+    B = g_out.shape[0]
+    if g_out.dim() != 2 or T < 2 or g_out.shape[1] != avgpool4s2_out_len(T) or (add is not None and tuple(add.shape) != (B, T)):
+        raise ValueError("avgpool4s2_bwd: g_out %s (and add) do not belong to a pool of %d samples" % (tuple(g_out.shape), T))
+    g_in = _buf((B, T), g_out.device, sentinel)
+    check(_lib.lib().set_avgpool4s2_bwd(_p(g_out), _p(add), _p(g_in), B, int(T), _stream()), "set_avgpool4s2_bwd")
+    return g_in
