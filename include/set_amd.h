@@ -1184,6 +1184,63 @@ int32_t set_avgpool4s2_out_len(int32_t T);
 int set_avgpool4s2_fwd(const float *x, float *out, int32_t B, int32_t T, void *stream);
 int set_avgpool4s2_bwd(const float *g_out, const float *add, float *g_in, int32_t B, int32_t T, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The discriminator step (tasks/vocoder/hifigan.py:51-61): gradients with respect to the discriminators' own weights.
+ * csrc/disc_wgrad.hip.  Activations are the [R][C][H] rows above, over ALL rows (real and generated).  fp32 operands; no atomics; every
+ * result is bit-identical from run to run.  `accumulate` 1: the result is ADDED to the output (one fp32 add per element), 0: stored.
+ *
+ * set_gconv1d_wgrad:  dW[co][ci][k] (+)= sum_r sum_h dz[r][co][h] x[r][g Cin/G + ci][s h + k - pad], x = 0 outside [0, H_in), g = co /
+ *   (Cout / G);  dW [Cout][Cin / G][K];  the ranges of set_gconv1d_fwd (G = 1: the dense layers of both discriminators).  db (optional)
+ *   [Cout]: db[co] (+)= sum_r sum_h dz[r][co][h].  dw or db may be NULL (not wanted), not both.
+ *   The reduction index j = r H_out + h runs over the frames of every row, in chunks of SET_GCONV_WGRAD_CHUNK; `slices` consecutive
+ *   runs of ceil(chunks / slices) chunks each (the last ones may be short or empty).  On v_mfma_f32_32x32x2_f32, a block being 32 rows
+ *   of one group by SET_GCONV_WGRAD_COLS flattened (ci, k) columns.  Order of an element's sum: per slice one fp32 fma chain from 0 over
+ *   j ascending, products unrounded (indices past the end and taps outside the row add an exact 0);  then t = ((p_0 + p_1) + p_2) + ..
+ *   over the slices ascending;  then dW = t, or dW_old + t.  With one slice and accumulate = 0 the chain is stored directly.
+ *   db: thread t of 256 adds the terms j = t, t + 256, .. ascending in double; the thread sums are halved (red[t] += red[t + st], st =
+ *   128, 64, .. 1); rounded to fp32 once; then stored or added.
+ *   slices: 0 = set_gconv1d_wgrad_plan on the current device's CU count, 1 .. SET_GCONV_WGRAD_MAX_SLICES forces it.  scratch:
+ *   set_gconv1d_wgrad_scratch_floats(.., slices) floats (slices Cout Cin/G K), reusable by the next call on the stream; not read when
+ *   slices == 1 and accumulate == 0 (may then be NULL).
+ * set_gconv1d_wgrad_plan: the slice count, a pure function of the shapes and n_cu (0: the current device's): with tiles = G
+ *   ceil((Cout/G) / 32) ceil((Cin/G) K / COLS) and chunks = ceil(R H_out / CHUNK): min(ceil(4 n_cu / tiles), chunks / 8, MAX_SLICES),
+ *   at least 1.
+ * set_mpd_fold_conv_wgrad / set_wave_conv_wgrad: the first layers (one input channel), from the waveforms y, y_hat [B][T] and dz over
+ *   all rows ([2 B p][C][H_out] / [2 B][C][T]; set_wave_conv_wgrad with y_hat NULL: the B rows of y alone):
+ *   dW[c][k] (+)= sum_r sum_h dz[r][c][h] X(r, s h + k - pad), db[c] (+)= sum dz, X as set_mpd_fold_conv_fwd's xpad[i p + w] (0 for i
+ *   outside [0, H)) / set_wave_conv_fwd's wav[i]; dW [C][K] raw.  K <= SET_WAVE_CONV_KMAX.  Order: j = r H_out + h; slice z owns the
+ *   j in [z per, (z + 1) per), per = ceil(J / slices); thread t adds the terms j = lo + t, lo + t + 256, .. ascending in double (products
+ *   exact), halved as above -> part[z][c][k] (k = K: the bias); then the slices ascending in double, rounded to fp32 once, stored or
+ *   added.  slices 0: min(ceil(4 n_cu / C), J / 4096, SET_FIRST_WGRAD_MAX_SLICES), at least 1.  part:
+ *   set_first_conv_wgrad_part_doubles(C, K, slices) doubles.  dw or db may be NULL.
+ * set_weight_norm_fold_bwd: w = g v / |v| per row (set_weight_norm_fold) -> dg[row] = <dW, v> / n, dv = (g / n) (dW - v <dW, v> / n^2),
+ *   n = sqrt(sum v^2).  Per row, thread t adds v_i^2 and dW_i v_i of i = t, t + 256, .. in double, halved as above; the formulas in
+ *   double, rounded once.  dg or dv may be NULL.
+ * set_spectral_norm_fold_bwd: W = W_orig / sigma, sigma = u^T W_orig v with u, v constants (torch.nn.utils.spectral_norm) ->
+ *   d W_orig = (dW - (<dW, W_orig> / sigma) u v^T) / sigma, W_orig [n0][inner], sigma a DEVICE float.  <dW, W_orig>: row sums as above
+ *   -> part[row] (n0 doubles), then thread t adds rows t, t + 256, .. ascending, halved; the formula in double, rounded once. */
+#define SET_GCONV_WGRAD_CHUNK 32
+#define SET_GCONV_WGRAD_COLS 128
+#define SET_GCONV_WGRAD_MAX_SLICES 64
+#define SET_FIRST_WGRAD_MAX_SLICES 64
+int32_t set_gconv1d_wgrad_plan(int32_t R, int32_t Cin, int32_t Cout, int32_t groups, int32_t H_in, int32_t K, int32_t s, int32_t pad,
+                               int32_t n_cu);
+int64_t set_gconv1d_wgrad_scratch_floats(int32_t R, int32_t Cin, int32_t Cout, int32_t groups, int32_t H_in, int32_t K, int32_t s,
+                                         int32_t pad, int32_t slices);
+int set_gconv1d_wgrad(const float *dz, const float *x, float *dw, float *db, int32_t R, int32_t Cin, int32_t Cout, int32_t groups,
+                      int32_t H_in, int32_t K, int32_t s, int32_t pad, int32_t accumulate, int32_t slices, float *scratch,
+                      int64_t scratch_floats, void *stream);
+int64_t set_first_conv_wgrad_part_doubles(int32_t C, int32_t K, int32_t slices);
+int set_mpd_fold_conv_wgrad(const float *dz, const float *y, const float *y_hat, float *dw, float *db, int32_t B, int32_t T, int32_t p,
+                            int32_t C, int32_t K, int32_t s, int32_t pad, int32_t accumulate, int32_t slices, double *part,
+                            int64_t part_doubles, void *stream);
+int set_wave_conv_wgrad(const float *dz, const float *y, const float *y_hat, float *dw, float *db, int32_t B, int32_t T, int32_t C,
+                        int32_t K, int32_t pad, int32_t accumulate, int32_t slices, double *part, int64_t part_doubles, void *stream);
+int set_weight_norm_fold_bwd(const float *dw, const float *g, const float *v, float *dg, float *dv, int32_t n0, int64_t inner,
+                             int32_t accumulate, void *stream);
+int set_spectral_norm_fold_bwd(const float *dw, const float *w_orig, const float *u, const float *v, const float *sigma, float *dw_orig,
+                               int32_t n0, int64_t inner, int32_t accumulate, double *part, void *stream);
+
 /* MFMA fragment-layout self test: runs a 32x32xK product through v_mfma_f32_32x32x2_f32 with the layout
  * this library assumes and returns the max abs error vs an in-kernel scalar reference via *max_err (HOST).
  * Synchronises.  Used by tests to pin the hardware layout assumption. */

@@ -18,7 +18,7 @@ LIB_PATH = os.path.join(_PKG, "libset_amd.so")
 # measurement only (tools/build_exp.sh): load an experimental build of the library instead; never built or rebuilt from here
 _LIB_OVERRIDE = os.environ.get("SET_AMD_LIB")
 SOURCES = ["conv1d.hip", "weight_image.hip", "conv_x2.hip", "resblock_x2.hip", "glue.hip", "diffnet.hip", "diffnet_x3.hip", "boundary.hip", "diffusion_ops.hip", "diffusion_loop.hip",
-           "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip", "melspec.hip", "mcd.hip", "stoi.hip", "wav_mcd.hip", "mel_loss.hip", "stft_loss.hip", "sconv.hip", "msd.hip"]
+           "train.hip", "attention.hip", "attention_fused.hip", "bf16.hip", "diffnet_bf16.hip", "stutter.hip", "melspec.hip", "mcd.hip", "stoi.hip", "wav_mcd.hip", "mel_loss.hip", "stft_loss.hip", "sconv.hip", "msd.hip", "disc_wgrad.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off"]
 
 # constants mirrored from set_amd.h
@@ -401,6 +401,14 @@ SIGNATURES = {
     "set_avgpool4s2_out_len": (_I32, [_I32]),
     "set_avgpool4s2_fwd": (C.c_int, [_V, _V, _I32, _I32, _V]),
     "set_avgpool4s2_bwd": (C.c_int, [_V, _V, _V, _I32, _I32, _V]),
+    "set_gconv1d_wgrad_plan": (_I32, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "set_gconv1d_wgrad_scratch_floats": (_I64, [_I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32]),
+    "set_gconv1d_wgrad": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _V, _I64, _V]),
+    "set_first_conv_wgrad_part_doubles": (_I64, [_I32, _I32, _I32]),
+    "set_mpd_fold_conv_wgrad": (C.c_int, [_V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _V, _I64, _V]),
+    "set_wave_conv_wgrad": (C.c_int, [_V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _I32, _I32, _I32, _V, _I64, _V]),
+    "set_weight_norm_fold_bwd": (C.c_int, [_V, _V, _V, _V, _V, _I32, _I64, _I32, _V]),
+    "set_spectral_norm_fold_bwd": (C.c_int, [_V, _V, _V, _V, _V, _V, _I32, _I64, _I32, _V, _V]),
     "set_mfcc": (C.c_int, [_V, _V, _V, _V, _I32, _I32, _I32, _I32, _I32, _V]),
     "set_dtw": (C.c_int, [_V, _V, _V, _V, _V, _V, _V, _I32, _I32, _I32, _I32, _V]),
     "set_dtw_path": (C.c_int, [_V, _V, _V, _V, _V, _I32, _I32, _I32, _V]),

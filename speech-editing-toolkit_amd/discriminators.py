@@ -7,10 +7,22 @@ tasks/vocoder/hifigan.py:26-50), on the GPU (csrc/sconv.hip):
     fm_f = feature_loss(fmap_rs, fmap_gs)
     (a_p + fm_f).backward()                                    # -> y_.grad
 
-Built: the forward on both waveforms with every feature map, the three loss functions, and the gradient with respect to the generated
-waveform.  Not built: gradients with respect to the discriminator's own weights (the discriminator step) -- the parameters are created
-with requires_grad=False and one that requires grad raises under grad mode instead of silently getting none --, the conditional input
-(use_cond) and spectral norm.
+Built: the forward on both waveforms with every feature map, the three loss functions, the gradient with respect to the generated
+waveform, and -- after `trainable_()` -- the discriminator step (tasks/vocoder/hifigan.py:51-61, csrc/disc_wgrad.hip):
+
+    mpd = MultiPeriodDiscriminator().cuda().trainable_()
+    y_d_rs, y_d_gs, _, _ = mpd(y, y_.detach())
+    r, f = discriminator_loss(y_d_rs, y_d_gs)
+    (r + f).backward()                                         # -> .grad of every parameter; torch.optim.AdamW(mpd.parameters()).step()
+
+Without `trainable_()` nothing changes: the parameters are created with requires_grad=False and one that requires grad raises under
+grad mode instead of silently getting none.  With it the parameters are inputs of the autograd node, the real SCORE is differentiable
+(the real MAPS stay targets, as feature_loss defines them), the backward runs the input-gradient chain over all 2 B (p) rows and after
+each layer its weight / bias gradient and the backward of the weight-norm (or spectral-norm) fold; the waveform gradient is computed
+only when y_hat requires grad, a frozen parameter costs no launch.  A gradient that reaches the generated maps while the weights are
+trainable (feature_loss) flows into the weights through the generated rows and into y_hat as before.  Everything runs on the compute
+stream (moving the weight gradients to the leaf stream is a follow-up).  Not built: the conditional input (use_cond) and spectral norm
+for the MPD.
 
 Layout: the reference folds [B, 1, T] into [B, 1, H, p] and runs (K, 1) Conv2d layers that never mix the p columns; here every (b, w)
 column is a row of its own and a layer's activations are one [2 B p, C, H] buffer, the real signal's rows first.  A returned feature
@@ -60,12 +72,39 @@ def _map_to_rows(g, B, p):
     return t.view(B * p, t.shape[2], t.shape[3])
 
 
+def _all_rows(g_real, g_gen, shape, like):
+    """The gradient over all rows [real; generated] of a chain from the two halves' (either may be None: zeros)."""
+    R, Cc, H = shape
+    halves = [torch.zeros(R // 2, Cc, H, dtype=torch.float32, device=like.device) if g is None else g.reshape(R // 2, Cc, H) for g in (g_real, g_gen)]
+    return torch.cat(halves, 0)
+
+
+def _chain_bwd(descr, maps, dz, adds, want, to_first, sentinel):
+    """The backward of layers n - 1 .. 1 of one chain over the rows of `maps`.  descr[i] = (dgrad, operand, K, stride, pad, groups);
+    maps[i - 1]: the input of layer i; dz: the gradient at the last layer's output; adds[i - 1]: what arrives at map i - 1 from outside
+    (or None); want[i] = (weight?, bias?).  Per layer the weight / bias gradient, then the input gradient -- the walk stops where
+    nothing below wants one (`to_first`: the first layer does).  -> (dz at the first layer's pre-activation or None, [(dW, db)])."""
+    n = len(descr)
+    grads = [(None, None)] * n
+    for i in range(n - 1, 0, -1):
+        run, op, K, s, pad, groups = descr[i]
+        f_in = maps[i - 1]
+        wdw, wdb = want[i]
+        if wdw or wdb:
+            grads[i] = ops.gconv1d_wgrad(dz, f_in, K, stride=s, pad=pad, groups=groups, want_dw=wdw, want_db=wdb, sentinel=sentinel)
+        if not (to_first or any(a or b for a, b in want[1:i])):
+            return None, grads
+        dz = run(dz, op, f_in.shape[2], stride=s, pad=pad, f_in=f_in, add=adds[i - 1], slope=LRELU_SLOPE, sentinel=sentinel)
+    return dz, grads
+
+
 class _DiscPFn(torch.autograd.Function):
     """One sub-discriminator on both signals.  Outputs: the generated score and six generated maps (differentiable in y_hat), then the
-    real score and maps (not differentiable)."""
+    real score and maps (not differentiable).  With the discriminator's parameters behind the four fixed inputs (trainable_): the
+    real score is differentiable too and the backward also yields the parameters' gradients."""
 
     @staticmethod
-    def forward(ctx, y_hat, y, mod, sentinel):
+    def forward(ctx, y_hat, y, mod, sentinel, *params):
         B, T = y_hat.shape
         p = mod.period
         convs = mod._layers()
@@ -76,18 +115,65 @@ class _DiscPFn(torch.autograd.Function):
         Rg = B * p
         gen = [m[Rg:] for m in maps]
         real = [m[:Rg] for m in maps]
-        ctx.mod, ctx.sentinel, ctx.dims = mod, sentinel, (B, T, p)
-        ctx.save_for_backward(*gen[:-1])
+        ctx.mod, ctx.sentinel, ctx.dims, ctx.n_params = mod, sentinel, (B, T, p), len(params)
+        if params:
+            ctx.set_materialize_grads(False)
+            ctx.save_for_backward(*maps[:-1], y, y_hat, *params)
+        else:
+            ctx.save_for_backward(*gen[:-1])
         outs_g = [_rows_to_map(m, B, p) for m in gen]
         outs_r = [_rows_to_map(m, B, p) for m in real]
         score_g, score_r = outs_g[-1].reshape(B, -1), outs_r[-1].reshape(B, -1)
-        ctx.mark_non_differentiable(score_r, *outs_r)
+        if params:
+            ctx.mark_non_differentiable(*outs_r)
+        else:
+            ctx.mark_non_differentiable(score_r, *outs_r)
         return (score_g, *outs_g, score_r, *outs_r)
+
+    @staticmethod
+    def _backward_trainable(ctx, g_score, g_maps, g_score_r):
+        """The discriminator step's backward: the dgrad chain over all 2 B p rows, each layer's weight / bias gradient from the same dz,
+        the weight-norm fold's backward, and d / d y_hat only when it is asked for."""
+        B, T, p = ctx.dims
+        n_par = ctx.n_params
+        none = (None,) * (4 + n_par)
+        if g_score is None and g_score_r is None and all(g is None for g in g_maps):
+            return none
+        saved = ctx.saved_tensors
+        maps, y, y_hat, params = saved[:5], saved[5], saved[6], saved[7:]
+        need = ctx.needs_input_grad
+        convs = ctx.mod._layers()
+        Rg, dev = B * p, y.device
+        H6 = ops.sconv_out_len(maps[4].shape[2], convs[5][0].K, convs[5][2], convs[5][3])
+
+        def rows_of_score(g):
+            return None if g is None else g.reshape(B, -1, p).permute(0, 2, 1).reshape(Rg, 1, -1)
+        dz_g = None if g_maps[5] is None else _map_to_rows(g_maps[5], B, p)
+        gs = rows_of_score(g_score)
+        dz_g = gs if dz_g is None else (dz_g if gs is None else dz_g + gs)
+        dz = _all_rows(rows_of_score(g_score_r), dz_g, (2 * Rg, 1, H6), y)
+        adds = [None if g is None else _all_rows(None, _map_to_rows(g, B, p), tuple(maps[i].shape), y) for i, g in enumerate(g_maps[:5])]
+        want = [(need[4 + 3 * i] or need[5 + 3 * i], need[6 + 3 * i]) for i in range(6)]
+        descr = [None] + [(ops.sconv1d_dgrad, cw, cw.K, s, pad, 1) for cw, _b, s, pad, _act in convs[1:]]
+        dz, grads = _chain_bwd(descr, maps, dz, adds, want, need[0] or any(want[0]), ctx.sentinel)
+        cw0, _b0, s0, pad0, _a0 = convs[0]
+        if any(want[0]):
+            grads[0] = ops.mpd_fold_conv_wgrad(dz, y, y_hat, p, cw0.K, stride=s0, pad=pad0, want_dw=want[0][0], want_db=want[0][1], sentinel=ctx.sentinel)
+        g_wav = ops.mpd_fold_conv_bwd(dz[Rg:], cw0.raw(), B, T, p, stride=s0, pad=pad0, sentinel=ctx.sentinel) if need[0] else None
+        out = [g_wav, None, None, None]
+        for i, (dw, db) in enumerate(grads):
+            g, v = params[3 * i], params[3 * i + 1]
+            dg, dv = (None, None) if dw is None else ops.weight_norm_fold_bwd(dw, g, v, want_dg=need[4 + 3 * i], want_dv=need[5 + 3 * i],
+                                                                              sentinel=ctx.sentinel)
+            out += [dg, dv, db]
+        return tuple(out)
 
     @staticmethod
     def backward(ctx, g_score, *rest):
         B, T, p = ctx.dims
         g_maps = list(rest[:6])
+        if ctx.n_params:
+            return _DiscPFn._backward_trainable(ctx, g_score, g_maps, rest[6])
         if g_score is None and all(g is None for g in g_maps):
             return None, None, None, None
         saved = ctx.saved_tensors
@@ -133,6 +219,21 @@ class DiscriminatorP(nn.Module):
         for q in self.parameters():
             q.requires_grad_(False)
         self._wn = [_WNConv2d(m) for m in list(self.convs) + [self.conv_post]]
+        self._trainable = False
+
+    def trainable_(self, flag=True):
+        """Opt in to (or out of) the discriminator step: the parameters require grad, become inputs of the autograd node and get
+        `.grad` from a backward through the scores (real and generated); the real MAPS stay targets.  Without it nothing changes."""
+        self._trainable = bool(flag)
+        for q in self.parameters():
+            q.requires_grad_(self._trainable)
+        return self
+
+    def _params(self):
+        """The node's parameter inputs while trainable: (weight_g, weight_v, bias) per layer."""
+        if not (self._trainable and torch.is_grad_enabled()):
+            return ()
+        return tuple(q for m in list(self.convs) + [self.conv_post] for q in (m.weight_g, m.weight_v, m.bias))
 
     def _layers(self):
         """[(ConvWeight, bias, stride, pad, leaky ReLU?)] of the six layers."""
@@ -140,7 +241,7 @@ class DiscriminatorP(nn.Module):
         return [(wn.conv_weight(), m.bias.data, m.stride[0], m.padding[0], i < 5) for i, (wn, m) in enumerate(zip(self._wn, mods))]
 
     def _check_weights(self):
-        if torch.is_grad_enabled():
+        if torch.is_grad_enabled() and not self._trainable:
             for name, q in self.named_parameters():
                 if q.requires_grad:
                     raise RuntimeError("%s requires grad: the discriminator's weight gradients are not built (only d/d y_hat is); "
@@ -149,7 +250,7 @@ class DiscriminatorP(nn.Module):
     def forward(self, y, y_hat, mel=None, sentinel=None):
         y2, yh2 = _check_waves(y, y_hat)
         self._check_weights()
-        outs = _DiscPFn.apply(yh2, y2, self, sentinel)
+        outs = _DiscPFn.apply(yh2, y2, self, sentinel, *self._params())
         return outs[7], outs[0], list(outs[8:14]), list(outs[1:7])
 
 
@@ -165,6 +266,13 @@ def _check_waves(y, y_hat):
         raise ValueError("y and y_hat must be equal [B, T] or [B, 1, T], got %s and %s" % (tuple(y.shape), tuple(y_hat.shape)))
     B, T = y.shape[0], y.shape[-1]
     return y.reshape(B, T).contiguous(), y_hat.reshape(B, T).contiguous()
+
+
+def _trainable_all(self, flag=True):
+    """trainable_ of every sub-discriminator (see DiscriminatorP.trainable_)."""
+    for d in self.discriminators:
+        d.trainable_(flag)
+    return self
 
 
 class _FanOut(torch.autograd.Function):
@@ -194,6 +302,8 @@ class MultiPeriodDiscriminator(nn.Module):
         super().__init__()
         self.discriminators = nn.ModuleList([DiscriminatorP(p, use_cond=use_cond, c_in=c_in, channels=channels) for p in PERIODS])
 
+    trainable_ = _trainable_all
+
     def forward(self, y, y_hat, mel=None, sentinel=None):
         y2, yh2 = _check_waves(y, y_hat)
         n = len(self.discriminators)
@@ -201,7 +311,7 @@ class MultiPeriodDiscriminator(nn.Module):
         y_d_rs, y_d_gs, fmap_rs, fmap_gs = [], [], [], []
         for d, yh in zip(self.discriminators, fan):
             d._check_weights()
-            outs = _DiscPFn.apply(yh, y2, d, sentinel)
+            outs = _DiscPFn.apply(yh, y2, d, sentinel, *d._params())
             y_d_rs.append(outs[7])
             y_d_gs.append(outs[0])
             fmap_rs.append(list(outs[8:14]))
@@ -312,11 +422,38 @@ class _SConv:
             return W, ops.ConvWeight(W, self.cout, self.cin, self.K)
         return W, ops.GroupedConvWeight(W, self.cout, self.cin, self.K, self.groups)
 
-    def _sigma_fold(self):
+    def _sigma(self):
         m = self.mod
         w = m.weight_orig
-        sigma = torch.dot(m.weight_u, torch.mv(w.reshape(w.shape[0], -1), m.weight_v))
-        return w / sigma
+        return torch.dot(m.weight_u, torch.mv(w.reshape(w.shape[0], -1), m.weight_v))
+
+    def _sigma_fold(self):
+        return self.mod.weight_orig / self._sigma()
+
+    def sn_state(self):
+        """(u, v, sigma) as they stand, copied: what the spectral-norm fold's backward needs of the forward that just ran (the
+        buffers move in place with the next power iteration)."""
+        m = self.mod
+        with torch.no_grad():
+            return m.weight_u.clone(), m.weight_v.clone(), self._sigma().reshape(1)
+
+    def params(self):
+        """The autograd node's inputs for this conv: (weight_orig, bias) or (weight_g, weight_v, bias)."""
+        m = self.mod
+        return (m.weight_orig, m.bias) if self.spectral else (m.weight_g, m.weight_v, m.bias)
+
+    def fold_bwd(self, dw, state, need, out, sentinel):
+        """dW -> the gradients of this conv's weight parameters, in params() order.  Spectral norm: `state` = (u, v, sigma) of the
+        forward; `out`: the back-projection so far (the other half's), to add to."""
+        if dw is None:
+            return [out] if self.spectral else [None, None]
+        m = self.mod
+        if self.spectral:
+            u, v, sigma = state
+            return [ops.spectral_norm_fold_bwd(dw, m.weight_orig.detach().contiguous(), u, v, sigma, out=out, accumulate=out is not None,
+                                               sentinel=sentinel)]
+        return list(ops.weight_norm_fold_bwd(dw, m.weight_g.detach().contiguous(), m.weight_v.detach().contiguous(), want_dg=need[0],
+                                             want_dv=need[1], sentinel=sentinel))
 
     def fixed(self):
         """(weight, operand) of a weight-normed conv, or of a spectrally normed one in eval(): cached per weight version."""
@@ -354,29 +491,114 @@ class _DiscSFn(torch.autograd.Function):
     """One DiscriminatorS on both signals.  Outputs: the generated score and maps (differentiable in y_hat), then the real ones (not)."""
 
     @staticmethod
-    def forward(ctx, y_hat, y, mod, sentinel):
+    def forward(ctx, y_hat, y, mod, sentinel, *params):
         B, T = y_hat.shape
         convs = mod._convs
         n = len(convs)
-        if mod.use_spectral_norm and mod.training:   # the reference's two calls: real first, then generated, one power iteration each
+        sn = mod.use_spectral_norm
+        w_real = st_real = st_gen = maps = None
+        if sn and mod.training:   # the reference's two calls: real first, then generated, one power iteration each
             w_real = [c.power_step() for c in convs]
+            st_real = [c.sn_state() for c in convs] if params else None
             real = _disc_s_run(convs, w_real, y, None, sentinel)
             w_gen = [c.power_step() for c in convs]
+            st_gen = [c.sn_state() for c in convs] if params else None
             gen = _disc_s_run(convs, w_gen, y_hat, None, sentinel)
         else:
             w_gen = [c.fixed() for c in convs]
+            st_gen = [c.sn_state() for c in convs] if params and sn else None
             maps = _disc_s_run(convs, w_gen, y, y_hat, sentinel)
             real, gen = [m[:B] for m in maps], [m[B:] for m in maps]
-        ctx.convs, ctx.weights, ctx.sentinel, ctx.n = convs, w_gen, sentinel, n
-        ctx.save_for_backward(*gen[:-1])
+        ctx.convs, ctx.weights, ctx.sentinel, ctx.n, ctx.n_params = convs, w_gen, sentinel, n, len(params)
         score_g, score_r = gen[-1].reshape(B, -1), real[-1].reshape(B, -1)
-        ctx.mark_non_differentiable(score_r, *real)
+        if params:
+            ctx.set_materialize_grads(False)
+            ctx.halves, ctx.weights_real, ctx.states = maps is None, w_real, (st_real, st_gen)
+            ctx.save_for_backward(*(real[:-1] + gen[:-1] if maps is None else maps[:-1]), y, y_hat, *params)
+            ctx.mark_non_differentiable(*real)
+        else:
+            ctx.save_for_backward(*gen[:-1])
+            ctx.mark_non_differentiable(score_r, *real)
         return (score_g, *gen, score_r, *real)
+
+    @staticmethod
+    def _backward_trainable(ctx, g_score, g_maps, g_score_r):
+        """The discriminator step's backward.  One chain over all 2 B rows; a spectrally normed net in train() ran its halves with
+        different weights and different u, v, so there the chain, the weight gradients and the fold's back-projection run per half and
+        weight_orig.grad is the sum of the two back-projections, the real half's first."""
+        n, n_par, convs, sentinel = ctx.n, ctx.n_params, ctx.convs, ctx.sentinel
+        if g_score is None and g_score_r is None and all(g is None for g in g_maps):
+            return (None,) * (4 + n_par)
+        saved = ctx.saved_tensors
+        n_maps = 2 * (n - 1) if ctx.halves else n - 1
+        y, y_hat = saved[n_maps], saved[n_maps + 1]
+        B = y.shape[0]
+        need = ctx.needs_input_grad
+        first, want = [], []
+        at = 4
+        for c in convs:
+            k = len(c.params())
+            first.append(at)
+            want.append((any(need[at:at + k - 1]), need[at + k - 1]))
+            at += k
+        H_last = convs[-1].out_len(saved[n - 2].shape[2])
+        dz_g = None if g_maps[-1] is None else g_maps[-1].contiguous()
+        if g_score is not None:
+            gs = g_score.reshape(B, 1, H_last)
+            dz_g = gs.contiguous() if dz_g is None else dz_g + gs
+        dz_r = None if g_score_r is None else g_score_r.reshape(B, 1, H_last).contiguous()
+        adds_g = [None if g is None else g.contiguous() for g in g_maps[:-1]]
+
+        def descr(weights):
+            return [None] + [(ops.sconv1d_dgrad if c.kind == "dense" else ops.gconv1d_dgrad, w[1], c.K, c.stride, c.pad, c.groups)
+                             for c, w in zip(convs[1:], weights[1:])]
+        c0 = convs[0]
+        g_wav = None
+        runs = []   # per chain: ([(dW, db)], the forward's (u, v, sigma) per conv)
+        if not ctx.halves:
+            maps = saved[:n - 1]
+            dz = _all_rows(dz_r, dz_g, (2 * B, 1, H_last), y)
+            adds = [None if g is None else _all_rows(None, g, tuple(m.shape), y) for g, m in zip(adds_g, maps)]
+            dz, grads = _chain_bwd(descr(ctx.weights), maps, dz, adds, want, need[0] or any(want[0]), sentinel)
+            if any(want[0]):
+                grads[0] = ops.wave_conv_wgrad(dz, y, y_hat, c0.K, pad=c0.pad, want_dw=want[0][0], want_db=want[0][1], sentinel=sentinel)
+            if need[0]:
+                g_wav = ops.wave_conv_bwd(dz[B:], ctx.weights[0][0], pad=c0.pad, sentinel=sentinel)
+            runs.append((grads, ctx.states[1]))
+        else:
+            if dz_r is not None:
+                dz, grads = _chain_bwd(descr(ctx.weights_real), saved[:n - 1], dz_r, [None] * (n - 1), want, any(want[0]), sentinel)
+                if any(want[0]):
+                    grads[0] = ops.wave_conv_wgrad(dz, y, None, c0.K, pad=c0.pad, want_dw=want[0][0], want_db=want[0][1], sentinel=sentinel)
+                runs.append((grads, ctx.states[0]))
+            if dz_g is not None or any(a is not None for a in adds_g):
+                if dz_g is None:
+                    dz_g = torch.zeros(B, 1, H_last, dtype=torch.float32, device=y.device)
+                dz, grads = _chain_bwd(descr(ctx.weights), saved[n - 1:n_maps], dz_g, adds_g, want, need[0] or any(want[0]), sentinel)
+                if any(want[0]):
+                    grads[0] = ops.wave_conv_wgrad(dz, y_hat, None, c0.K, pad=c0.pad, want_dw=want[0][0], want_db=want[0][1], sentinel=sentinel)
+                if need[0]:
+                    g_wav = ops.wave_conv_bwd(dz, ctx.weights[0][0], pad=c0.pad, sentinel=sentinel)
+                runs.append((grads, ctx.states[1]))
+        out = [g_wav, None, None, None]
+        for i, c in enumerate(convs):
+            k = len(c.params())
+            gw, gb = [None] * (k - 1), None
+            for grads, states in runs:
+                dw, db = grads[i]
+                if dw is not None:
+                    gw = c.fold_bwd(dw, states[i] if states else None, need[first[i]:first[i] + k - 1], gw[0], sentinel)
+                if db is not None:
+                    gb = db if gb is None else gb + db
+            out += gw + [gb]
+        return tuple(out)
 
     @staticmethod
     def backward(ctx, g_score, *rest):
         n = ctx.n
         g_maps = list(rest[:n])
+        if ctx.n_params:
+            return _DiscSFn._backward_trainable(ctx, g_score, g_maps, rest[n])
         if g_score is None and all(g is None for g in g_maps):
             return None, None, None, None
         saved, convs, weights = ctx.saved_tensors, ctx.convs, ctx.weights
@@ -420,8 +642,16 @@ class DiscriminatorS(nn.Module):
             q.requires_grad_(False)
         mods = list(self.convs) + [self.conv_post]
         self._convs = [_SConv(m, self.use_spectral_norm, i < 7) for i, m in enumerate(mods)]
+        self._trainable = False
 
     _check_weights = DiscriminatorP._check_weights
+    trainable_ = DiscriminatorP.trainable_
+
+    def _params(self):
+        """The node's parameter inputs while trainable: per conv (weight_orig, bias) under spectral norm, else (weight_g, weight_v, bias)."""
+        if not (self._trainable and torch.is_grad_enabled()):
+            return ()
+        return tuple(q for c in self._convs for q in c.params())
 
     def _check_length(self, T):
         H = T
@@ -435,7 +665,7 @@ class DiscriminatorS(nn.Module):
         self._check_weights()
         self._check_length(y2.shape[1])
         n = len(self._convs)
-        outs = _DiscSFn.apply(yh2, y2, self, sentinel)
+        outs = _DiscSFn.apply(yh2, y2, self, sentinel, *self._params())
         return outs[n + 1], outs[0], list(outs[n + 2:2 * n + 2]), list(outs[1:n + 1])
 
 
@@ -467,6 +697,8 @@ class MultiScaleDiscriminator(nn.Module):
                                              for i in range(3)])
         self.meanpools = nn.ModuleList([nn.AvgPool1d(4, 2, padding=1), nn.AvgPool1d(4, 2, padding=1)])
 
+    trainable_ = _trainable_all
+
     def forward(self, y, y_hat, mel=None, sentinel=None):
         y2, yh2 = _check_waves(y, y_hat)
         T, D = y2.shape[1], len(self.discriminators)
@@ -485,7 +717,7 @@ class MultiScaleDiscriminator(nn.Module):
                 y_next = ops.avgpool4s2_fwd(y2, sentinel=sentinel)
             else:
                 yh_i, yh_next, y_next = yh2, None, None
-            outs = _DiscSFn.apply(yh_i, y2, d, sentinel)
+            outs = _DiscSFn.apply(yh_i, y2, d, sentinel, *d._params())
             y_d_rs.append(outs[n + 1])
             y_d_gs.append(outs[0])
             fmap_rs.append(list(outs[n + 2:2 * n + 2]))

@@ -1978,3 +1978,135 @@ def avgpool4s2_bwd(g_out, T, add=None, sentinel=None):
     g_in = _buf((B, T), g_out.device, sentinel)
     check(_lib.lib().set_avgpool4s2_bwd(_p(g_out), _p(add), _p(g_in), B, int(T), _stream()), "set_avgpool4s2_bwd")
     return g_in
+
+
+# --------------------------------------------------------------------------
+# the discriminator step (csrc/disc_wgrad.hip): weight and bias gradients of the discriminators' convs, the backward of the norm folds
+# --------------------------------------------------------------------------
+GCONV_WGRAD_CHUNK, GCONV_WGRAD_COLS, GCONV_WGRAD_MAX_SLICES, FIRST_WGRAD_MAX_SLICES = 32, 128, 64, 64
+
+
+def gconv_wgrad_plan(R, Cin, Cout, groups, H_in, K, stride, pad, n_cu=0):
+    """The number of reduction slices set_gconv1d_wgrad takes at `slices` = 0 (set_gconv1d_wgrad_plan); n_cu 0: the current device's."""
+    n = _lib.lib().set_gconv1d_wgrad_plan(int(R), int(Cin), int(Cout), int(groups), int(H_in), int(K), int(stride), int(pad), int(n_cu))
+    if n < 0:
+        check(n, "set_gconv1d_wgrad_plan")
+    return n
+
+
+def _grad_out(t, shape, dev, accumulate, sentinel, name):
+    """The buffer a gradient is written to (new, `sentinel`-filled for the tests) or added to (`t`, which accumulate requires)."""
+    if t is None:
+        if accumulate:
+            raise ValueError("%s: accumulate needs the tensor to add to" % name)
+        return _buf(shape, dev, sentinel)
+    _f(t, name)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def gconv1d_wgrad(dz, x, K, *, stride, pad, groups=1, want_dw=True, want_db=False, dw=None, db=None, accumulate=False, slices=0, sentinel=None):
+    """set_gconv1d_wgrad: dz [R,Cout,H_out], x [R,Cin,H_in] -> (dW [Cout, Cin / groups, K] or None, db [Cout] or None).  `dw` / `db`:
+    tensors to write or, with accumulate, to add to.  slices 0: the plan's."""
+    _rows3(dz, "dz"), _rows3(x, "x")
+    R, Cout, H_out = dz.shape
+    _R, Cin, H_in = x.shape
+    K, groups = int(K), int(groups)
+    if _R != R or Cin % groups or Cout % groups or not 1 <= K <= GCONV_KMAX or H_out != gconv_out_len(H_in, K, stride, pad):
+        raise ValueError("gconv1d_wgrad: dz %s and x %s do not belong to one (K = %d, stride %d, pad %d, groups %d) layer"
+                         % (tuple(dz.shape), tuple(x.shape), K, stride, pad, groups))
+    if not (want_dw or want_db):
+        return None, None
+    L = _lib.lib()
+    dev = dz.device
+    dw = _grad_out(dw, (Cout, Cin // groups, K), dev, accumulate, sentinel, "dw") if want_dw else None
+    db = _grad_out(db, (Cout,), dev, accumulate, sentinel, "db") if want_db else None
+    scratch, n = None, 0
+    if want_dw:
+        if slices == 0:
+            slices = gconv_wgrad_plan(R, Cin, Cout, groups, H_in, K, stride, pad)
+        if slices != 1 or accumulate:
+            n = L.set_gconv1d_wgrad_scratch_floats(R, Cin, Cout, groups, H_in, K, int(stride), int(pad), int(slices))
+            if n < 0:
+                check(n, "set_gconv1d_wgrad_scratch_floats")
+            scratch = _buf((n,), dev, sentinel)
+    check(L.set_gconv1d_wgrad(_p(dz), _p(x), _p(dw), _p(db), R, Cin, Cout, groups, H_in, K, int(stride), int(pad), int(bool(accumulate)), int(slices),
+                              _p(scratch), n, _stream()), "set_gconv1d_wgrad")
+    return dw, db
+
+
+def _first_part(Cc, K, slices, dev, sentinel):
+    n = _lib.lib().set_first_conv_wgrad_part_doubles(int(Cc), int(K), int(slices))
+    if n < 0:
+        check(n, "set_first_conv_wgrad_part_doubles")
+    part = torch.empty(n, dtype=torch.float64, device=dev)
+    return (part if sentinel is None else part.fill_(sentinel)), n
+
+
+def mpd_fold_conv_wgrad(dz, y, y_hat, period, K, *, stride, pad, want_dw=True, want_db=True, dw=None, db=None, accumulate=False, slices=0,
+                        sentinel=None):
+    """set_mpd_fold_conv_wgrad: dz [2 B p, C, H_out] (all rows), y, y_hat [B, T] -> (dW [C, K] or None, db [C] or None)."""
+    _rows3(dz, "dz"), _f(y, "y"), _f(y_hat, "y_hat")
+    if y.dim() != 2 or y.shape != y_hat.shape:
+        raise ValueError("mpd_fold_conv_wgrad: y and y_hat must be equal [B, T], got %s and %s" % (tuple(y.shape), tuple(y_hat.shape)))
+    B, T = y.shape
+    R, Cc, H_out = dz.shape
+    if T <= period or R != 2 * B * period or H_out != sconv_out_len((T + period - 1) // period, K, stride, pad):
+        raise ValueError("mpd_fold_conv_wgrad: dz %s does not belong to period %d on %s" % (tuple(dz.shape), period, tuple(y.shape)))
+    if not (want_dw or want_db):
+        return None, None
+    dw = _grad_out(dw, (Cc, K), dz.device, accumulate, sentinel, "dw") if want_dw else None
+    db = _grad_out(db, (Cc,), dz.device, accumulate, sentinel, "db") if want_db else None
+    part, n = _first_part(Cc, K, slices, dz.device, sentinel)
+    check(_lib.lib().set_mpd_fold_conv_wgrad(_p(dz), _p(y), _p(y_hat), _p(dw), _p(db), B, T, int(period), Cc, int(K), int(stride), int(pad),
+                                             int(bool(accumulate)), int(slices), _p(part), n, _stream()), "set_mpd_fold_conv_wgrad")
+    return dw, db
+
+
+def wave_conv_wgrad(dz, y, y_hat, K, *, pad, want_dw=True, want_db=True, dw=None, db=None, accumulate=False, slices=0, sentinel=None):
+    """set_wave_conv_wgrad: dz [2 B, C, T] (all rows; [B, C, T] with y_hat None), y, y_hat [B, T] -> (dW [C, K] or None, db [C] or None)."""
+    _rows3(dz, "dz"), _f(y, "y"), _f(y_hat, "y_hat")
+    B, T = y.shape
+    R, Cc, H = dz.shape
+    if y.dim() != 2 or (y_hat is not None and y_hat.shape != y.shape) or R != (1 if y_hat is None else 2) * B or H != T:
+        raise ValueError("wave_conv_wgrad: dz %s does not belong to waveforms %s" % (tuple(dz.shape), tuple(y.shape)))
+    if not (want_dw or want_db):
+        return None, None
+    dw = _grad_out(dw, (Cc, K), dz.device, accumulate, sentinel, "dw") if want_dw else None
+    db = _grad_out(db, (Cc,), dz.device, accumulate, sentinel, "db") if want_db else None
+    part, n = _first_part(Cc, K, slices, dz.device, sentinel)
+    check(_lib.lib().set_wave_conv_wgrad(_p(dz), _p(y), _p(y_hat), _p(dw), _p(db), B, T, Cc, int(K), int(pad), int(bool(accumulate)), int(slices),
+                                         _p(part), n, _stream()), "set_wave_conv_wgrad")
+    return dw, db
+
+
+def weight_norm_fold_bwd(dw, g, v, *, want_dg=True, want_dv=True, sentinel=None):
+    """set_weight_norm_fold_bwd: dW (v's shape), g, v -> (dg (g's shape) or None, dv or None)."""
+    _f(dw, "dw"), _f(g, "g"), _f(v, "v")
+    n0 = v.shape[0]
+    if dw.numel() != v.numel() or g.numel() != n0:
+        raise ValueError("weight_norm_fold_bwd: dW %s, g %s, v %s" % (tuple(dw.shape), tuple(g.shape), tuple(v.shape)))
+    if not (want_dg or want_dv):
+        return None, None
+    dg = _buf(tuple(g.shape), v.device, sentinel) if want_dg else None
+    dv = _buf(tuple(v.shape), v.device, sentinel) if want_dv else None
+    check(_lib.lib().set_weight_norm_fold_bwd(_p(dw), _p(g), _p(v), _p(dg), _p(dv), n0, v.numel() // n0, 0, _stream()), "set_weight_norm_fold_bwd")
+    return dg, dv
+
+
+def spectral_norm_fold_bwd(dw, w_orig, u, v, sigma, *, out=None, accumulate=False, sentinel=None):
+    """set_spectral_norm_fold_bwd: dW, weight_orig [n0, ...], u [n0], v [inner], sigma (a device scalar) -> d weight_orig (written to
+    or, with accumulate, added to `out`)."""
+    _f(dw, "dw"), _f(w_orig, "w_orig"), _f(u, "u"), _f(v, "v"), _f(sigma, "sigma")
+    n0 = w_orig.shape[0]
+    inner = w_orig.numel() // n0
+    if dw.numel() != w_orig.numel() or u.numel() != n0 or v.numel() != inner or sigma.numel() != 1:
+        raise ValueError("spectral_norm_fold_bwd: dW %s, weight_orig %s, u %s, v %s" % (tuple(dw.shape), tuple(w_orig.shape), tuple(u.shape), tuple(v.shape)))
+    out = _grad_out(out, tuple(w_orig.shape), w_orig.device, accumulate, sentinel, "out")
+    part = torch.empty(n0, dtype=torch.float64, device=w_orig.device)
+    if sentinel is not None:
+        part.fill_(sentinel)
+    check(_lib.lib().set_spectral_norm_fold_bwd(_p(dw), _p(w_orig), _p(u), _p(v), _p(sigma), _p(out), n0, inner, int(bool(accumulate)), _p(part), _stream()),
+          "set_spectral_norm_fold_bwd")
+    return out
