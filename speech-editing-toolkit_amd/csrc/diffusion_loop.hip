@@ -372,6 +372,9 @@ extern "C" int set_diffusion_loop(const SetDiffLoopArgs *args, void *stream) {
                     a.w_outp_p && a.b_outp, "set_diffusion_loop");
     if (a.img16_all) {
         SET_REQUIRE(a.cond && a.b_cond_all, "set_diffusion_loop(bf16 loop needs cond and b_cond_all)");
+        // the bf16 layer kernels take dilations up to 8: refuse a longer cycle here, before the in-projection and the first layers are
+        // enqueued (set_diffnet_layer_fwd_bf16 would refuse layer 4 with x's workspaces half written); stack_validate asks the same
+        SET_REQUIRE(a.dilation_cycle_length <= 4, "set_diffusion_loop(bf16 loop: dilation_cycle_length <= 4)");
     } else {
         SET_REQUIRE(a.condproj && a.w1p_all && a.w2p_all, "set_diffusion_loop");
         SET_REQUIRE(!a.persistent || a.sync_ws, "set_diffusion_loop(persistent needs sync_ws)");

@@ -22,8 +22,10 @@ the same case under SET_AMD_BOUNDARY_X2=0.
             bf16x3 within e32 + 1e-7); utterance groups bit-identical to one group in every buffer; the Philox seed delta.
   the range word of the two-piece boundary (err_flag = 2) raised through x', s and h.
 
-Not swept, on purpose: the opt-in bf16 layer bodies (their own tests cover them; the boundary they run with is the two-piece one swept
-here), layer_span_ms timing, the 2 GiB offset limits."""
+Swept elsewhere: the two opt-in bf16 step bodies (SetDiffLoopArgs.img16_all: one layer or a group of layers per launch, the host code
+that composes them, every boundary form behind them) in tests/test_gpu_bf16_loop_branches.py, which reuses this file's plumbing; that
+file also checks that layer_span_ms and loop_ms are written (finite, > 0) and change no bit of any buffer.  Not swept, on purpose: the
+VALUES of the timing outputs (no time is compared with another), the 2 GiB offset limits."""
 import ctypes as C
 import math
 
